@@ -14,11 +14,22 @@ device memory.  Weak scaling: per-GPU work is fixed.  `--tracks 1` i
 (one 4K frame per GPU per step); the default keeps 16 tracks per GPU so that one step exceeds the Infinity Cache.
 
 Before the W warm-up steps the device is woken up with ~60 ms of the same launch (clock / power ramp; not part of the
-schedule).  Prints ONE JSON line on rank 0 (contract in the task statement), including
+schedule).  Prints ONE JSON line on rank 0: metric, value (frames/s over the --steps timed steps), unit, higher_is_better, dtype,
+ms_per_step (wall milliseconds of one timed step) and the workload's config.  A plain run does nothing else: set up, wake up, warm up,
+time the steps, write the outputs (--dump-outputs DIR) and print the line.  `--full` adds every other measurement, each after the timed
+steps and outside them:
   roofline     : algorithmic bytes / launch  divided by  the kernel's average launch duration, measured live with
-                 HIP events on the launch stream (lgpu_chain_timed), against the 8 TB/s HBM3E peak
+                 HIP events on the launch stream (lgpu_chain_timed), against the 8 TB/s HBM3E peak, and the box's bare stream rate
+  batch8       : the 8-track launch on one GPU (the denominator of the 8-GPU aggregate), with and without the gaussian
+  config5      : launched jobs (and --config5): the one-frame-per-GPU steps through the C stepper
+  seam_chain   : the same chain through the reference's API from C host threads (N = 1)
   cpu_baseline : the CPU oracle (a port of the reference path; oracle/) timed on this host's cores on a
-                 bounded sample of the same workload (rank 0, N = 1 only)
+                 bounded sample of the same workload (rank 0, N = 1 only; --no-cpu skips it)
+
+--dump-outputs DIR writes what the timed path computed in its last step (rank 0's destination frames) as float32 .npy files, at most
+64 MB in all: dst_track0.npy, the first track's whole frame [DH, DW, 4]; dst_sample.npy, a fixed seeded sample of the byte positions of
+every track's frame [T, K] (dst_sample_index.npy holds the positions, as float64); dst_row_sums.npy, every track's per-row, per-channel
+sums [T, DH, 4] (exact in float32), which every output byte enters.  The inputs are seeded: the same arguments give the same inputs.
 """
 import argparse
 import ctypes
@@ -60,6 +71,12 @@ def main():
     ap.add_argument("--no-seam", action="store_true", help="skip the seam_chain leg (a profiled run then holds the launches behind `value` only under the headline kernel's name)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch / rendezvous / reduce / print path only, on the gloo backend with no GPU work (tests/test_dist_cpu.py runs this on a CPU box)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, every other measurement as well: roofline and stream probe, the 8-track batch, the config-5 legs of launched jobs, "
+                         "the seam_chain leg, the cpu_baseline (a plain run times the steps and prints the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's destinations: one whole frame, a seeded sample and row sums of every track) "
+                         "as float32 DIR/<name>.npy, at most 64 MB in all")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -230,18 +247,22 @@ def main():
     frames = world * T * args.steps
     fps = frames / dt
 
+    # what the last timed step wrote, before any leg of --full launches into the same destinations
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, keep[(args.warmup + args.steps - 1) % nsets][2])
+
     # N > 1: BASELINE config 5's own shape as well -- ONE 4K frame per GPU per step, the exchange on -- through the same C step: once on the chain of the headline
     # (north_star's convert -> resize -> blend -> gamma) and once with config 5's 5x5 gaussian between the scaler and the blend
     prm_blur = prm if args.blur else ops.chain_params(SW, SH, SW * 4, DW, DH, DW * 4, DW * 4, swap_rb=1, interp=3 | (0x100 if args.resize_backend == "pixbuf" else 0), do_blur=1, bf=128, lut=lut,
                                                       param_block=pblock)
     config5 = None
-    # every rank count of a launched job (the driver's scaling run starts N = 1 under torch.distributed.run as well): at N = 1 the same C step without a communicator.
-    # NOT in the plain `python bench.py`: its ~2,000 one-frame launches carry the 16-track launch's kernel name and would drag the average rocprofv3 --stats prints for it
-    # away from roofline.launch_us (`--config5` asks for the leg there)
-    if stepper is not None or (not multi and (args.config5 or "WORLD_SIZE" in os.environ)):
-        if stepper is not None:
-            stepper.close()
-        stepper = None
+    # with --full, every rank count of a launched job (the driver's scaling run starts N = 1 under torch.distributed.run as well): at N = 1 the same C step without a
+    # communicator.  NOT in the unlaunched `python bench.py --full`: its ~2,000 one-frame launches carry the 16-track launch's kernel name and would drag the average
+    # rocprofv3 --stats prints for it away from roofline.launch_us (`--config5` asks for the leg there, with or without --full)
+    if stepper is not None:
+        stepper.close()
+    stepper = None
+    if (args.full or args.config5) and (comm is not None or (not multi and (args.config5 or "WORLD_SIZE" in os.environ))):
         one = groups_of(1)                    # every frame of every buffer set in turn: the one-frame launches, too, see buffers the memory-side cache has long lost
         n5 = max(args.steps, 200)
 
@@ -277,94 +298,94 @@ def main():
             d5b = one_frame_leg(prm_blur)
             config5.update({"config5_blur_fps": round(world * n5 / d5b, 1), "config5_blur_ms_per_step": round(d5b / n5 * 1e3, 4)})
 
-    # ---- roofline of the dominant kernel: HIP events on the launch stream around K launches ----
-    reps = max(10, min(args.steps, 200))
-    if nsets == 1:
-        ms = ops.chain_timed(prm, trk, reps)       # the library's own event pair (hipEventRecord on the launch stream around `reps` launches)
-    else:                                          # the same, around launches that rotate through the buffer sets: ops.chain launches on torch's current stream,
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)    # which is the stream these events are recorded on
-        prm.param_block_d = sched_base if world == 1 else pblock.data_ptr()
-        e0.record()
-        for i in range(reps):
-            ops.chain(prm, trks[i % nsets])
-        e1.record()
-        torch.cuda.synchronize()
-        ms = e0.elapsed_time(e1)
-    launch_s = ms * 1e-3 / reps
-    algo = ALGO_BYTES_PER_FRAME * T
-    achieved = algo / launch_s / 1e9
-    traffic, traffic_source = None, None
-    try:   # HBM bytes per launch from the PMC passes of this round's build on this exact workload (tools/pmc.sh + tools/pmc_traffic.py -> profiles/pmc_traffic*.json, which names the commit)
-        tf = "pmc_traffic_pixbuf.json" if args.resize_backend == "pixbuf" else "pmc_traffic.json"
-        with open(os.path.join(ROOT, "profiles", tf)) as f:
-            pj = json.load(f)
-        if pj.get("tracks") == T and pj.get("blur") == args.blur:
-            traffic = pj.get("hbm_bytes_per_launch")
-            traffic_source = "profiles/%s@%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of that commit's build; not measured in this run)" % (tf, pj.get("commit"))
-    except (OSError, ValueError):
-        pass
-
-    # the denominator of "aggregate at 8 GPUs on an 8-track batch": the same 8 tracks as ONE launch on ONE GPU (every rank measures its own; rank 0's is printed)
-    batch8 = None
-    if T >= 8:
-        prm.param_block_d = sched_base if world == 1 else pblock.data_ptr()
-        t8 = groups_of(8)                     # 16 tracks x 2 sets = four 8-track groups, 1.6 GB: with two groups the 256 MiB memory-side cache still holds part of a group when its turn
-        for i in range(10):                   # comes again (tools/sets_ab.sh, profiles/r04/sets_ab.txt: 8 tracks 69 us over two groups, 82 us over four or more; 16 tracks 156 us either way)
-            ops.chain(prm, t8[i % len(t8)])
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        n8 = 20          # few launches: they carry the same kernel name as the 16-track launch in a rocprofv3 --stats run (30 of ~1,600: the average moves by < 1 %)
-        e0.record()
-        for i in range(n8):
-            ops.chain(prm, t8[i % len(t8)])
-        e1.record()
-        torch.cuda.synchronize()
-        us8 = e0.elapsed_time(e1) * 1e3 / n8
-        batch8 = {"batch8_1gpu_fps": round(8e6 / us8, 1), "batch8_1gpu_us_per_step": round(us8, 2), "batch8_groups_rotated": len(t8)}
-        if args.resize_backend == "pixbuf" and not args.blur:      # the same with config 5's gaussian in the chain
-            prm_blur.param_block_d = prm.param_block_d
-            for i in range(6):
-                ops.chain(prm_blur, t8[i % len(t8)])
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    # ---- --full: everything else this benchmark measures, after the timed steps and outside them ----
+    roof, batch8, seam = None, None, None
+    if args.full:
+        # ---- roofline of the dominant kernel: HIP events on the launch stream around K launches ----
+        reps = max(10, min(args.steps, 200))
+        if nsets == 1:
+            ms = ops.chain_timed(prm, trk, reps)       # the library's own event pair (hipEventRecord on the launch stream around `reps` launches)
+        else:                                          # the same, around launches that rotate through the buffer sets: ops.chain launches on torch's current stream,
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)    # which is the stream these events are recorded on
+            prm.param_block_d = sched_base if world == 1 else pblock.data_ptr()
             e0.record()
-            for i in range(n8):
-                ops.chain(prm_blur, t8[i % len(t8)])
+            for i in range(reps):
+                ops.chain(prm, trks[i % nsets])
             e1.record()
             torch.cuda.synchronize()
-            batch8["batch8_blur_1gpu_us_per_step"] = round(e0.elapsed_time(e1) * 1e3 / n8, 2)
-            # ... and on frames whose alpha is 255 everywhere (decoded video), with the caller's word for it (LGPU_INTERP_OPAQUE): the lighter instantiation, same bytes
-            opq = []
-            for srcs, l2s, dsts in keep:
-                for i in range(0, T - 7, 8):
-                    o_s = [t.clone() for t in srcs[i:i + 8]]
-                    for t in o_s:
-                        t[:, 3::4] = 255
-                    opq.append((o_s, ops.chain_tracks(o_s, l2s[i:i + 8], dsts[i:i + 8])))
-            prm_op = ops.chain_params(SW, SH, SW * 4, DW, DH, DW * 4, DW * 4, swap_rb=1, interp=3 | 0x100 | 0x200, do_blur=1, bf=128, lut=lut, param_block=pblock)
-            prm_op.param_block_d = prm.param_block_d
-            for i in range(6):
-                ops.chain(prm_op, opq[i % len(opq)][1])
+            ms = e0.elapsed_time(e1)
+        launch_s = ms * 1e-3 / reps
+        algo = ALGO_BYTES_PER_FRAME * T
+        achieved = algo / launch_s / 1e9
+        traffic, traffic_source = None, None
+        try:   # HBM bytes per launch from the PMC passes of this round's build on this exact workload (tools/pmc.sh + tools/pmc_traffic.py -> profiles/pmc_traffic*.json, which names the commit)
+            tf = "pmc_traffic_pixbuf.json" if args.resize_backend == "pixbuf" else "pmc_traffic.json"
+            with open(os.path.join(ROOT, "profiles", tf)) as f:
+                pj = json.load(f)
+            if pj.get("tracks") == T and pj.get("blur") == args.blur:
+                traffic = pj.get("hbm_bytes_per_launch")
+                traffic_source = "profiles/%s@%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of that commit's build; not measured in this run)" % (tf, pj.get("commit"))
+        except (OSError, ValueError):
+            pass
+
+        # the denominator of "aggregate at 8 GPUs on an 8-track batch": the same 8 tracks as ONE launch on ONE GPU (every rank measures its own; rank 0's is printed)
+        if T >= 8:
+            prm.param_block_d = sched_base if world == 1 else pblock.data_ptr()
+            t8 = groups_of(8)                     # 16 tracks x 2 sets = four 8-track groups, 1.6 GB: with two groups the 256 MiB memory-side cache still holds part of a group when its turn
+            for i in range(10):                   # comes again (tools/sets_ab.sh, profiles/r04/sets_ab.txt: 8 tracks 69 us over two groups, 82 us over four or more; 16 tracks 156 us either way)
+                ops.chain(prm, t8[i % len(t8)])
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            n8 = 20          # few launches: they carry the same kernel name as the 16-track launch in a rocprofv3 --stats run (30 of ~1,600: the average moves by < 1 %)
             e0.record()
             for i in range(n8):
-                ops.chain(prm_op, opq[i % len(opq)][1])
+                ops.chain(prm, t8[i % len(t8)])
             e1.record()
             torch.cuda.synchronize()
-            batch8["batch8_blur_opaque_sources_1gpu_us_per_step"] = round(e0.elapsed_time(e1) * 1e3 / n8, 2)
-            del opq
+            us8 = e0.elapsed_time(e1) * 1e3 / n8
+            batch8 = {"batch8_1gpu_fps": round(8e6 / us8, 1), "batch8_1gpu_us_per_step": round(us8, 2), "batch8_groups_rotated": len(t8)}
+            if args.resize_backend == "pixbuf" and not args.blur:      # the same with config 5's gaussian in the chain
+                prm_blur.param_block_d = prm.param_block_d
+                for i in range(6):
+                    ops.chain(prm_blur, t8[i % len(t8)])
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for i in range(n8):
+                    ops.chain(prm_blur, t8[i % len(t8)])
+                e1.record()
+                torch.cuda.synchronize()
+                batch8["batch8_blur_1gpu_us_per_step"] = round(e0.elapsed_time(e1) * 1e3 / n8, 2)
+                # ... and on frames whose alpha is 255 everywhere (decoded video), with the caller's word for it (LGPU_INTERP_OPAQUE): the lighter instantiation, same bytes
+                opq = []
+                for srcs, l2s, dsts in keep:
+                    for i in range(0, T - 7, 8):
+                        o_s = [t.clone() for t in srcs[i:i + 8]]
+                        for t in o_s:
+                            t[:, 3::4] = 255
+                        opq.append((o_s, ops.chain_tracks(o_s, l2s[i:i + 8], dsts[i:i + 8])))
+                prm_op = ops.chain_params(SW, SH, SW * 4, DW, DH, DW * 4, DW * 4, swap_rb=1, interp=3 | 0x100 | 0x200, do_blur=1, bf=128, lut=lut, param_block=pblock)
+                prm_op.param_block_d = prm.param_block_d
+                for i in range(6):
+                    ops.chain(prm_op, opq[i % len(opq)][1])
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for i in range(n8):
+                    ops.chain(prm_op, opq[i % len(opq)][1])
+                e1.record()
+                torch.cuda.synchronize()
+                batch8["batch8_blur_opaque_sources_1gpu_us_per_step"] = round(e0.elapsed_time(e1) * 1e3 / n8, 2)
+                del opq
 
-    # ---- the same chain through the REFERENCE's API (N = 1, outside the timed region of `value`): the tracks as pinned weed_layer_t's, one host thread per track,
-    # convert_layer_palette -> resize_layer -> "chroma blend" process_func -> gamma_convert_layer by the reference names (liblivesgpu_dropin.so + livesgpu_fx.so),
-    # lives_gpu_layers_flush once per tick: the calls are recorded on the planes and become ONE lgpu_chain launch (tools/seam_host.c; include/lives_gpu_layer.h)
-    seam = None
-    if world == 1 and not args.blur and args.resize_backend == "pixbuf" and not args.dry_run and not args.no_seam:
-        try:
-            seam = seam_chain_leg(keep[0][0], keep[0][1], ops, fps, T)
-        except Exception as e:      # noqa: BLE001 -- a second measurement, never fatal for the line
-            seam = {"error": str(e)}
+        # ---- the same chain through the REFERENCE's API (N = 1, outside the timed region of `value`): the tracks as pinned weed_layer_t's, one host thread per track,
+        # convert_layer_palette -> resize_layer -> "chroma blend" process_func -> gamma_convert_layer by the reference names (liblivesgpu_dropin.so + livesgpu_fx.so),
+        # lives_gpu_layers_flush once per tick: the calls are recorded on the planes and become ONE lgpu_chain launch (tools/seam_host.c; include/lives_gpu_layer.h)
+        if world == 1 and not args.blur and args.resize_backend == "pixbuf" and not args.dry_run and not args.no_seam:
+            try:
+                seam = seam_chain_leg(keep[0][0], keep[0][1], ops, fps, T)
+            except Exception as e:      # noqa: BLE001 -- a second measurement, never fatal for the line
+                seam = {"error": str(e)}
 
-    # what this box's memory system gives the launch's own algorithmic bytes as a bare stream (no arithmetic, no re-reads): tells a slow box from a regression
-    box = None
-    if True:
+        # what this box's memory system gives the launch's own algorithmic bytes as a bare stream (no arithmetic, no re-reads): tells a slow box from a regression
+        box = None
         try:
             ops.stream_probe(prm, trks[0], 3)
             sp = sum(ops.stream_probe(prm, trks[i % nsets], 5) for i in range(2)) / 10.0 * 1e3      # 10 launches over both buffer sets, us per launch
@@ -373,12 +394,12 @@ def main():
                    "what": "lgpu_debug_stream_probe: the launch's algorithmic bytes (every source / layer-2 byte read once, every result byte written once, 16-byte non-temporal accesses, no arithmetic)"}
         except Exception as e:      # noqa: BLE001 -- a measurement aid, never fatal
             box = {"error": str(e)}
-    roof = {"bound": "hbm", "kernel": pixbuf_kernel_name(args) if args.resize_backend == "pixbuf" else "lgpu::k_half8s<0,0>", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
-            "algorithmic_bytes_per_launch": algo, "launch_us": round(launch_s * 1e6, 2),
-            "timed_as": "HIP events around %d back-to-back launches on ONE stream: the kernel's own duration, what rocprofv3 --kernel-trace --stats reports for it%s" % (
-                reps, "; the steps behind `value` alternate between two launch streams, so ms_per_step is below it" if two_streams else ""),
-            "box_class": box}
+        roof = {"bound": "hbm", "kernel": pixbuf_kernel_name(args) if args.resize_backend == "pixbuf" else "lgpu::k_half8s<0,0>", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
+                "algorithmic_bytes_per_launch": algo, "launch_us": round(launch_s * 1e6, 2),
+                "timed_as": "HIP events around %d back-to-back launches on ONE stream: the kernel's own duration, what rocprofv3 --kernel-trace --stats reports for it%s" % (
+                    reps, "; the steps behind `value` alternate between two launch streams, so ms_per_step is below it" if two_streams else ""),
+                "box_class": box}
 
     out = None
     if rank == 0:
@@ -395,8 +416,9 @@ def main():
                                           "torch.distributed broadcast (fallback)"),
                        "launch_streams": 2 if two_streams else 1,
                        "launches_per_step": 2 if (args.blur and args.resize_backend != "pixbuf") else 1, "layer2_translucent_fraction": args.l2_translucent, "buffer_sets_rotated": nsets},
-            "roofline": roof,
         }
+        if roof:
+            out["roofline"] = roof
         if seam:
             out["seam_chain"] = seam
         if batch8:
@@ -420,7 +442,7 @@ def main():
             out["config"]["rccl_ranks"] = nr
             if world > 1:
                 out["config"]["rccl_preflight"] = rccl_preflight if rccl_preflight is not None else "not run (librccl could not be bound on every rank)"
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(args.blur, args.resize_backend == "pixbuf")
     ctypes.CDLL(None).fflush(None)          # every rank: whatever librccl left in C stdio's buffer goes out now, not at exit behind rank 0's line
     if comm is not None:
@@ -433,6 +455,38 @@ def main():
         ctypes.CDLL(None).fflush(None)      # librccl prints its version banner through C stdio, which a pipe buffers until exit: out with it BEFORE the one JSON line
         sys.stdout.flush()
         print(json.dumps(out), flush=True)
+
+
+DUMP_BYTES = 64_000_000       # --dump-outputs: at most 64 MB of .npy in all
+DUMP_SAMPLE = 1 << 18         # byte positions per track in dst_sample.npy (fewer when many tracks would pass DUMP_BYTES)
+DUMP_SEED = 0x11FE5
+
+
+def dump_outputs(dirname, dsts):
+    """the destinations the last timed step wrote (uint8 [DH, DW * 4] each) as float32 .npy under dirname: dst_track0 (the first frame whole, [DH, DW, 4]),
+    dst_sample ([T, K] at the seeded positions dst_sample_index holds, the same for every track and every run), dst_row_sums ([T, DH, 4] per row and channel)"""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    T, n = len(dsts), DH * DW * 4
+    frames = torch.stack(dsts).view(T, n)
+    whole = DH * DW * 4 * 4
+    sums_bytes = T * DH * 4 * 4
+    k = min(DUMP_SAMPLE, (DUMP_BYTES - whole - sums_bytes - 4096) // (T * 4 + 8))
+    assert k > 0, "--dump-outputs: %d tracks do not fit %d bytes" % (T, DUMP_BYTES)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+    arrays = {
+        "dst_track0": frames[0].view(DH, DW, 4).float(),
+        "dst_sample": frames.index_select(1, torch.from_numpy(idx).to(frames.device)).float(),
+        "dst_sample_index": idx.astype(np.float64),
+        "dst_row_sums": frames.view(T, DH, DW, 4).sum(dim=2, dtype=torch.int64).float(),     # at most 1920 * 255: exact in float32
+    }
+    total = 0
+    for name, a in arrays.items():
+        a = a.cpu().numpy() if torch.is_tensor(a) else a
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= DUMP_BYTES, total
 
 
 def seam_chain_leg(srcs, l2s, ops, value_fps, T, ticks=600, warm=150):

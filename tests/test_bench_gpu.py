@@ -1,5 +1,6 @@
-"""bench.py itself on the GPU, short: the line's contract (one JSON object with roofline and the 8-GPU denominators), the two-stream option, and the N > 1 host path
-forced onto one GPU (library RCCL communicator of one rank, C stepper, config-5 legs with and without the gaussian)."""
+"""bench.py itself on the GPU, short: the plain line (headline only) and its --dump-outputs, the --full line's contract (one JSON object with roofline and the
+8-GPU denominators), the two-stream option, and the N > 1 host path forced onto one GPU (library RCCL communicator of one rank, C stepper, config-5 legs with and
+without the gaussian)."""
 import json
 import os
 import subprocess
@@ -10,10 +11,11 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_bench(extra, env=None):
+def run_bench(extra, env=None, full=True):
     e = dict(os.environ)
     e.update(env or {})
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "2", "--no-cpu"] + extra, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=e, timeout=900)
+    base = ["--steps", "8", "--warmup", "2"] + (["--full", "--no-cpu"] if full else [])
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + base + extra, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=e, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     lines = [ln for ln in out.stdout.decode().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout.decode()[-2000:]
@@ -32,6 +34,36 @@ def test_bench_line(streams):
     assert r["bound"] == "hbm" and r["peak"] == 8000.0 and 0.2 < r["frac"] < 1.0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3
     assert r["algorithmic_bytes_per_launch"] == 16 * (3840 * 2160 * 4 + 2 * 1920 * 1080 * 4) and "ONE stream" in r["timed_as"]
     assert r["box_class"]["stream_probe_us"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_its_outputs(tmp_path):
+    """A plain run times the steps and prints the headline alone; --dump-outputs writes what the last timed step computed, float32, within 64 MB, the same
+    bytes in every run with the same arguments -- and the same under --full, whose legs all run after the dump"""
+    import numpy as np
+    j = run_bench(["--dump-outputs", str(tmp_path / "a")], full=False)
+    assert j["metric"] == "effect-chain frames/sec at 3840x2160 RGBA32" and j["unit"] == "frames/s" and j["higher_is_better"] is True and j["dtype"] == "u8"
+    assert j["steps"] == 8 and j["warmup"] == 2 and j["value"] > 2000 and j["ms_per_step"] > 0
+    assert abs(j["value"] - 16 * 1e3 / j["ms_per_step"]) <= 1e-3 * j["value"] + 0.1
+    for k in ("roofline", "seam_chain", "cpu_baseline"):
+        assert k not in j, k
+    assert "batch8_1gpu_us_per_step" not in j["config"] and "config5_ms_per_step" not in j["config"]
+    names = ("dst_track0", "dst_sample", "dst_sample_index", "dst_row_sums")
+    a = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in names}
+    assert sum(v.nbytes for v in a.values()) <= 64_000_000
+    assert a["dst_track0"].shape == (1080, 1920, 4) and a["dst_row_sums"].shape == (16, 1080, 4) and a["dst_sample"].shape[0] == 16
+    for n in names:
+        assert a[n].dtype in (np.float32, np.float64), n
+    frame0 = a["dst_track0"]
+    assert (frame0 == np.round(frame0)).all() and frame0.min() >= 0 and frame0.max() <= 255 and frame0.std() > 10
+    idx = a["dst_sample_index"].astype(np.int64)
+    assert (a["dst_sample"][0] == frame0.reshape(-1)[idx]).all()
+    assert (a["dst_row_sums"][0] == frame0.sum(axis=1, dtype=np.float64)).all()
+    assert not (a["dst_sample"][0] == a["dst_sample"][1]).all()             # every track its own frame
+    f = run_bench(["--dump-outputs", str(tmp_path / "b")])
+    assert "roofline" in f and f["steps"] == 8
+    for n in names:
+        assert np.array_equal(a[n], np.load(str(tmp_path / "b" / (n + ".npy")))), n
 
 
 @pytest.mark.gpu
@@ -58,7 +90,7 @@ def test_bench_under_the_drivers_launcher_agrees_with_the_plain_run():
     e = dict(os.environ)
     e.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(port),
-                          os.path.join(ROOT, "bench.py"), "--gpus", "1", "--no-cpu", "--steps", "200", "--warmup", "50"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=e, timeout=900)
+                          os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--no-cpu", "--steps", "200", "--warmup", "50"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=e, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     lines = [ln for ln in out.stdout.decode().splitlines() if ln.startswith("{")]
     assert len(lines) == 1

@@ -3,7 +3,8 @@
 cd $GRAFT_REPO_ROOT
 rocm-smi --showclocks --showpower --showtemp 2>&1 | grep -v "^=\|^$" | head -20
 echo "---- under load"
-python bench.py --no-cpu --steps 150000 --warmup 100 > gpurun_out/clock_probe_bench.json 2>/dev/null &
+J=$(mktemp)
+python bench.py --full --no-cpu --steps 150000 --warmup 100 > "$J" 2>/dev/null &
 BP=$!
 sleep 6
 for i in 1 2 3 4 5 6; do
@@ -11,4 +12,4 @@ for i in 1 2 3 4 5 6; do
   sleep 3
 done
 wait $BP
-python -c "import json; j=json.loads(open('gpurun_out/clock_probe_bench.json').readlines()[-1]); print('launch_us', j['roofline']['launch_us'])"
+python -c "import json, sys; j=json.loads(open(sys.argv[1]).readlines()[-1]); print('launch_us', j['roofline']['launch_us'])" "$J"; rm -f "$J"

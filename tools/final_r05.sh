@@ -5,16 +5,16 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/final_r05; mkdir -p $O
 C=$(cat tools/_commit 2>/dev/null || echo unknown)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_first -o t -- python bench.py --no-cpu > $O/bench_line_inside_the_rocprofv3_run.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_first -o t -- python bench.py --full --no-cpu > $O/bench_line_inside_the_rocprofv3_run.log 2>&1
 cp $O/trace_first/t_kernel_stats.csv $O/final_kernel_stats.csv
-python bench.py > $O/bench_default.json 2>$O/bench_default.err
-python bench.py --steps 20 --warmup 5 --no-cpu 2>/dev/null | grep "^{" > $O/bench_driver_shape.json
+python bench.py --full > $O/bench_default.json 2>$O/bench_default.err
+python bench.py --full --steps 20 --warmup 5 --no-cpu 2>/dev/null | grep "^{" > $O/bench_driver_shape.json
 for a in "--tracks 1" "--tracks 8" "--blur 1" "--blur 1 --tracks 8" "--blur 1 --tracks 1" "--resize-backend polyphase" "--launch-streams 2"; do
-  timeout 300 python bench.py --no-cpu $a 2>/dev/null | grep "^{" >> $O/final_bench.jsonl
+  timeout 300 python bench.py --full --no-cpu $a 2>/dev/null | grep "^{" >> $O/final_bench.jsonl
 done
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_blur -o t -- python bench.py --no-cpu --blur 1 > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_blur -o t -- python bench.py --full --no-cpu --blur 1 > /dev/null 2>&1
 cp $O/trace_blur/t_kernel_stats.csv $O/blur_kernel_stats.csv
-LGPU_BENCH_FORCE_EXCHANGE=1 python bench.py --no-cpu 2>/dev/null | grep "^{" > $O/bench_forced_exchange.json
+LGPU_BENCH_FORCE_EXCHANGE=1 python bench.py --full --no-cpu 2>/dev/null | grep "^{" > $O/bench_forced_exchange.json
 gcc -O2 -o tools/_worker tools/worker.c -Iinclude -Llives_amd -llivesgpu -Wl,-rpath,$PWD/lives_amd
 for a in "--tracks 1 --exchange 1 --ahead 16" "--tracks 1 --exchange 0 --ahead 16" "--tracks 8 --exchange 1 --steps 600" "--tracks 16 --exchange 1 --ahead 16 --steps 500"; do LD_LIBRARY_PATH=/usr/local/lib/python3.10/dist-packages/torch/lib:$LD_LIBRARY_PATH timeout 300 tools/_worker $a 2>&1 | grep tool >> $O/worker.jsonl; done
 timeout 900 tools/pmc.sh gpurun_out/pmc_final_r05 > /dev/null 2>&1

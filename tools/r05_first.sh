@@ -3,9 +3,9 @@
 # (not on record until now), the counters of config 4 in one launch, and the single-frame op timings the review lists
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r05/first; mkdir -p $O
-python bench.py > $O/bench_default.json 2>$O/bench_default.err
+python bench.py --full > $O/bench_default.json 2>$O/bench_default.err
 for a in "--blur 1" "--blur 1 --tracks 8" "--blur 1 --tracks 1" "--tracks 8" "--tracks 1"; do
-  timeout 300 python bench.py --no-cpu $a 2>/dev/null | grep "^{" >> $O/bench_shapes.jsonl
+  timeout 300 python bench.py --full --no-cpu $a 2>/dev/null | grep "^{" >> $O/bench_shapes.jsonl
 done
 tools/pmc.sh gpurun_out/r05/pmc_blur16 --blur 1 > /dev/null 2>&1
 python tools/pmc_summary.py gpurun_out/r05/pmc_blur16 k_pb_half > $O/pmc_pb_half_blur.md
