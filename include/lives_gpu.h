@@ -149,9 +149,9 @@ int lgpu_yuv420p_to_rgb_batch(int nframes, const lgpu_yuv_frame *frames, const i
    through the one-column kernel), threads per workgroup (256 / 512 / 1024), resident groups of 256 threads per CU; -1 keeps a value.  Results do not
    depend on it (tests walk every setting); process-wide, not meant to change while conversions are in flight. */
 int lgpu_yuv420_tuning(int cell_columns, int block, int groups_per_cu);
-/* Launch-shape / ablation switches by name ("PBH_TH", "PBH_ALIGNED", "PB_NO_PAIRS", "GCK_TH", "CHAIN_SPARE_WGS", ...: the LGPU_<NAME> environment variables
+/* Launch-shape switches by name ("PBH_TH", "PBH_ALIGNED", "PB_NO_PAIRS", "EDGE_TH", "CHAIN_SPARE_WGS", ...: the LGPU_<NAME> environment variables
    without the prefix).  The environment is read ONCE, at the library's first launch; afterwards only this call changes a switch (value < 0 clears it), so no
-   launch path ever calls getenv() beside a host that calls setenv().  Results do not depend on any of them (the tests walk them).  lgpu_tuning_get: the
+   launch path ever calls getenv() beside a host that calls setenv().  Results do not depend on any of them (the tests walk them).  An unknown name: LGPU_E_BADARG.  lgpu_tuning_get: the
    current value, -1 when unset or unknown. */
 int lgpu_tuning_set(const char *name, int value);
 int lgpu_tuning_get(const char *name);

@@ -215,7 +215,6 @@ int gauss5_rows(const uint8_t *src_d, int irow, uint8_t *dst_d, int orow, int wi
   a.src0 = src_d; a.src1 = nullptr; a.dst = dst_d; a.irow0 = irow; a.irow1 = 0; a.orow = orow; a.width = width; a.height = height;
   a.strips = (int)cdiv((unsigned)width, 248); a.cgroups = (a.strips + 3) / 4;
   a.th = 8;
-  { const int v = tune(TUNE_GCK_TH); if (v >= 1 && v <= 1024) a.th = v; }
   a.bands = (int)cdiv((unsigned)height, (unsigned)a.th);
   a.key = 0;
   const dim3 grid(8u * cdiv((unsigned)(a.cgroups * a.bands), 8u));
@@ -267,7 +266,6 @@ int lgpu::gauss5_colorkey_n(const FxFrames &F, int nframes, int irow0, int irow1
       }
     }
   }
-  { const int v = tune(TUNE_GCK_TH); if (v >= 1 && v <= 1024) a.th = v; }      // tuning probe
   a.bands = (int)cdiv((unsigned)height, (unsigned)a.th);
   // parameter preparation exactly as the script does it (host side, double)
   double xdelta = delta * 2.;

@@ -76,14 +76,17 @@ constexpr int kBlock = 256;   // 4 wavefronts of 64
 // frames of one geometry for the batch forms of the single-plane kernels (lgpu_*_batch): the frame is the grid's z index; travels in the kernarg segment
 struct FrameTab { const uint8_t *src[16]; uint8_t *dst[16]; };        // 16 = LGPU_FX_MAX_FRAMES
 
-// ---- launch-shape / ablation switches ------------------------------------------------------------------
+// ---- launch-shape switches ------------------------------------------------------------------
 // Every switch the launch paths consult lives in ONE process-wide table of atomics: filled once from the environment (LGPU_<NAME>) at first use, changed
 // afterwards only through lgpu_tuning_set() (tests, sweeps).  No launch path calls getenv(): the host (LiVES) calls setenv() at run time from other threads.
+#define LGPU_TUNE_SWITCHES(X)                                                                                     \
+  X(PBH_ALIGNED) X(PBH_TH) X(PBH_ORDER) X(PBH_GROUP) X(PBH_OCC) X(PB_NO_PAIRS) X(PB_UP_RB) X(PB_CACHE_MAX) X(PB_CHAIN_GROUP) \
+  X(CHAIN_SPARE_WGS) X(SEP2P_FORCE) X(SOFT_NO_S) X(SOFT_RB) X(EDGE_NO_S) X(EDGE_TH) X(SEAM_STAGED)
 enum Tune {
-  TUNE_PBH_ALIGNED, TUNE_PBH_TH, TUNE_PB_NO_DOUBLE, TUNE_PB_NO_HALF3, TUNE_PB_NO_PAIRS, TUNE_PB_NO_GATHER, TUNE_PB_NO_UP, TUNE_PB_UP_RB,
-  TUNE_GCK_TH, TUNE_CHAIN_SPARE_WGS, TUNE_SEP2_LDS_KB, TUNE_NO_SEP2P, TUNE_NO_SEP2P_MFMA, TUNE_PLAN_DEBUG,
-  TUNE_SEP2P_FORCE, TUNE_PB_CACHE_MAX, TUNE_K2_WGS, TUNE_SOFT_NO_S, TUNE_SOFT_RB, TUNE_EDGE_NO_S, TUNE_EDGE_TH, TUNE_PBH_ORDER, TUNE_PBH_OCC, TUNE_PBH_GROUP, TUNE_G5_MFMA, TUNE_RGB2YUV_NO_S, TUNE_UYVY_NO_S, TUNE_REPACK_NO_S, TUNE_DISABLE_HALF8, TUNE_NO_SEP2, TUNE_SEP2P_TH, TUNE_G5_CLASSIC,
-  TUNE_GAUSS5_NO_ROWS, TUNE_PB_NO_PRE, TUNE_PB_LDS_KB, TUNE_PHASE_PROFILE, TUNE_PB_TILE_ORDER, TUNE_PB_CHAIN_GROUP, TUNE_SEAM_STAGED, TUNE_COUNT
+#define LGPU_TUNE_ENUM(n) TUNE_##n,
+  LGPU_TUNE_SWITCHES(LGPU_TUNE_ENUM)
+#undef LGPU_TUNE_ENUM
+  TUNE_COUNT
 };
 int tune(Tune t);                                  // the value, or -1 when the switch is unset
 static inline bool tune_on(Tune t) { return tune(t) > 0; }

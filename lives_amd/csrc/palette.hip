@@ -1482,8 +1482,7 @@ static int rgb_to_yuv_impl_n(const uint8_t *const *srcs, int irow, int width, in
   const int npairs = width >> 1;
   if (npairs == 0) return LGPU_OK;
   // aligned 4-byte pixels -> 4:2:0: the cell form
-  const bool no_s420 = tune_on(TUNE_RGB2YUV_NO_S);
-  if (out_fmt == 4 && ips == 4 && in_order <= 1 && !no_s420 && (width & 3) == 0 && height >= 2 &&
+  if (out_fmt == 4 && ips == 4 && in_order <= 1 && (width & 3) == 0 && height >= 2 &&
       (sbits & 15) == 0 && (d0bits & 3) == 0 && (d12bits & 1) == 0) {
     const int ngr = width >> 2, nunits = (height >> 1) + 1;
     const unsigned long long cells = (unsigned long long)ngr * nunits;
@@ -1497,7 +1496,7 @@ static int rgb_to_yuv_impl_n(const uint8_t *const *srcs, int irow, int width, in
     }
   }
   // aligned 4-byte pixels -> packed / planar 4:2:2 without a gamma LUT: the cell form
-  if ((out_fmt == 2 || out_fmt == 3 || out_fmt == 5) && ips == 4 && in_order <= 1 && !lut16_d && !no_s420 && (width & 3) == 0 &&
+  if ((out_fmt == 2 || out_fmt == 3 || out_fmt == 5) && ips == 4 && in_order <= 1 && !lut16_d && (width & 3) == 0 &&
       (sbits & 15) == 0 &&
       (out_fmt == 5 ? ((d0bits & 3) == 0 && (d12bits & 1) == 0) : ((d0bits & 7) == 0))) {
     const int ngr = width >> 2;
@@ -1516,7 +1515,7 @@ static int rgb_to_yuv_impl_n(const uint8_t *const *srcs, int irow, int width, in
   uintptr_t pbits = d0bits | d12bits;
   if (out_fmt == 1 && out_alpha) { pbits |= (uintptr_t)orow[3]; for (int f = 0; f < nfr; f++) pbits |= (uintptr_t)dsts[f][3]; }
   if (((out_fmt == 0 && (d0bits & (out_alpha ? 15 : 3)) == 0) || (out_fmt == 1 && (pbits & 3) == 0)) &&
-      in_order <= 1 && !no_s420 && (width & 3) == 0 && (sbits & (ips == 4 ? 15 : 3)) == 0) {
+      in_order <= 1 && (width & 3) == 0 && (sbits & (ips == 4 ? 15 : 3)) == 0) {
     const int ngr = width >> 2;
     const unsigned long long cells = (unsigned long long)ngr * height;
     if (cells < (1ull << 31)) {
@@ -1607,8 +1606,7 @@ static int yuv_to_rgb_n(const uint8_t *const (*srcs)[4], const int irow[4], int 
     if (in_fmt >= 2) LGPU_REQUIRE(!((uintptr_t)srcs[f][0] & 3), "UYVY / YUYV rows must be 4-byte aligned");
   }
   // UYVY / YUYV -> 4-byte pixels on aligned frames: the cell form
-  const bool no_s = tune_on(TUNE_UYVY_NO_S);
-  if (in_fmt >= 2 && ops == 4 && !no_s && (width & 3) == 0 && (sbits & 7) == 0 && (dbits & 15) == 0) {
+  if (in_fmt >= 2 && ops == 4 && (width & 3) == 0 && (sbits & 7) == 0 && (dbits & 15) == 0) {
     const int ngr = width >> 2;
     const unsigned long long cells = (unsigned long long)ngr * height;
     if (cells < (1ull << 31)) {
@@ -1626,7 +1624,7 @@ static int yuv_to_rgb_n(const uint8_t *const (*srcs)[4], const int irow[4], int 
     const int ips = in_alpha ? 4 : 3;
     uintptr_t pb = 0;
     if (in_fmt == 1) for (int f = 0; f < nfr; f++) for (int i = 0; i < nplanes; i++) pb |= (uintptr_t)srcs[f][i] | (uintptr_t)irow[i];
-    if (((in_fmt == 0 && (sbits & (ips == 4 ? 15 : 3)) == 0) || (in_fmt == 1 && (pb & 3) == 0)) && !no_s && (width & 3) == 0 && (dbits & (ops == 4 ? 15 : 3)) == 0) {
+    if (((in_fmt == 0 && (sbits & (ips == 4 ? 15 : 3)) == 0) || (in_fmt == 1 && (pb & 3) == 0)) && (width & 3) == 0 && (dbits & (ops == 4 ? 15 : 3)) == 0) {
       const int ngr = width >> 2;
       const unsigned long long cells = (unsigned long long)ngr * height;
       if (cells < (1ull << 31)) {
@@ -1703,7 +1701,7 @@ int lgpu::yuv411_to_rgb_n(const FxFrames &F, int nframes, int width_mp, int heig
   LGPU_REQUIRE((unsigned long long)width_mp * height < (1ull << 31), "frame too large");
   const uint32_t ncells = (uint32_t)width_mp * (uint32_t)height;
   const uint32_t magic = (uint32_t)((1ull << 32) / (unsigned)width_mp - (width_mp == 1 ? 1 : 0));
-  unsigned wgs = cdiv(ncells, kBlock), cap = cdiv((unsigned)device_cus() * (unsigned)(tune(TUNE_K2_WGS) > 0 ? tune(TUNE_K2_WGS) : 8), (unsigned)nframes);
+  unsigned wgs = cdiv(ncells, kBlock), cap = cdiv((unsigned)device_cus() * 8u, (unsigned)nframes);
   hipLaunchKernelGGL(k_yuv411_to_rgb, dim3(wgs < cap ? wgs : cap, (unsigned)nframes), dim3(kBlock), 0, st, a, magic, ncells, F);
   LGPU_CHECK_LAUNCH();
   return LGPU_OK;
@@ -1930,8 +1928,7 @@ extern "C" int lgpu_yuv_repack(int in_pal, int out_pal, const uint8_t *const src
     LGPU_REQUIRE(dst_d[3], "null alpha plane");
     if ((rc = lgpu_fill(dst_d[3], 255, (size_t)orow[3] * height, stream))) return rc;                 // :7819
   }
-  const bool no_s = tune_on(TUNE_REPACK_NO_S);
-  if (a.kind == lgpu::RK_420_TO_PK && !no_s && (width & 7) == 0 && (((uintptr_t)src_d[0] | (uintptr_t)irow[0]) & 7) == 0 &&
+  if (a.kind == lgpu::RK_420_TO_PK && (width & 7) == 0 && (((uintptr_t)src_d[0] | (uintptr_t)irow[0]) & 7) == 0 &&
       (((uintptr_t)src_d[1] | (uintptr_t)src_d[2] | (uintptr_t)irow[1] | (uintptr_t)irow[2]) & 3) == 0 &&        // dword loads on EVERY chroma row
       (((uintptr_t)dst_d[0] | (uintptr_t)((orow[0] / 4) * 4)) & 15) == 0 && (unsigned long long)(width >> 3) * height < (1ull << 31)) {
     const int ngr = width >> 3;
@@ -1941,7 +1938,7 @@ extern "C" int lgpu_yuv_repack(int in_pal, int out_pal, const uint8_t *const src
     LGPU_CHECK_LAUNCH();
     return LGPU_OK;
   }
-  if (a.kind == lgpu::RK_COMBINE && !no_s && (width & 3) == 0 && ((irow[0] | irow[1] | irow[2]) & 3) == 0 && irow[0] == irow[1] && irow[0] == irow[2] &&
+  if (a.kind == lgpu::RK_COMBINE && (width & 3) == 0 && ((irow[0] | irow[1] | irow[2]) & 3) == 0 && irow[0] == irow[1] && irow[0] == irow[2] &&
       (((uintptr_t)src_d[0] | (uintptr_t)src_d[1] | (uintptr_t)src_d[2]) & 3) == 0 && (!a.in_alpha || !a.out_alpha || (((uintptr_t)src_d[3]) & 3) == 0) &&
       (((uintptr_t)dst_d[0] | (uintptr_t)orow[0]) & (a.out_alpha ? 15 : 3)) == 0 && (unsigned long long)(width >> 2) * height < (1ull << 31)) {
     const int ngr = width >> 2;
@@ -1950,7 +1947,7 @@ extern "C" int lgpu_yuv_repack(int in_pal, int out_pal, const uint8_t *const src
     LGPU_CHECK_LAUNCH();
     return LGPU_OK;
   }
-  if (a.kind == lgpu::RK_SPLIT && !no_s && (width & 3) == 0 && (((uintptr_t)src_d[0] | (uintptr_t)irow[0]) & 3) == 0 &&
+  if (a.kind == lgpu::RK_SPLIT && (width & 3) == 0 && (((uintptr_t)src_d[0] | (uintptr_t)irow[0]) & 3) == 0 &&
       (((uintptr_t)dst_d[0] | (uintptr_t)dst_d[1] | (uintptr_t)dst_d[2] | (uintptr_t)orow[0] | (uintptr_t)orow[1] | (uintptr_t)orow[2]) & 3) == 0 &&
       (unsigned long long)(width >> 2) * height < (1ull << 31)) {
     const int ngr = width >> 2;
@@ -1959,7 +1956,7 @@ extern "C" int lgpu_yuv_repack(int in_pal, int out_pal, const uint8_t *const src
     LGPU_CHECK_LAUNCH();
     return LGPU_OK;
   }
-  if (a.kind == lgpu::RK_SWAB && !no_s && (width & 7) == 0 && (((uintptr_t)src_d[0] | (uintptr_t)irow[0] | (uintptr_t)dst_d[0] | (uintptr_t)orow[0]) & 15) == 0 &&
+  if (a.kind == lgpu::RK_SWAB && (width & 7) == 0 && (((uintptr_t)src_d[0] | (uintptr_t)irow[0] | (uintptr_t)dst_d[0] | (uintptr_t)orow[0]) & 15) == 0 &&
       (unsigned long long)(width >> 3) * height < (1ull << 31)) {
     const int ngr = width >> 3;
     const uint32_t magic = (uint32_t)((1ull << 32) / (unsigned)ngr - (ngr == 1 ? 1 : 0));
@@ -1967,7 +1964,7 @@ extern "C" int lgpu_yuv_repack(int in_pal, int out_pal, const uint8_t *const src
     LGPU_CHECK_LAUNCH();
     return LGPU_OK;
   }
-  if ((a.kind == lgpu::RK_PK_TO_420 || a.kind == lgpu::RK_PK_TO_444 || a.kind == lgpu::RK_PK_TO_888) && !no_s && (width & 7) == 0 &&
+  if ((a.kind == lgpu::RK_PK_TO_420 || a.kind == lgpu::RK_PK_TO_444 || a.kind == lgpu::RK_PK_TO_888) && (width & 7) == 0 &&
       (((uintptr_t)src_d[0] | (uintptr_t)((irow[0] / 4) * 4)) & 15) == 0 && (unsigned long long)(width >> 3) * height < (1ull << 31)) {
     bool ok;
     if (a.kind == lgpu::RK_PK_TO_420) ok = (((uintptr_t)dst_d[0]) & 7) == 0 && (((uintptr_t)dst_d[1] | (uintptr_t)dst_d[2]) & 3) == 0;      // (compact destination: width a multiple of 8)
@@ -1984,7 +1981,7 @@ extern "C" int lgpu_yuv_repack(int in_pal, int out_pal, const uint8_t *const src
       return LGPU_OK;
     }
   }
-  if ((a.kind == lgpu::RK_888_TO_420 || a.kind == lgpu::RK_888_TO_422) && !no_s && (width & 3) == 0 && (((uintptr_t)src_d[0] | (uintptr_t)irow[0]) & (a.in_alpha ? 15 : 3)) == 0 &&
+  if ((a.kind == lgpu::RK_888_TO_420 || a.kind == lgpu::RK_888_TO_422) && (width & 3) == 0 && (((uintptr_t)src_d[0] | (uintptr_t)irow[0]) & (a.in_alpha ? 15 : 3)) == 0 &&
       (unsigned long long)(width >> 2) * height < (1ull << 31)) {
     // (the destinations of these kinds are compact: checked above)
     const bool planar = a.kind == lgpu::RK_888_TO_420 || a.out_alpha;
@@ -1999,7 +1996,7 @@ extern "C" int lgpu_yuv_repack(int in_pal, int out_pal, const uint8_t *const src
       return LGPU_OK;
     }
   }
-  if (a.kind == lgpu::RK_420_TO_422P && !no_s && (width & 7) == 0 && (unsigned long long)(width >> 3) * height < (1ull << 31) &&
+  if (a.kind == lgpu::RK_420_TO_422P && (width & 7) == 0 && (unsigned long long)(width >> 3) * height < (1ull << 31) &&
       (((uintptr_t)src_d[0] | (uintptr_t)irow[0] | (uintptr_t)dst_d[0] | (uintptr_t)orow[0]) & 7) == 0 &&
       (((uintptr_t)src_d[1] | (uintptr_t)src_d[2] | (uintptr_t)irow[1] | (uintptr_t)irow[2] | (uintptr_t)dst_d[1] | (uintptr_t)dst_d[2] | (uintptr_t)orow[1] | (uintptr_t)orow[2]) & 3) == 0) {
     const int ngr = width >> 3;

@@ -1863,7 +1863,6 @@ int pb_chain(const lgpu_chain_params *pr, const lgpu_canvas *cv, const lgpu_chai
   }
   if (pixbuf && !(cv && pr->do_blur) && !(noblend && pr->do_blur)) {
     rc = pb_chain_half(pr, cv, tracks, ntracks, st, amounts);         // one launch
-    if (tune_on(TUNE_PLAN_DEBUG)) fprintf(stderr, "pb_chain: one-launch form rc %d (%s)\n", rc, rc ? lgpu_last_error() : "ok");
     if (rc != LGPU_E_UNSUPPORTED) return rc;
   }
   // any other ratio, no gaussian, no canvas: the scaler of that ratio with the chain's last stages in its store -- one launch as well
@@ -1881,7 +1880,6 @@ int pb_chain(const lgpu_chain_params *pr, const lgpu_canvas *cv, const lgpu_chai
     e.bf_d = amounts ? nullptr : pr->param_block_d; e.bf0 = (uint32_t)pr->bf & 0xFF; e.irow2 = pr->irow2; e.swap_rb = pr->swap_rb ? 1 : 0; e.use_lut = pr->use_lut ? 1 : 0;
     e.bf_tracks = amounts ? 1 : 0; e.blend = noblend ? 0 : 1; e.lut = pack_lut(pr->use_lut ? pr->lut8 : nullptr);
     rc = pb_scale_fused(srcs, dsts, ntracks, pr->irow, pr->sw, pr->sh, pr->orow, pr->dw, pr->dh, (pr->interp & 0xFF) | (pr->interp & LGPU_INTERP_OPAQUE), st, &e);
-    if (tune_on(TUNE_PLAN_DEBUG)) fprintf(stderr, "pb_chain: scaler with the chain's last stages rc %d\n", rc);
     if (rc == LGPU_OK && cv && (cv->nwidth != pr->dw || cv->nheight != pr->dh)) {
       for (int i = 0; i < ntracks; i++) e.l2[i] = tracks[i].layer2_d;      // the bars read layer 2 at canvas coordinates
       hipLaunchKernelGGL(k_pb_bars_epi, dim3(cdiv((unsigned)cv->nwidth, 64), cdiv((unsigned)cv->nheight, 4), (unsigned)ntracks), dim3(256), 0, st, T, e, pr->orow,
@@ -2052,7 +2050,7 @@ static int pb_scale_n(const uint8_t *const *srcs, uint8_t *const *dsts, int n, i
     return rc;
   }
   if (!epi && channels == 4 && dw == 2 * sw && dh == 2 * sh && (sw & 1) == 0 && ((sbits | (unsigned)irow) & 7) == 0 && ((dbits | (unsigned)orow) & 15) == 0 &&
-      pb_double_ok(t, x_step, y_step) && !tune_on(TUNE_PB_NO_DOUBLE)) {
+      pb_double_ok(t, x_step, y_step)) {
     PbHalfArgs h;
     h.sw = sw; h.sh = sh; h.irow = irow; h.dw = dw; h.dh = dh; h.orow = orow;
     h.strips = (int)cdiv((unsigned)sw, 124); h.cgroups = (h.strips + 3) / 4;
@@ -2062,7 +2060,7 @@ static int pb_scale_n(const uint8_t *const *srcs, uint8_t *const *dsts, int n, i
     LGPU_CHECK_LAUNCH();
     return LGPU_OK;
   }
-  if (channels == 3 && sw == 2 * dw && sh == 2 * dh && (sw & 7) == 0 && ((sbits | dbits | (unsigned)irow | (unsigned)orow) & 3) == 0 && !tune_on(TUNE_PB_NO_HALF3)) {
+  if (channels == 3 && sw == 2 * dw && sh == 2 * dh && (sw & 7) == 0 && ((sbits | dbits | (unsigned)irow | (unsigned)orow) & 3) == 0) {
     PbHalfArgs h;
     // the same table check as the 4-byte kernel (alignment arguments that always pass: this kernel's own are checked above)
     if (pb_half_ok(t, interp, sw, sh, dw, dh, 0, 0, &h.hyper, &h.ashift)) {
@@ -2097,10 +2095,8 @@ static int pb_scale_n(const uint8_t *const *srcs, uint8_t *const *dsts, int n, i
     }
   }
   const bool no_pairs = tune_on(TUNE_PB_NO_PAIRS);        // tests: the one-tap-per-operation kernels at any ratio
-  const bool no_gather = tune_on(TUNE_PB_NO_GATHER);
   // both sides enlarged: the register-window walk
-  const bool no_up = tune_on(TUNE_PB_NO_UP);
-  if (channels == 4 && t->gpairs_d && !no_pairs && !no_up && x_step <= 65536 && y_step <= 65536) {
+  if (channels == 4 && t->gpairs_d && !no_pairs && x_step <= 65536 && y_step <= 65536) {
     const int unp = (t->tx1 - t->tx0 + 1) / 2, uny = t->ty1 - t->ty0;
     if (unp >= 1 && unp <= 2 && uny >= 1 && uny <= 4) {
       PbUpArgs ua;
@@ -2121,7 +2117,7 @@ static int pb_scale_n(const uint8_t *const *srcs, uint8_t *const *dsts, int n, i
     }
   }
   // integer reductions (one phase for the whole frame): the barrier-free kernel with scalar weights; every other ratio keeps the LDS window
-  if (channels == 4 && t->gpairs_d && !no_pairs && !no_gather && (x_step & 0xFFFF) == 0 && (y_step & 0xFFFF) == 0) {
+  if (channels == 4 && t->gpairs_d && !no_pairs && (x_step & 0xFFFF) == 0 && (y_step & 0xFFFF) == 0) {
     PbGatherArgs ga;
     ga.src = src_d; ga.dst = dst_d; ga.irow = irow; ga.orow = orow; ga.sw = sw; ga.sh = sh; ga.dw = dw; ga.dh = dh;
     ga.x_step = x_step; ga.y_step = y_step; ga.xoff = t->xoff; ga.yoff = t->yoff; ga.tx0 = t->tx0; ga.ty0 = t->ty0; ga.ny_eff = t->ty1 - t->ty0;
@@ -2145,7 +2141,7 @@ static int pb_scale_n(const uint8_t *const *srcs, uint8_t *const *dsts, int n, i
     pa.wpairs = ((int)((((63LL * x_step + 65535) >> 16) + 1) / 2) + 4 * t->nq + 3 + 3) & ~3;       // whole quads of pairs, and wx0 is rounded down to a multiple of 4 below
 
     pa.tile_h = 0;
-    size_t lds_cap = (tune(TUNE_PB_LDS_KB) > 0 ? (size_t)tune(TUNE_PB_LDS_KB) : 24) * 1024;     // 6 workgroups per CU: the per-lane weight loads want occupancy more than the window wants rows (profiles/r03/pb_pairs_lds_sweep.txt)
+    const size_t lds_cap = 24 * 1024;     // 6 workgroups per CU: the per-lane weight loads want occupancy more than the window wants rows (profiles/r03/pb_pairs_lds_sweep.txt)
     for (int th = 16; th >= 1; th >>= 1) {
       const int wh = (int)(((long long)(th - 1) * y_step + 65535) >> 16) + pa.ny_eff + 1;
       if ((size_t)pa.wpairs * wh * 16 <= lds_cap) { pa.tile_h = th; pa.win_h = wh; break; }
@@ -2155,21 +2151,20 @@ static int pb_scale_n(const uint8_t *const *srcs, uint8_t *const *dsts, int n, i
       pa.gx = (int)g.x; pa.gy = (int)g.y; pa.per_xcd = 0;
       // Tile order.  Counters on 4K -> 1706x960 (profiles/r06/fetch_size_calibration.md: FETCH_SIZE reports HALF of what is read for this kernel's 640-byte window
       // segments exactly as for a full-wave stream -- 128-byte requests) put its L2 -> fabric reads at 2.0 x the source: with the tiles of a row dealt round robin to
-      // the XCDs, the window rows that vertically neighbouring tiles share (5 of 14) are fetched by another XCD's L2 again.  LGPU_PB_TILE_ORDER=1: every XCD a
+      // the XCDs, the window rows that vertically neighbouring tiles share (5 of 14) are fetched by another XCD's L2 again.  So every XCD takes a
       // contiguous run of the row-major tile sequence.
-      if (tune(TUNE_PB_TILE_ORDER) != 0 && g.x * g.y >= 64) { pa.per_xcd = (int)cdiv(g.x * g.y, 8u); g = dim3(8u * (unsigned)pa.per_xcd, 1, (unsigned)n); }
+      if (g.x * g.y >= 64) { pa.per_xcd = (int)cdiv(g.x * g.y, 8u); g = dim3(8u * (unsigned)pa.per_xcd, 1, (unsigned)n); }
       const size_t lds = (size_t)pa.wpairs * pa.win_h * 16;
       const int np = (t->tx1 - t->tx0 + 2) / 2;
 #define PB_PRE(CHN, NP_, NY_, OQ, EAT, EAV) { if (pa.tile_h <= 4) hipLaunchKernelGGL((k_pb_pairs<CHN, NP_, NY_, 1, OQ, EAT>), g, block, lds, st, pa, F, EAV); else hipLaunchKernelGGL((k_pb_pairs<CHN, NP_, NY_, 0, OQ, EAT>), g, block, lds, st, pa, F, EAV); }
 #define PB_PAIRS(CHN, OQ, EAT, EAV)                                                                                       \
       { const int ny = t->ty1 - t->ty0;                                                                                   \
-        const bool pre = !tune_on(TUNE_PB_NO_PRE);                                                                          \
         if (np == 2 && ny == 2) PB_PRE(CHN, 2, 2, OQ, EAT, EAV)                                                              \
         else if (np == 2 && ny == 3) PB_PRE(CHN, 2, 3, OQ, EAT, EAV)                                                         \
         else if (np == 3 && ny == 3) PB_PRE(CHN, 3, 3, OQ, EAT, EAV)                                                         \
-        else if (pre && np == 3 && ny == 4) PB_PRE(CHN, 3, 4, OQ, EAT, EAV)                                                  \
-        else if (pre && np == 3 && ny == 5) PB_PRE(CHN, 3, 5, OQ, EAT, EAV)                                                  \
-        else if (pre && np == 4 && ny == 6) PB_PRE(CHN, 4, 6, OQ, EAT, EAV)                                                  \
+        else if (np == 3 && ny == 4) PB_PRE(CHN, 3, 4, OQ, EAT, EAV)                                                         \
+        else if (np == 3 && ny == 5) PB_PRE(CHN, 3, 5, OQ, EAT, EAV)                                                         \
+        else if (np == 4 && ny == 6) PB_PRE(CHN, 4, 6, OQ, EAT, EAV)                                                         \
         else if (np == 1) hipLaunchKernelGGL((k_pb_pairs<CHN, 1, 0, 0, OQ, EAT>), g, block, lds, st, pa, F, EAV);            \
         else if (np == 2) hipLaunchKernelGGL((k_pb_pairs<CHN, 2, 0, 0, OQ, EAT>), g, block, lds, st, pa, F, EAV);            \
         else if (np == 3) hipLaunchKernelGGL((k_pb_pairs<CHN, 3, 0, 0, OQ, EAT>), g, block, lds, st, pa, F, EAV);            \

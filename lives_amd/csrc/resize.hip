@@ -48,7 +48,6 @@ struct SepArgs {
   const uint32_t *hco2, *vco2;
   int nph, npv;
   int ntracks;                      // k_sep2p: tracks of the launch (the tile list is tiles_x * tiles_y * ntracks long)
-  unsigned long long *dbg;          // k_sep2p, LGPU_S2P_DEBUG=1: per-wave phase cycle sums [grid][6][8] (nullptr otherwise)
   // k_sep2p with the horizontal pass on the matrix cores (uniform integer ratio r: every output column has the same taps and starts r pixels after
   // its neighbour): B fragments [KB][hi, lo][64 lanes] of v_mfma_i32_16x16x64_i8, see sep2p_bfrag()
   const void *bfrag;
@@ -436,16 +435,9 @@ __device__ __forceinline__ uint32_t g5_sum(uint32_t a, uint32_t b, uint32_t c, u
   return a + e + ((b + d) << 2) + (c << 2) + (c << 1);   // 32-bit SWAR operands: no 24-bit multiply
 }
 
-// MH (measurement variant, LGPU_G5_MFMA=1): the horizontal pass as a banded-Toeplitz product on the matrix cores, the form BASELINE config 4
-// names ("MFMA row/col").  The window is kept as packed pixels biased to int8; A = 16 window rows x 16 pixels (one ds_read_b128 per lane),
-// B[k = (pixel, byte)][n = (column, channel)] = {1 4 6 4 1}[pixel - column] on matching channels; 16 source pixels give 12 output columns
-// = three v_mfma_i32_16x16x64_i8 per A fragment, six fragments per 64 columns, two row blocks (rows 0..15 and 4..19) per 20-row window:
-// 36 MFMAs per tile.  Every D register is one channel of one column: it is un-biased (+ 16 * 128) and written as a 16-bit lane of the
-// SWAR layout the vertical pass reads.  Same bytes as the SWAR pass; the timing is in profiles/r02/gauss5_mfma.md.
-constexpr int kG5MPitch = 76 * 4;        // bytes per window row of the MFMA variant: 6 fragments x 12 pixels + 4
-template <bool EPI, bool MH = false>   // EPI: chroma blend with layer 2 and / or the gamma LUT after the blur (the chain); false = plain blur
+template <bool EPI>   // EPI: chroma blend with layer 2 and / or the gamma LUT after the blur (the chain); false = plain blur
 __global__ __launch_bounds__(256) void k_gauss5x(G5Args a, SepTracks t, Lut8 l) {
-  __shared__ uint4 s_win4[MH ? (kG5WH * kG5MPitch + 64) / 16 : kG5WH * kG5WW / 2];
+  __shared__ uint4 s_win4[kG5WH * kG5WW / 2];
   __shared__ uint2 s_h[kG5WH * kG5W];
   __shared__ uint8_t s_lut[256];
   __shared__ uint2 s_k[EPI ? 256 : 1];
@@ -491,70 +483,16 @@ __global__ __launch_bounds__(256) void k_gauss5x(G5Args a, SepTracks t, Lut8 l) 
   const int ox = tx0 + col;
   for (int sub = 0; sub < nsub; sub++) {
     const int ty0 = ty00 + sub * kG5H;
-    if (!MH) {
 #pragma unroll
-      for (int k = 0; k < kIter; k++)
-        if (tid + k * 256 < kPairs) s_win4[tid + k * 256] = make_uint4(cur[k].x & M, (cur[k].x >> 8) & M, cur[k].y & M, (cur[k].y >> 8) & M);
-    } else {
-      uint8_t *s_raw = reinterpret_cast<uint8_t *>(s_win4);
-#pragma unroll
-      for (int k = 0; k < kIter; k++) {
-        const int i = tid + k * 256;
-        if (i < kPairs) {
-          const int row = i / (kG5WW / 2), pr = i - row * (kG5WW / 2);
-          *reinterpret_cast<uint2 *>(s_raw + row * kG5MPitch + pr * 8) = make_uint2(cur[k].x ^ 0x80808080u, cur[k].y ^ 0x80808080u);
-        }
-      }
-    }
+    for (int k = 0; k < kIter; k++)
+      if (tid + k * 256 < kPairs) s_win4[tid + k * 256] = make_uint4(cur[k].x & M, (cur[k].x >> 8) & M, cur[k].y & M, (cur[k].y >> 8) & M);
     __syncthreads();
     if (sub + 1 < nsub) fetch(ty0 + kG5H);       // next window's loads fly under this sub-tile's two passes
-    if (!MH) {
-      for (int i = tid; i < kG5WH * kG5W; i += 256) {
-        const int row = i >> 6, c = i & 63;
-        const uint2 *p = s_win + row * kG5WW + c;
-        const uint2 A = p[0], B = p[1], C = p[2], D = p[3], E = p[4];
-        s_h[i] = make_uint2(g5_sum(A.x, B.x, C.x, D.x, E.x), g5_sum(A.y, B.y, C.y, D.y, E.y));
-      }
-    } else {
-      const uint8_t *s_raw = reinterpret_cast<const uint8_t *>(s_win4);
-      const int lane = tid & 63, wave = tid >> 6, m = lane & 15, g = lane >> 4;
-      // B fragments of the three 4-column groups of a 16-pixel span: lane (g, n) supplies k = 16 g + e, e = 0..15
-      int4v bfr[3];
-#pragma unroll
-      for (int nb = 0; nb < 3; nb++) {
-        uint32_t w4[4];
-#pragma unroll
-        for (int d = 0; d < 4; d++) {
-          uint32_t v = 0;
-#pragma unroll
-          for (int e4 = 0; e4 < 4; e4++) {
-            const int k = 16 * g + 4 * d + e4, px = k >> 2, ch = k & 3, col = 4 * nb + (m >> 2), och = m & 3, j = px - col;
-            const int tap = (ch == och && j >= 0 && j <= 4) ? (j == 0 || j == 4 ? 1 : j == 2 ? 6 : 4) : 0;
-            v |= (uint32_t)tap << (8 * e4);
-          }
-          w4[d] = v;
-        }
-        bfr[nb] = int4v{(int)w4[0], (int)w4[1], (int)w4[2], (int)w4[3]};
-      }
-      uint16_t *s_h16 = reinterpret_cast<uint16_t *>(s_h);
-      const int slot = (m & 1) * 2 + ((m >> 1) & 1);                 // 16-bit lane of channel m & 3 in the uint2 {ch0 | ch2 << 16, ch1 | ch3 << 16}
-      // 12 (row block, fragment) jobs over the four waves
-      for (int job = wave; job < 12; job += 4) {
-        const int blk = job / 6, fj = job - blk * 6;
-        const int row0 = blk * 4;                                      // block 1 covers rows 4..19 and delivers rows 16..19
-        const int4v afr = *reinterpret_cast<const int4v *>(s_raw + (row0 + m) * kG5MPitch + fj * 48 + g * 16);
-        const int4v zero = {0, 0, 0, 0};
-#pragma unroll
-        for (int nb = 0; nb < 3; nb++) {
-          const int4v d = __builtin_amdgcn_mfma_i32_16x16x64_i8(afr, bfr[nb], zero, 0, 0, 0);
-          const int col = fj * 12 + nb * 4 + (m >> 2);
-#pragma unroll
-          for (int r = 0; r < 4; r++) {
-            const int row = row0 + 4 * g + r;
-            if (col < kG5W && (blk == 0 || row >= 16)) s_h16[(row * kG5W + col) * 4 + slot] = (uint16_t)(d[r] + 2048);
-          }
-        }
-      }
+    for (int i = tid; i < kG5WH * kG5W; i += 256) {
+      const int row = i >> 6, c = i & 63;
+      const uint2 *p = s_win + row * kG5WW + c;
+      const uint2 A = p[0], B = p[1], C = p[2], D = p[3], E = p[4];
+      s_h[i] = make_uint2(g5_sum(A.x, B.x, C.x, D.x, E.x), g5_sum(A.y, B.y, C.y, D.y, E.y));
     }
     __syncthreads();
     if (ox < a.w) {
@@ -668,7 +606,6 @@ struct Half8Args {
   const int32_t *bf_d;
   int use_lut;
   int tiles_x, tiles_y, ntracks;
-  unsigned long long *dbg;          // profiling build (LGPU_PROFILING): per-wave phase cycle sums [grid][6][8]
   int nt_out;                       // result stores non-temporal (the result is not read back by the next launch)
 };
 
@@ -861,19 +798,9 @@ struct H8sTile {
 };
 
 // ---- compute waves (shared by both loader designs below) -------------------------------------------------------------
-// ABL (A / B builds only): 16 = barriers only (no compute), 32 = no source window loads
-template <int DBG, int ABL, int NWAVES>
 __device__ __forceinline__ void h8s_compute(const Half8Args &a, uint8_t *smem, int wave, int lane, int work, int wend, int wstride) {
   using C = H8S;
   using L = H8SL;
-  unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = 0;
-#define H8S_T(i)                                                                                     \
-  if (DBG) {                                                                                          \
-    __builtin_amdgcn_sched_barrier(0);                                                                \
-    const unsigned long long now_ = __builtin_amdgcn_s_memtime();                                     \
-    tacc[i] += now_ - tprev; tprev = now_;                                                            \
-    __builtin_amdgcn_sched_barrier(0);                                                                \
-  }
   uint8_t *s_win = smem + C::kOffWin;
   uint8_t *s_h = smem + L::kOffH;
   uint8_t *s_q = smem + L::kOffQ;
@@ -902,12 +829,8 @@ __device__ __forceinline__ void h8s_compute(const Half8Args &a, uint8_t *smem, i
   const uint32_t aoff = (uint32_t)(m * kH8Pitch + wave * (NQ * 32) + g * 16);
   const uint32_t aoff2 = (uint32_t)((32 + 2 * (m >> 2) + (m & 1)) * kH8Pitch + wave * (NQ * 32) + g * 16);
   int par = 0;
-  if (DBG) tprev = __builtin_amdgcn_s_memtime();
   for (; work < wend; work += wstride) {
-    H8S_T(0)
     H8S_BARRIER();                                                                     // A(n)
-    H8S_T(1)
-    if (ABL & 16) { H8S_BARRIER(); par ^= 1; continue; }
     // ---- horizontal pass on the matrix cores ----
     // Software pipelined over the three 16-row blocks: the four A fragments of block mb + 1 are read while block mb is
     // on the matrix pipe, and a block's eight MFMAs are issued back to back before any result is consumed.
@@ -958,9 +881,7 @@ __device__ __forceinline__ void h8s_compute(const Half8Args &a, uint8_t *smem, i
         }
       }
     }
-    H8S_T(2)
     H8S_BARRIER();                                                                     // B(n)
-    H8S_T(3)
     // ---- vertical pass + epilogue; layer 2 comes from / the result goes to the ring slot ----
     {
       uint32_t *qs = reinterpret_cast<uint32_t *>(s_q + par * 4096) + ly0 * kTileW + lane;
@@ -1048,9 +969,6 @@ __device__ __forceinline__ void h8s_compute(const Half8Args &a, uint8_t *smem, i
     par ^= 1;
   }
   H8S_BARRIER();                                                                       // A(last + 1)
-  if (DBG && lane == 0)
-    for (int i = 0; i < 8; i++) a.dbg[((size_t)blockIdx.x * NWAVES + wave) * 8 + i] = tacc[i];
-#undef H8S_T
 }
 
 // shared prologue: tables into LDS, this workgroup's share of the XCD-aware persistent work list (each XCD owns a contiguous
@@ -1074,7 +992,6 @@ __device__ __forceinline__ bool h8s_prologue(const Half8Args &a, const Lut8 &lut
 // a mover wave (two more windows in flight per workgroup, hand-counted vmcnt) 173.3 against 173.3, memory side alone 163 against
 // 161: the bytes in flight are not the limit -- with the compute waves ablated the launch moves its 818 MB at 5.0 TB/s, the
 // rate a device-to-device hipMemcpy of the same size reaches on the same box (5.17 TB/s).
-template <int DBG, int ABL>
 __global__ __launch_bounds__(kH8sThreads, 3) void k_half8s(Half8Args a, SepTracks trk, Lut8 lut) {
   using C = H8S;
   using L = H8SL;
@@ -1084,15 +1001,7 @@ __global__ __launch_bounds__(kH8sThreads, 3) void k_half8s(Half8Args a, SepTrack
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int work, wend, wstride;
   if (!h8s_prologue(a, lut, smem, work, wend, wstride)) return;
-  if (wave < kH8sCW) { h8s_compute<DBG, ABL, kH8sCW + 2>(a, smem, wave, lane, work, wend, wstride); return; }
-  unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = 0;
-#define H8S_T(i)                                                                                     \
-  if (DBG) {                                                                                          \
-    __builtin_amdgcn_sched_barrier(0);                                                                \
-    const unsigned long long now_ = __builtin_amdgcn_s_memtime();                                     \
-    tacc[i] += now_ - tprev; tprev = now_;                                                            \
-    __builtin_amdgcn_sched_barrier(0);                                                                \
-  }
+  if (wave < kH8sCW) { h8s_compute(a, smem, wave, lane, work, wend, wstride); return; }
   {
 
     // ------------------------------------------------ memory waves ------------------------------------------------
@@ -1104,8 +1013,7 @@ __global__ __launch_bounds__(kH8sThreads, 3) void k_half8s(Half8Args a, SepTrack
     //   B(n)   | first part of window n+2 | wait for all but that part: window n+1 (and layer-2 n+1) have landed |
     //          | edge fix-up and int8 bias of window n+1 (own chunks)
     constexpr int WAUX = 0;                                      // cache policy of the source stream (non-temporal measured 196 us against 176: the halos live in L2)
-    constexpr int K2 = (ABL & 64) ? 11 : 16;                     // A / B: balanced split of a window between the two waves
-    constexpr int K0 = 0, K1 = (ABL & 128) ? K2 : 6, K3 = 21, K4 = 21;     // wave 4: [K0,K1) after B + [K1,K2) after A; wave 5: [K2,K3) after B (+ [K3,K4) after A)
+    constexpr int K0 = 0, K1 = 6, K2 = 16, K3 = 21, K4 = 21;     // wave 4: [K0,K1) after B + [K1,K2) after A; wave 5: [K2,K3) after B (+ [K3,K4) after A)
     const bool w5 = wave == kH8sCW + 1;
     H8sLaneOff lo;
     h8s_lane_offsets(a, lane, lo);
@@ -1114,14 +1022,14 @@ __global__ __launch_bounds__(kH8sThreads, 3) void k_half8s(Half8Args a, SepTrack
     const bool has1 = work + wstride < wend;
     if (w5) {
       if (a.blend) h8s_issue_q2(a, trk.l2[t0.track], t0.tx0(), t0.ty0(), lane, s_q);
-      if (!(ABL & 32)) h8s_issue_window<K2, K4, WAUX>(a, trk.src[t0.track], t0.tx0(), t0.ty0(), lane, s_win, lo);
-      if (has1) { if (!(ABL & 32)) h8s_issue_window<K2, K3, WAUX>(a, trk.src[t1.track], t1.tx0(), t1.ty0(), lane, s_win + C::kWinBytes, lo); asm volatile("s_waitcnt vmcnt(%0)" :: "n"(K3 - K2) : "memory"); }
+      h8s_issue_window<K2, K4, WAUX>(a, trk.src[t0.track], t0.tx0(), t0.ty0(), lane, s_win, lo);
+      if (has1) { h8s_issue_window<K2, K3, WAUX>(a, trk.src[t1.track], t1.tx0(), t1.ty0(), lane, s_win + C::kWinBytes, lo); asm volatile("s_waitcnt vmcnt(%0)" :: "n"(K3 - K2) : "memory"); }
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       if (h8s_border(2 * t0.tx0() - 3 - a.xoff, a.sw)) h8s_fix_edges(s_win, 2 * t0.tx0() - 3 - a.xoff, a.sw, lane, K2 * 64, K4 * 64);
       h8s_bias_window<K2 * 1024, C::kWinBytes>(s_win, lane);
     } else {
-      if (!(ABL & 32)) h8s_issue_window<K0, K2, WAUX>(a, trk.src[t0.track], t0.tx0(), t0.ty0(), lane, s_win, lo);
-      if (has1) { if (!(ABL & 32)) h8s_issue_window<K0, K1, WAUX>(a, trk.src[t1.track], t1.tx0(), t1.ty0(), lane, s_win + C::kWinBytes, lo); asm volatile("s_waitcnt vmcnt(%0)" :: "n"(K1 - K0) : "memory"); }
+      h8s_issue_window<K0, K2, WAUX>(a, trk.src[t0.track], t0.tx0(), t0.ty0(), lane, s_win, lo);
+      if (has1) { h8s_issue_window<K0, K1, WAUX>(a, trk.src[t1.track], t1.tx0(), t1.ty0(), lane, s_win + C::kWinBytes, lo); asm volatile("s_waitcnt vmcnt(%0)" :: "n"(K1 - K0) : "memory"); }
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       if (h8s_border(2 * t0.tx0() - 3 - a.xoff, a.sw)) h8s_fix_edges(s_win, 2 * t0.tx0() - 3 - a.xoff, a.sw, lane, K0 * 64, K2 * 64);
       h8s_bias_window<K0 * 1024, K2 * 1024>(s_win, lane);
@@ -1129,33 +1037,25 @@ __global__ __launch_bounds__(kH8sThreads, 3) void k_half8s(Half8Args a, SepTrack
     H8sTile tp = t0;                  // tile n-1
     bool has_prev = false;
     int par = 0;
-    if (DBG) tprev = __builtin_amdgcn_s_memtime();
     for (; work < wend; work += wstride) {
-      H8S_T(0)
       H8S_BARRIER();                                                                   // A(n)
-      H8S_T(1)
       const bool has_next = work + wstride < wend, has_nn = work + 2 * wstride < wend;
       uint8_t *w1 = s_win + (par ^ 1) * C::kWinBytes;
       if (w5) {
-        if (has_next) if (!(ABL & 32)) h8s_issue_window<K3, K4, WAUX>(a, trk.src[t1.track], t1.tx0(), t1.ty0(), lane, w1, lo);
-        H8S_T(2)
+        if (has_next) h8s_issue_window<K3, K4, WAUX>(a, trk.src[t1.track], t1.tx0(), t1.ty0(), lane, w1, lo);
         uint4 ov[4];
         if (has_prev) h8s_read_tile(lane, s_q + (par ^ 1) * 4096, ov);
         if (has_next && a.blend) h8s_issue_q2(a, trk.l2[t1.track], t1.tx0(), t1.ty0(), lane, s_q + (par ^ 1) * 4096);
         if (has_prev) h8s_store_tile(a, trk.dst[tp.track], tp.tx0(), tp.ty0(), lane, ov);
       } else {
-        if (has_next) if (!(ABL & 32)) h8s_issue_window<K1, K2, WAUX>(a, trk.src[t1.track], t1.tx0(), t1.ty0(), lane, w1, lo);
-        H8S_T(2)
+        if (has_next) h8s_issue_window<K1, K2, WAUX>(a, trk.src[t1.track], t1.tx0(), t1.ty0(), lane, w1, lo);
       }
-      H8S_T(3)
       H8S_BARRIER();                                                                   // B(n): window slot n & 1 is free
-      H8S_T(4)
       if (has_nn) {
         uint8_t *w2 = s_win + par * C::kWinBytes;
-        if (w5) { if (!(ABL & 32)) h8s_issue_window<K2, K3, WAUX>(a, trk.src[t2.track], t2.tx0(), t2.ty0(), lane, w2, lo); H8S_T(5) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(K3 - K2) : "memory"); }
-        else { if (!(ABL & 32)) h8s_issue_window<K0, K1, WAUX>(a, trk.src[t2.track], t2.tx0(), t2.ty0(), lane, w2, lo); H8S_T(5) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(K1 - K0) : "memory"); }
+        if (w5) { h8s_issue_window<K2, K3, WAUX>(a, trk.src[t2.track], t2.tx0(), t2.ty0(), lane, w2, lo); asm volatile("s_waitcnt vmcnt(%0)" :: "n"(K3 - K2) : "memory"); }
+        else { h8s_issue_window<K0, K1, WAUX>(a, trk.src[t2.track], t2.tx0(), t2.ty0(), lane, w2, lo); asm volatile("s_waitcnt vmcnt(%0)" :: "n"(K1 - K0) : "memory"); }
       } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      H8S_T(6)
       if (has_next) {
         const int sx1 = 2 * t1.tx0() - 3 - a.xoff;
         if (h8s_border(sx1, a.sw)) {
@@ -1174,12 +1074,9 @@ __global__ __launch_bounds__(kH8sThreads, 3) void k_half8s(Half8Args a, SepTrack
       h8s_read_tile(lane, s_q + (par ^ 1) * 4096, ov);
       h8s_store_tile(a, trk.dst[tp.track], tp.tx0(), tp.ty0(), lane, ov);
     }
-    if (DBG && lane == 0)
-      for (int i = 0; i < 8; i++) a.dbg[((size_t)blockIdx.x * (kH8sCW + 2) + wave) * 8 + i] = tacc[i];
     return;
   
   }
-#undef H8S_T
 }
 
 // =====================================================================================================================
@@ -1316,8 +1213,6 @@ __device__ __forceinline__ void s2p_compute(const SepArgs &a, const SepTracks &t
       bl[kb] = reinterpret_cast<const int4v *>(a.bfrag)[(kb * 2 + 1) * 64 + lane];
     }
   }
-  unsigned long long tacc[4] = {0, 0, 0, 0}, tprev = a.dbg ? __builtin_amdgcn_s_memtime() : 0;
-#define S2P_T(i) if (a.dbg) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); tacc[i] += now_ - tprev; tprev = now_; }
   for (; work < wend; work += wstride, par ^= 1) {
     S2pTile t;
     t.set(a, work);
@@ -1334,9 +1229,7 @@ __device__ __forceinline__ void s2p_compute(const SepArgs &a, const SepTracks &t
         if (ly < thh && lane < tw) qpre[r] = reinterpret_cast<const uint32_t *>(l2 + (size_t)(t.ty0 + ly) * a.irow2)[t.tx0 + lane];
       }
     }
-    S2P_T(3)
     H8S_BARRIER();                                                                   // A(i): window i, tables i in place; row pairs free
-    S2P_T(0)
     const uint32_t *s_src = reinterpret_cast<const uint32_t *>(smem + par * L.win);
     const uint32_t *s_hc = reinterpret_cast<const uint32_t *>(smem + L.hc + par * L.hcslot);
     const uint32_t *s_vc = reinterpret_cast<const uint32_t *>(smem + L.vc + par * L.vcslot);
@@ -1374,9 +1267,7 @@ __device__ __forceinline__ void s2p_compute(const SepArgs &a, const SepTracks &t
       s_p[k * kS2pPitch + lane] = pk;
     }
     }
-    S2P_T(1)
     H8S_BARRIER();                                                                   // B(i): row pairs complete, window slot i & 1 free
-    S2P_T(2)
     // ---- vertical pass + epilogue: wave = output row, lane = output column ----
     // NB output rows of the wave at a time (4 when the tile gives a wave more than two rows, else 2): their row-pair / tap-pair reads are requested
     // together, so the LDS latency of the (run-time long) pair loop is paid once per batch (one row at a time measured 900 cycles per row, mostly waiting)
@@ -1431,10 +1322,6 @@ __device__ __forceinline__ void s2p_compute(const SepArgs &a, const SepTracks &t
     };
     if (a.th > 2 * CW) vrows(std::integral_constant<int, 4>()); else vrows(std::integral_constant<int, 2>());
   }
-  S2P_T(3)
-  if (a.dbg && lane == 0)          // [0] waiting at A, [1] horizontal pass, [2] waiting at B, [3] vertical pass + stores
-    for (int i = 0; i < 4; i++) a.dbg[((size_t)blockIdx.x * (CW + 2) + wave) * 8 + i] = tacc[i];
-#undef S2P_T
 }
 
 template <int NPH, int KB, int CW>
@@ -1526,27 +1413,17 @@ __global__ __launch_bounds__((CW + 2) * 64, (CW + 2) / 2) void k_sep2p(SepArgs a
     issue(first, m, gx, gy);
     if (first + 2 * wstride < wend) geom(first + 2 * wstride, gx, gy);
   }
-  unsigned long long tacc[4] = {0, 0, 0, 0}, tprev = a.dbg ? __builtin_amdgcn_s_memtime() : 0;
-#define S2P_T(i) if (a.dbg) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); tacc[i] += now_ - tprev; tprev = now_; }
   if (m == 0) land(0);
-  S2P_T(1)
   int i = 0;
   for (; work < wend; work += wstride, i++) {
     H8S_BARRIER();                                                                   // A(i)
-    S2P_T(0)
     if (((i + 1) & 1) == m && work + wstride < wend) land((i + 1) & 1);
-    S2P_T(1)
     H8S_BARRIER();                                                                   // B(i)
-    S2P_T(2)
     if ((i & 1) == m && work + 2 * wstride < wend) {
       issue(work + 2 * wstride, i & 1, gx, gy);
       if (work + 4 * wstride < wend) geom(work + 4 * wstride, gx, gy);
     }
-    S2P_T(3)
   }
-  if (a.dbg && lane == 0)          // [0] waiting at A, [1] waiting for the window + fix-up, [2] waiting at B, [3] issuing
-    for (int k = 0; k < 4; k++) a.dbg[((size_t)blockIdx.x * (CW + 2) + wave) * 8 + k] = tacc[k];
-#undef S2P_T
 }
 
 // ---- generic two-launch path: any pixel size (bytes are independent channels), global int16 scratch ----
@@ -1747,16 +1624,24 @@ static int get_half8_const(const int16_t taps[8], int swap_rb, int xoff, const H
   return LGPU_OK;
 }
 
-static int g_h8s_opt = 0;
-#ifdef LGPU_H8S_AB
-extern "C" int lgpu_h8s_set_opt(int opt) { g_h8s_opt = opt; return LGPU_OK; }   // A / B builds only (tools/ab_h8s.py), not part of the ABI
-#endif
+// An XCD's workgroups walk its share of a persistent kernel's tile list with a stride of grid / 8 tiles.  When that stride shares a large factor with
+// the number of tiles per row the workgroups march down fixed tile columns in lockstep and the launch takes up to 1.7x as long (measured: 4096 x 2160
+// sources, 32 tiles per row, stride 64: 283 us against 180 with stride 62; 24 tiles per row: 185 against 161; profiles/r02/chain_stride.md): take the
+// largest stride whose gcd with the row length is at most 2.  grid: whole workgroups per XCD (a multiple of 8).
+static int xcd_stride_grid(int grid, int tiles_x) {
+  if (grid < 64) return grid;
+  auto gcd = [](int x, int y) { while (y) { const int t_ = x % y; x = y; y = t_; } return x; };
+  int w = grid >> 3;
+  for (int k = 0; k < 6 && w - k >= 8; k++)
+    if (gcd(w - k, tiles_x) <= 2) { w -= k; break; }
+  return w << 3;
+}
+
 // returns LGPU_OK and launches when the fast path applies; LGPU_E_UNSUPPORTED when it does not
 static int try_half8(const Bank *hb, const Bank *vb, int sw, int sh, int irow, int dw, int dh, int orow, int swap_rb, int blend,
                      int irow2, uint32_t bf, const int32_t *bf_d, int use_lut, const SepTracks &t, int ntracks, const Lut8 &l,
                      hipStream_t st, int nt_out = 1) {
-  const bool disabled = tune_on(TUNE_DISABLE_HALF8);
-  if (disabled || !hb->uniform2 || !vb->uniform2) return LGPU_E_UNSUPPORTED;
+  if (!hb->uniform2 || !vb->uniform2) return LGPU_E_UNSUPPORTED;
   if ((irow & 3) || (orow & 3)) return LGPU_E_UNSUPPORTED;
   {   // operand ranges of the int8 / int16 forms used by the kernel
     int hsum = 0, vsum = 0, hneg = 0;
@@ -1771,7 +1656,6 @@ static int try_half8(const Bank *hb, const Bank *vb, int sw, int sh, int irow, i
   // (a multiple of four pixels) and the tap matrix is shifted by one pixel instead
   int xoff = ((irow & 15) == 0) ? 1 : 0;
   for (int i = 0; i < ntracks; i++) if ((uintptr_t)t.src[i] & 15) xoff = 0;
-  if (g_h8s_opt & 256) xoff = 0;                   // A / B builds
   const Half8Const *hc;
   int rc = get_half8_const(hb->taps8, swap_rb, xoff, &hc);
   if (rc) return rc;
@@ -1783,13 +1667,11 @@ static int try_half8(const Bank *hb, const Bank *vb, int sw, int sh, int irow, i
   for (int k = 0; k < 4; k++) a.vc[k] = (uint32_t)(uint16_t)vb->taps8[2 * k] | ((uint32_t)(uint16_t)vb->taps8[2 * k + 1] << 16);
   a.swap_rb = swap_rb; a.blend = blend; a.irow2 = irow2; a.bf = bf; a.nbf = 0xFF - bf; a.bf_d = bf_d; a.use_lut = use_lut;
   a.ntracks = ntracks;
-  a.dbg = nullptr;
   a.nt_out = nt_out;
   // persistent grid: as many workgroups as stay resident (two per CU by LDS), each walks its XCD's share of the work list
   const int g_cus = device_cus();
   a.tiles_x = (dw + kTileW - 1) / kTileW; a.tiles_y = (dh + H8S::kTileH - 1) / H8S::kTileH;
   const int nwork = a.tiles_x * a.tiles_y * ntracks;
-  const int mode = g_h8s_opt & 255;                // A / B builds (tools/ab_h8s.py): ablations of k_half8s
   const size_t lds = H8SL::kLds;
   int grid = g_cus * (int)(160 * 1024 / lds);
   // multi-GPU hosts: leave a few workgroup slots (one per XCD) free, so that a kernel with a large LDS footprint enqueued on another stream -- RCCL's
@@ -1797,62 +1679,9 @@ static int try_half8(const Bank *hb, const Bank *vb, int sw, int sh, int irow, i
   { const int n = tune(TUNE_CHAIN_SPARE_WGS); if (n > 0 && n < grid / 2) grid -= n; }
   if (grid > nwork) grid = nwork;
   grid = (grid + 7) & ~7;                      // whole workgroups per XCD
-  // An XCD's workgroups walk its share of the tile list with a stride of grid / 8 tiles.  When that stride shares a large factor with the number of tiles per
-  // row the workgroups march down fixed tile columns in lockstep and the launch takes up to 1.7x as long (measured: 4096 x 2160 sources, 32 tiles per row,
-  // stride 64: 283 us against 180 with stride 62; 24 tiles per row: 185 against 161; profiles/r02/chain_stride.md): take the largest stride whose gcd with
-  // the row length is at most 2.
-  if (grid >= 64) {
-    auto gcd = [](int x, int y) { while (y) { const int t_ = x % y; x = y; y = t_; } return x; };
-    int w = grid >> 3;
-    for (int k = 0; k < 6 && w - k >= 8; k++)
-      if (gcd(w - k, a.tiles_x) <= 2) { w -= k; break; }
-    grid = w << 3;
-  }
-#define H8S_LAUNCH(DBG_, ABL_)                                                                                          \
-  do {                                                                                                                  \
-    LGPU_HIP(hipFuncSetAttribute((const void *)k_half8s<DBG_, ABL_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    hipLaunchKernelGGL((k_half8s<DBG_, ABL_>), dim3((unsigned)grid), dim3(kH8sThreads), lds, st, a, t, l);              \
-  } while (0)
-#ifdef LGPU_PROFILING
-  const bool dbg_s = tune_on(TUNE_PHASE_PROFILE);      // LGPU_PLAN_DEBUG only prints: the run being diagnosed keeps its timing and captures into graphs
-  if (dbg_s) {     // in-kernel phase profile: s_memtime ticks between fixed points of the tile loop, per wave
-    static unsigned long long *g_dbg_s = nullptr;
-    constexpr int nw = kH8sCW + 2;
-    if (!g_dbg_s) LGPU_HIP(hipMalloc((void **)&g_dbg_s, sizeof(unsigned long long) * 8 * nw * 4096));
-    a.dbg = g_dbg_s;
-    H8S_LAUNCH(1, 0);
-    static int dumps = 0;
-    if (dumps++ < 3) {
-      LGPU_HIP(hipStreamSynchronize(st));
-      std::vector<unsigned long long> h((size_t)grid * 8 * nw);
-      LGPU_HIP(hipMemcpy(h.data(), g_dbg_s, h.size() * 8, hipMemcpyDeviceToHost));
-      double c[8] = {0}, m[8] = {0}, m5[8] = {0};
-      for (int b = 0; b < grid; b++)
-        for (int i = 0; i < 8; i++) {
-          for (int w = 0; w < kH8sCW; w++) c[i] += (double)h[((size_t)b * nw + w) * 8 + i] / kH8sCW;
-          m[i] += (double)h[((size_t)b * nw + kH8sCW) * 8 + i]; m5[i] += (double)h[((size_t)b * nw + kH8sCW + 1) * 8 + i];
-        }
-      const double it = (double)nwork;
-      fprintf(stderr, "[h8s compute wave, ticks/tile] V+epilogue %.0f | wait A %.0f | H %.0f | wait B %.0f\n", c[0] / it, c[1] / it, c[2] / it, c[3] / it);
-      fprintf(stderr, "[h8s memory wave 4, ticks/tile] fix+bias %.0f | wait A %.0f | dma window b %.0f | - %.0f | wait B %.0f | dma window a %.0f | land %.0f\n",
-              m[0] / it, m[1] / it, m[2] / it, m[3] / it, m[4] / it, m[5] / it, m[6] / it);
-      fprintf(stderr, "[h8s memory wave 5, ticks/tile] fix+bias %.0f | wait A %.0f | dma window b %.0f | read + dma l2 + store %.0f | wait B %.0f | dma window a %.0f | land %.0f\n",
-              m5[0] / it, m5[1] / it, m5[2] / it, m5[3] / it, m5[4] / it, m5[5] / it, m5[6] / it);
-    }
-    LGPU_CHECK_LAUNCH();
-    return LGPU_OK;
-  }
-#endif
-  switch (mode) {
-#ifdef LGPU_H8S_AB
-    case 16: H8S_LAUNCH(0, 16); break;      // no compute: memory waves and barriers only
-    case 32: H8S_LAUNCH(0, 32); break;      // no source window DMA: compute, layer 2 and stores only
-    case 2: H8S_LAUNCH(0, 128); break;      // wave 4 issues its whole share of a window right after B
-    case 3: H8S_LAUNCH(0, 192); break;      // the same with an 11 / 10 split of the DMA rounds
-#endif
-    default: H8S_LAUNCH(0, 0); break;
-  }
-#undef H8S_LAUNCH
+  grid = xcd_stride_grid(grid, a.tiles_x);
+  LGPU_HIP(hipFuncSetAttribute((const void *)k_half8s, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k_half8s, dim3((unsigned)grid), dim3(kH8sThreads), lds, st, a, t, l);
   LGPU_CHECK_LAUNCH();
   return LGPU_OK;
 }
@@ -1876,7 +1705,7 @@ struct SepPlan {
 static int plan_sep(const Bank *hb, const Bank *vb, int sw, int sh, int irow, int dw, int dh, int orow, int ntracks,
                     int hround, int hshift, int vround, int vshift, SepPlan *p) {
   SepArgs &a = p->a;
-  a.dbg = nullptr; a.ntracks = ntracks; a.hco2 = a.vco2 = nullptr; a.nph = a.npv = 0; a.bfrag = nullptr; a.mh_r = 0;
+  a.ntracks = ntracks; a.hco2 = a.vco2 = nullptr; a.nph = a.npv = 0; a.bfrag = nullptr; a.mh_r = 0;
   a.sw = sw; a.sh = sh; a.irow = irow; a.dw = dw; a.dh = dh; a.orow = orow;
   a.hpos = hb->pos; a.hco = hb->co; a.nth = hb->nt;
   a.vpos = vb->pos; a.vco = vb->co; a.ntv = vb->nt;
@@ -1896,9 +1725,8 @@ static int plan_sep(const Bank *hb, const Bank *vb, int sw, int sh, int irow, in
   p->variant = (a.nth == 8 && a.ntv == 8) ? 1 : (a.nth == 5 && a.ntv == 5) ? 2 : (a.nth == 4 && a.ntv == 4) ? 3 :
                (a.nth == 2 && a.ntv == 2) ? 4 : (a.nth == 6 && a.ntv == 6) ? 5 : 0;
   // k_sep2 (dot2 on both passes): tap pair counts with an instantiation, windows that leave two workgroups per CU
-  const bool no_sep2 = tune_on(TUNE_NO_SEP2);
   const int nph = hb->nph;
-  if (!no_sep2 && (nph == 1 || nph == 2 || nph == 3 || nph == 4 || nph == 5 || nph == 6 || nph == 7 || nph == 8 || nph == 10 || nph == 12) && vb->nt <= 64) {
+  if ((nph == 1 || nph == 2 || nph == 3 || nph == 4 || nph == 5 || nph == 6 || nph == 7 || nph == 8 || nph == 10 || nph == 12) && vb->nt <= 64) {
     SepArgs b = a;
     b.hco2 = hb->co2h; b.vco2 = vb->co2v; b.nph = nph; b.npv = vb->npv;
     // the padded last tap pair reads one pixel further, rows come in even-aligned pairs
@@ -1920,12 +1748,10 @@ static int plan_sep(const Bank *hb, const Bank *vb, int sw, int sh, int irow, in
     };
     // tile height: 16 rows, 32 when enlarging (small windows: taller tiles amortise a workgroup's three phases; measured 29.8 against 33.9 us for
     // 1080p -> 4K, profiles/r02/resize_ratios.md)
-    size_t sep2_lds_cap = 80 * 1024;
-    { const int v = tune(TUNE_SEP2_LDS_KB); if (v >= 8 && v <= 160) sep2_lds_cap = (size_t)v * 1024; }      // tuning probe
     for (int th2 = dh > sh ? 32 : 16;; th2 >>= 1) {
       const int sht2 = window_rows(th2);
       const size_t lds2 = (size_t)sht2 * b.swt * 4 + (size_t)(sht2 >> 1) * kTileW * 16 + 256 + (size_t)th2 * (vb->npv + 1) * 4;
-      if (lds2 <= sep2_lds_cap || th2 == 1) {
+      if (lds2 <= 80 * 1024 || th2 == 1) {
         if (lds2 <= 160 * 1024) {
           b.th = th2; b.sht = sht2;
           b.tiles_y = (dh + th2 - 1) / th2;
@@ -1940,10 +1766,8 @@ static int plan_sep(const Bank *hb, const Bank *vb, int sw, int sh, int irow, in
     // the horizontal pass as a matrix product: same taps for every column, integer ratio, taps that split into int8 hi / 6-bit lo, at most two K blocks
     // (decided before the tile height: such a launch carries no per-column tap tables in LDS)
     p->mh_r = 0;
-    const bool no_sep2p = tune_on(TUNE_NO_SEP2P);
-    const bool no_mh = tune_on(TUNE_NO_SEP2P_MFMA);
-    const bool pers_ok = p->variant >= 100 && !no_sep2p && (sw & 3) == 0;
-    if (pers_ok && !no_mh && dw >= 1 && sw % dw == 0 && sw / dw >= 2 && hb->nt <= 32 && hround == 64 && hshift == 7) {
+    const bool pers_ok = p->variant >= 100 && (sw & 3) == 0;
+    if (pers_ok && dw >= 1 && sw % dw == 0 && sw / dw >= 2 && hb->nt <= 32 && hround == 64 && hshift == 7) {
       const int r = sw / dw, c0 = hb->hpos[0] & 3, nt = hb->nt;
       bool ok = (c0 + 3 * r + nt) <= 32;
       for (int c = 0; c < dw && ok; c++) {
@@ -1959,9 +1783,8 @@ static int plan_sep(const Bank *hb, const Bank *vb, int sw, int sh, int irow, in
       }
     }
     // k_sep2p: two window slots + double-buffered tables must leave two workgroups per CU; a window is at most kS2pMaxReq DMA requests
-    const int th_force = tune(TUNE_SEP2P_TH) > 0 ? tune(TUNE_SEP2P_TH) : 0;
     if (pers_ok) {
-      for (int th2 = th_force ? th_force : dh > sh ? 32 : 16; th2 >= 1; th2 >>= 1) {
+      for (int th2 = dh > sh ? 32 : 16; th2 >= 1; th2 >>= 1) {
         const int sht2 = window_rows(th2);
         const S2pLds L(sht2, a.swt, th2, vb->npv, p->mh_r ? 1 : nph);
         if (L.total <= 80 * 1024 && sht2 * (a.swt >> 2) <= kS2pMaxReq * 64 && th2 * (vb->npv + 1) <= 256 && vb->npv <= kS2pMaxNpv) {
@@ -2023,7 +1846,6 @@ static int launch_sep(const SepPlan &p, const SepTracks &t, const Lut8 &l, hipSt
       LGPU_HIP(hipFuncSetAttribute((const void *)k_sep2<N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds)); \
     hipLaunchKernelGGL((k_sep2<N>), p.grid, blk, p.lds, st, p.a, t, l);                                      \
   } while (0)
-  if (tune_on(TUNE_PLAN_DEBUG)) fprintf(stderr, "plan: %dx%d -> %dx%d variant %d lds %zu th %d sht %d swt %d | pers %d vec %d mh_r %d p_th %d p_sht %d p_lds %zu npv %d nth %d\n", p.a.sw, p.a.sh, p.a.dw, p.a.dh, p.variant, p.lds, p.a.th, p.a.sht, p.a.swt, (int)p.pers, p.a.vec, p.mh_r, p.p_th, p.p_sht, p.p_lds, p.a.npv, p.a.nth);
   const bool s2p_force = tune_on(TUNE_SEP2P_FORCE);          // tests: the persistent kernel on small frames
   // k_sep2p pays when a workgroup gets a few tiles to pipeline and the windows are the heavy part (shrinking); measured in profiles/r02/resize_ratios.md
   if (p.pers && p.a.vec && p.variant >= 100 &&
@@ -2042,17 +1864,7 @@ static int launch_sep(const SepPlan &p, const SepTracks &t, const Lut8 &l, hipSt
     int g = (nwork + 7) & ~7;
     if (g > 2 * g_cus) g = (2 * g_cus) & ~7;          // two workgroups per CU by LDS (three or four smaller ones measured slower: 38 / 48 us against 24 for 4K -> 720p)
     if (g < 8) g = 8;
-    if (g >= 64) {                                     // the tile-list stride (g / 8) must not share a large factor with the tiles per row (see try_half8)
-      auto gcd = [](int x, int y) { while (y) { const int t_ = x % y; x = y; y = t_; } return x; };
-      int w = g >> 3;
-      for (int k = 0; k < 6 && w - k >= 8; k++)
-        if (gcd(w - k, ap.tiles_x) <= 2) { w -= k; break; }
-      g = w << 3;
-    }
-    const bool s2p_dbg = tune_on(TUNE_PHASE_PROFILE);      // the instrumented kernel path (allocates, synchronises): its own switch, not LGPU_PLAN_DEBUG
-    ap.dbg = nullptr;
-    const int nwv = (p.mh_r ? kS2pMhCW : 4) + 2;
-    if (s2p_dbg) { LGPU_HIP(hipMalloc((void **)&ap.dbg, (size_t)g * nwv * 8 * 8)); LGPU_HIP(hipMemsetAsync(ap.dbg, 0, (size_t)g * nwv * 8 * 8, st)); }
+    g = xcd_stride_grid(g, ap.tiles_x);
 #define SEP2P_LAUNCH(N)                                                                                      \
   do {                                                                                                       \
     if (p.p_lds > 48 * 1024)                                                                                 \
@@ -2081,21 +1893,6 @@ static int launch_sep(const SepPlan &p, const SepTracks &t, const Lut8 &l, hipSt
     }
 #undef SEP2P_LAUNCH
     LGPU_CHECK_LAUNCH();
-    if (s2p_dbg) {           // debugging aid: mean cycles (100 MHz s_memtime ticks) per phase over the workgroups, compute wave 0 and the two memory waves
-      std::vector<unsigned long long> h((size_t)g * nwv * 8);
-      LGPU_HIP(hipStreamSynchronize(st));
-      LGPU_HIP(hipMemcpy(h.data(), ap.dbg, h.size() * 8, hipMemcpyDeviceToHost));
-      LGPU_HIP(hipFree(ap.dbg));
-      double acc[3][4] = {{0}};
-      for (int b = 0; b < g; b++)
-        for (int k = 0; k < 4; k++) { acc[0][k] += (double)h[((size_t)b * nwv + 0) * 8 + k]; acc[1][k] += (double)h[((size_t)b * nwv + nwv - 2) * 8 + k]; acc[2][k] += (double)h[((size_t)b * nwv + nwv - 1) * 8 + k]; }
-      int occ = -1;
-      if (p.mh_r) { if (p.mh_kb == 1) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_sep2p<1, 1, kS2pMhCW>, (kS2pMhCW + 2) * 64, lds_launch); else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_sep2p<1, 2, kS2pMhCW>, (kS2pMhCW + 2) * 64, lds_launch); }
-      fprintf(stderr, "occupancy (workgroups per CU by the runtime's calculator): %d\n", occ);
-      fprintf(stderr, "k_sep2p<%d>%s grid %d th %d sht %d swt %d tiles %d lds %zu | compute w0: A %.0f H %.0f B %.0f V %.0f | mem w4: A %.0f land %.0f B %.0f issue %.0f | mem w5: A %.0f land %.0f B %.0f issue %.0f (ticks of 10 ns, mean per workgroup)\n",
-              p.variant - 100, p.mh_r ? " (matrix-core horizontal pass)" : "", g, ap.th, ap.sht, ap.swt, nwork, lds_launch, acc[0][0] / g, acc[0][1] / g, acc[0][2] / g, acc[0][3] / g, acc[1][0] / g, acc[1][1] / g, acc[1][2] / g,
-              acc[1][3] / g, acc[2][0] / g, acc[2][1] / g, acc[2][2] / g, acc[2][3] / g);
-    }
     return LGPU_OK;
   }
   switch (p.variant) {
@@ -2143,12 +1940,9 @@ static int get_scratch(size_t bytes, hipStream_t st, void **out) {
   return LGPU_OK;
 }
 
-// 5x5 binomial blur through k_gauss5x; LGPU_E_UNSUPPORTED when the frames are not 8-byte aligned (or LGPU_G5_CLASSIC
-// asks for the generic separable kernel, for A/B runs)
+// 5x5 binomial blur through k_gauss5x; LGPU_E_UNSUPPORTED when the frames are not 8-byte aligned
 static int try_gauss5x(int w, int h, int irow, int orow, int blend, int irow2, uint32_t bf, const int32_t *bf_d, int use_lut,
                        const SepTracks &t, int ntracks, const Lut8 &l, hipStream_t st) {
-  const bool classic = tune_on(TUNE_G5_CLASSIC);
-  if (classic) return LGPU_E_UNSUPPORTED;
   if (irow & 7) return LGPU_E_UNSUPPORTED;
   for (int i = 0; i < ntracks; i++)
     if (((uintptr_t)t.src[i] & 7) || ((uintptr_t)t.dst[i] & 3) || (blend && ((uintptr_t)t.l2[i] & 3))) return LGPU_E_UNSUPPORTED;
@@ -2161,11 +1955,7 @@ static int try_gauss5x(int w, int h, int irow, int orow, int blend, int irow2, u
   a.tiles_x = (w + kG5W - 1) / kG5W;
   const int tiles_y = (h + kG5H * kG5Sub - 1) / (kG5H * kG5Sub);
   const dim3 grid((unsigned)(a.tiles_x * tiles_y), (unsigned)ntracks);
-  const bool mfma_h = tune_on(TUNE_G5_MFMA);       // the matrix-core form of the horizontal pass (north_star names it; measured slower: profiles/r02/gauss5_mfma.md), LGPU_G5_MFMA / lgpu_tuning_set
-  if (mfma_h) {
-    if (blend || use_lut) hipLaunchKernelGGL((k_gauss5x<true, true>), grid, dim3(256), 0, st, a, t, l);
-    else hipLaunchKernelGGL((k_gauss5x<false, true>), grid, dim3(256), 0, st, a, t, l);
-  } else if (blend || use_lut) hipLaunchKernelGGL(k_gauss5x<true>, grid, dim3(256), 0, st, a, t, l);
+  if (blend || use_lut) hipLaunchKernelGGL(k_gauss5x<true>, grid, dim3(256), 0, st, a, t, l);
   else hipLaunchKernelGGL(k_gauss5x<false>, grid, dim3(256), 0, st, a, t, l);
   LGPU_CHECK_LAUNCH();
   return LGPU_OK;
@@ -2237,8 +2027,7 @@ extern "C" int lgpu_gauss5(const uint8_t *src_d, int irow, uint8_t *dst_d, int o
   hipStream_t st = (hipStream_t)stream;
   const Lut8 l = pack_lut(nullptr);
   // aligned 3- / 4-byte frames: the register-pipelined row walk of fused.hip (the same arithmetic; profiles/r03/ops_roofline.md)
-  const bool no_rows = tune_on(TUNE_GAUSS5_NO_ROWS);
-  if (!no_rows && (psize == 3 || psize == 4)) {
+  if (psize == 3 || psize == 4) {
     rc = lgpu::gauss5_rows(src_d, irow, dst_d, orow, width, height, psize, st);
     if (rc != LGPU_E_UNSUPPORTED) return rc;
   }

@@ -106,9 +106,10 @@ int device_cus() {
 }
 
 static const char *const kTuneNames[TUNE_COUNT] = {
-  "PBH_ALIGNED", "PBH_TH", "PB_NO_DOUBLE", "PB_NO_HALF3", "PB_NO_PAIRS", "PB_NO_GATHER", "PB_NO_UP", "PB_UP_RB",
-  "GCK_TH", "CHAIN_SPARE_WGS", "SEP2_LDS_KB", "NO_SEP2P", "NO_SEP2P_MFMA", "PLAN_DEBUG",
-  "SEP2P_FORCE", "PB_CACHE_MAX", "K2_WGS", "SOFT_NO_S", "SOFT_RB", "EDGE_NO_S", "EDGE_TH", "PBH_ORDER", "PBH_OCC", "PBH_GROUP", "G5_MFMA", "RGB2YUV_NO_S", "UYVY_NO_S", "REPACK_NO_S", "DISABLE_HALF8", "NO_SEP2", "SEP2P_TH", "G5_CLASSIC", "GAUSS5_NO_ROWS", "PB_NO_PRE", "PB_LDS_KB", "PHASE_PROFILE", "PB_TILE_ORDER", "PB_CHAIN_GROUP", "SEAM_STAGED"};
+#define LGPU_TUNE_NAME(n) #n,
+  LGPU_TUNE_SWITCHES(LGPU_TUNE_NAME)
+#undef LGPU_TUNE_NAME
+};
 static std::atomic<int> g_tune[TUNE_COUNT];
 static std::once_flag g_tune_once;
 static void tune_init() {
@@ -130,7 +131,7 @@ int tune(Tune t) {
 
 extern "C" {
 
-// launch-shape / ablation switches by name (the LGPU_<NAME> environment variables without the prefix); value < 0 clears a switch.  Results never depend on them.
+// launch-shape switches by name (the LGPU_<NAME> environment variables without the prefix); value < 0 clears a switch.  Results never depend on them.
 int lgpu_tuning_set(const char *name, int value) {
   if (!name) { lgpu::set_error("lgpu_tuning_set: null name"); return LGPU_E_BADARG; }
   lgpu::tune_init();

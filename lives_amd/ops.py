@@ -35,7 +35,7 @@ def init(device=0):
 
 
 def tuning(name, value):
-    """a launch-shape / ablation switch by name (lgpu_tuning_set; value < 0 or None clears it); returns the previous value (-1: unset)"""
+    """a launch-shape switch by name (lgpu_tuning_set; value < 0 or None clears it); returns the previous value (-1: unset)"""
     L = lib.load()
     old = L.lgpu_tuning_get(name.encode())
     assert L.lgpu_tuning_set(name.encode(), -1 if value is None else int(value)) == 0, lib.last_error()

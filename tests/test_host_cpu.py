@@ -223,3 +223,31 @@ def test_clamped_luma_premultiply_tables_have_an_exact_integer_form():
     for tab, lim, cap in ((t[0], 219, 235), (t[1], 224, 240)):
         cand = np.where((2 * j * i + 255) // 510 > lim, cap, (2 * (j - 16) * i + 8415) // 510)
         assert (cand == tab).all()
+
+
+TUNE_KEPT = ["PBH_ALIGNED", "PBH_TH", "PBH_ORDER", "PBH_GROUP", "PBH_OCC", "PB_NO_PAIRS", "PB_UP_RB", "PB_CACHE_MAX", "PB_CHAIN_GROUP",
+             "CHAIN_SPARE_WGS", "SEP2P_FORCE", "SOFT_NO_S", "SOFT_RB", "EDGE_NO_S", "EDGE_TH", "SEAM_STAGED"]
+TUNE_RETIRED = ["PB_NO_DOUBLE", "PB_NO_HALF3", "PB_NO_GATHER", "PB_NO_UP", "PB_NO_PRE", "PB_LDS_KB", "PB_TILE_ORDER", "PLAN_DEBUG",
+                "DISABLE_HALF8", "NO_SEP2", "NO_SEP2P", "NO_SEP2P_MFMA", "G5_CLASSIC", "GAUSS5_NO_ROWS", "SEP2_LDS_KB", "SEP2P_TH", "G5_MFMA",
+                "PHASE_PROFILE", "GCK_TH", "K2_WGS", "RGB2YUV_NO_S", "UYVY_NO_S", "REPACK_NO_S"]
+
+
+def test_tuning_switches_are_the_ones_the_tests_walk():
+    """lgpu_tuning_set knows exactly the launch-shape switches some test sets (the table in lgpu_common.h); a retired name is refused like any
+    unknown one.  Every value touched is restored."""
+    L = lib.load()
+    text = open(os.path.join(ROOT, "lives_amd", "csrc", "lgpu_common.h")).read()
+    table = re.search(r"#define LGPU_TUNE_SWITCHES\(X\)((?:.*\\\n)*.*)", text).group(1)
+    assert sorted(re.findall(r"X\((\w+)\)", table)) == sorted(TUNE_KEPT)
+    for name in TUNE_KEPT:
+        old = L.lgpu_tuning_get(name.encode())
+        try:
+            assert L.lgpu_tuning_set(name.encode(), 7) == 0, name
+            assert L.lgpu_tuning_get(name.encode()) == 7, name
+        finally:
+            assert L.lgpu_tuning_set(name.encode(), old) == 0
+        assert L.lgpu_tuning_get(name.encode()) == old
+    for name in TUNE_RETIRED:
+        assert L.lgpu_tuning_set(name.encode(), 1) == -2, name        # LGPU_E_BADARG
+        assert b"unknown switch" in L.lgpu_last_error()
+        assert L.lgpu_tuning_get(name.encode()) == -1, name

@@ -3,7 +3,7 @@
 # One interleaved A / B / ... comparison of launch-shape switches (LGPU_* variables, lgpu_common.h's Tune table): every setting in turn, REPS rounds (default 2), so that
 # clock and box drift hit all of them alike.  Default: `python bench.py --full --no-cpu ARGS` and its roofline.launch_us; -o: `python tools/bench_one.py ARGS` (single
 # entry points by graph replay) and its lines.  "-" stands for "no variable set".  Replaces the per-experiment *_ab.sh scripts of rounds 3 and 4, e.g.
-#   tools/ab.sh - LGPU_PBH_ORDER=1 LGPU_PBH_ORDER=2 -- --tracks 16          tools/ab.sh -o - LGPU_GCK_TH=12 -- --cold c4rgba fx8:c4rgba
+#   tools/ab.sh - LGPU_PBH_ORDER=1 LGPU_PBH_ORDER=2 -- --tracks 16          tools/ab.sh -o - LGPU_EDGE_TH=16 -- --cold edge
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 reps=2; one=0
 while [ "$1" = "-r" ] || [ "$1" = "-o" ]; do if [ "$1" = "-r" ]; then reps=$2; shift 2; else one=1; shift; fi; done

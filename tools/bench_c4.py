@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/bench_c4.py -- BASELINE config 4 in one launch (lgpu_gauss5_colorkey) on 3840x2160 RGBA32 and RGB24, HIP-graph replay; LGPU_GCK_TH sets the band height"""
+"""tools/bench_c4.py -- BASELINE config 4 in one launch (lgpu_gauss5_colorkey) on 3840x2160 RGBA32 and RGB24, HIP-graph replay"""
 import json
 import os
 import sys
@@ -41,7 +41,7 @@ def main():
         torch.cuda.synchronize()
         us = e0.elapsed_time(e1) * 1e3 / (10 * 4 * nb)
         ab = 3 * w * h * ps
-        print(json.dumps({"op": "C4 gauss5 -> colour key %s 3840x2160, th=%s" % ("RGBA32" if ps == 4 else "RGB24", os.environ.get("LGPU_GCK_TH", "default")), "us": round(us, 2),
+        print(json.dumps({"op": "C4 gauss5 -> colour key %s 3840x2160" % ("RGBA32" if ps == 4 else "RGB24"), "us": round(us, 2),
                           "algorithmic_bytes": ab, "frac_of_8TBs": round(ab / us / 1e3 / 8000, 4)}), flush=True)
 
 
