@@ -425,6 +425,18 @@ int lgpu_chain_canvas(const lgpu_chain_params *params, const lgpu_canvas *canvas
    layer 2; amounts may be NULL), and sw == dw && sh == dh -- no resize stage: [R <-> B] [-> letterbox] [-> blend] [-> gamma LUT] on frames that already have their
    size (dst must not be src). */
 int lgpu_chain_amounts(const lgpu_chain_params *params, const lgpu_canvas *canvas, const lgpu_chain_track *tracks, int ntracks, const uint8_t *amounts, void *stream);
+/* the same chain starting at decoded planar YUV 4:2:0 frames (YUV420P; YVU420P: pass the planes swapped): the K2 conversion (lgpu_yuv420p_to_rgb, every quirk kept,
+   no gamma LUT in it) -> [R <-> B when params->swap_rb] -> scale [-> letterbox] [-> chroma blend] [-> gamma LUT], ONE launch for every track, and no RGBA frame is
+   ever written.  Conventions of lgpu_chain_amounts (LGPU_INTERP_PIXBUF required; LGPU_INTERP_NOBLEND: no layer 2, amounts may be NULL).  The converted frame has
+   alpha 255 everywhere, so the scaler's all-opaque arithmetic is exact and used.  src: plane rowstrides (any), chroma plane sizes (they must hold the (sw / 2) x
+   (sh / 2) samples; K2's one read past the last row's end is clamped to the last byte), out_order 0 RGBA / 1 BGRA, which_tables / pb_quality / flags
+   (LGPU_YUV_FIX_EDGES) as lgpu_yuv420p_to_rgb.  Every argument is checked before anything is enqueued: LGPU_E_BADARG.  Only the one-launch form is served --
+   exact 2:1 (sw == 2 dw, sh == 2 dh, sw % 4 == 0), HYPER or BILINEAR, no gaussian, an even canvas offs_x, 8-byte aligned destination / layer 2 rows -- anything else
+   is LGPU_E_UNSUPPORTED (run lgpu_yuv420p_to_rgb_batch + lgpu_chain_amounts then); nothing is written in either case. */
+typedef struct { const uint8_t *y_d, *u_d, *v_d; const uint8_t *layer2_d; uint8_t *dst_d; } lgpu_chain_yuv_track;
+typedef struct { int istrides[3]; long u_size, v_size; int out_order; int which_tables; int pb_quality; int flags; } lgpu_yuv_source;
+int lgpu_chain_yuv420p(const lgpu_chain_params *params, const lgpu_yuv_source *src, const lgpu_canvas *canvas, const lgpu_chain_yuv_track *tracks, int ntracks,
+                       const uint8_t *amounts, void *stream);
 
 /* ---- timing helper: HIP events on `stream` around `reps` launches of the last-configured chain; used by
    bench.py to measure the kernel's average launch duration on the stream it is launched on. */

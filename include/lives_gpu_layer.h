@@ -153,12 +153,19 @@ int lives_gpu_layer_set_opaque(lives_gpu_layer_t *layer, int on);
    "chroma blend" in place, gamma_convert_layer -- are RECORDED on the plane (every leaf changes as in the eager call) and run as ONE launch of the fused chain
    kernel: by themselves when anyone needs the pixels (another seam call, an effect, sync / unpin), or for all tracks of a tick together when the host calls
    lives_gpu_layers_flush(layers, n) after its plan steps have returned (programs of equal shape share the launch: this is lgpu_chain, reached through the
-   reference's own calls).  Results are those of the eager calls, bit for bit (tests/test_deferred.py).  What a stage can refuse is checked when it is recorded;
+   reference's own calls).  A decoder's YUV420P / YVU420P frame converted to RGBA32 / BGRA32 without a gamma change is recorded the same way (the program takes the
+   three planes; external surfaces of lives_gpu_layer_pin_device are only read): a flush then runs the group as ONE lgpu_chain_yuv420p launch in the exact 2:1
+   shape, as at most two launches otherwise (the batched conversion, then lgpu_chain_amounts).  Results are those of the eager calls, bit for bit
+   (tests/test_deferred.py, tests/test_deferred_yuv.py).  What a stage can refuse is checked when it is recorded;
    device failures at run time surface at the flush / sync that runs the program.  lives_gpu_set_deferred(0) launches every call by itself (returns the old value). */
 int lives_gpu_set_deferred(int on);
 int lives_gpu_layers_flush(lives_gpu_layer_t *const *layers, int nlayers);
 /* counters since load: [0] stages recorded, [1] fused chain launches made for pending programs, [2] programs (tracks) those carried, [3] programs run stage by stage */
 void lives_gpu_deferred_stats(unsigned long long out[4]);
+/* the four counters above, then [4] YUV420P / YVU420P -> RGBA32 / BGRA32 conversions recorded (convert_layer_palette on a pinned layer, no gamma change), [5] one-launch
+   YUV chain launches (lgpu_chain_yuv420p) and [6] the tracks they carried, [7] conversion pre-launches of the two-launch path (lgpu_yuv420p_to_rgb_batch for a group whose
+   shape the one-launch form does not take); at most n entries are written */
+void lives_gpu_deferred_stats_n(unsigned long long *out, int n);
 /* (for livesgpu_fx.so) record an in-place "chroma blend" of the pending plane dst_host with the resident plane layer2_host; 1 = recorded, 0 = run the kernel */
 int lives_gpu_deferred_blend_chroma(const void *dst_host, int orow, int width, int height, int palette, const void *layer2_host, int irow2, int bf);
 /* the host is about to free or replace the pixel_data of a pinned layer itself (weed_layer_pixel_data_free, an error path): release the

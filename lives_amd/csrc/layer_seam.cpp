@@ -586,7 +586,9 @@ lives_gpu_boolean decline(weed_plant_t *layer) {
 // What a stage could refuse is checked when it is recorded (palette, geometry, the scaler's range), so a recorded call cannot turn into a FALSE later; a device
 // failure at run time (allocation, launch) surfaces at the flush / sync that runs the program, which then stays pending.
 // lives_gpu_set_deferred(0) switches the recording off (every call launches its own kernels, as before round 6); tests compare the two.
-enum { LZ_NONE = 0, LZ_SWAP = 1, LZ_SCALE = 2, LZ_CANVAS = 3, LZ_BLEND = 4, LZ_LUT = 5 };
+// LZ_YUV: a decoder's YUV420P / YVU420P frame converted to RGBA32 / BGRA32 (K2, no gamma change) -- the program then owns (or, for surfaces of
+// lives_gpu_layer_pin_device, borrows) the three source planes and stands for the new RGBA host plane; the stages above are recorded on top of it.
+enum { LZ_NONE = 0, LZ_YUV = 1, LZ_SWAP = 2, LZ_SCALE = 3, LZ_CANVAS = 4, LZ_BLEND = 5, LZ_LUT = 6 };
 struct Lazy {
   Dev src;                          // the frame the program starts from (owned: goes back to the pool when the program has run, unless external)
   int sw = 0, sh = 0, srs = 0;
@@ -597,9 +599,12 @@ struct Lazy {
   bool blend = false; int bf = 0; const void *l2h = nullptr; Dev l2; int l2rs = 0;
   bool lut = false; uint8_t lut8[256];
   int w = 0, h = 0, rs = 0;         // the plane the program stands for
+  // LZ_YUV: src is the luma plane; yu / yv the chroma planes (U, V order: a YVU420P layer's planes are swapped when recorded)
+  bool yuv = false; Dev yu, yv; int ystr[3] = {0, 0, 0}; long usz = 0, vsz = 0; int order = 0, which = 0, quality = 2;
 };
 std::atomic<int> g_deferred{1};
 std::atomic<unsigned long long> g_lz_recorded{0}, g_lz_chain_launches{0}, g_lz_chain_tracks{0}, g_lz_staged{0};      // lives_gpu_deferred_stats
+std::atomic<unsigned long long> g_lz_yuv_recorded{0}, g_lz_yuv_launches{0}, g_lz_yuv_tracks{0}, g_lz_yuv_pre{0};        // lives_gpu_deferred_stats_n [4..7]
 std::mutex g_lazy_mu;               // one program (group) runs at a time; never taken with a table lock held
 bool lazy_pal(int pal) { return pal == WEED_PALETTE_RGBA32 || pal == WEED_PALETTE_BGRA32; }
 
@@ -614,19 +619,22 @@ void lazy_unread(Lazy *z) {          // (no lock held) the program no longer rea
 void lazy_discard(Lazy *z) {
   if (!z) return;
   lazy_unread(z);
-  Dev src = z->src;
+  Dev src = z->src, yu = z->yu, yv = z->yv;
+  const bool yuv = z->yuv;
   delete z;
   pool_give(src);
+  if (yuv) { pool_give(yu); pool_give(yv); }
 }
 bool lazy_same_shape(const Lazy *a, const Lazy *b) {
   return a->sw == b->sw && a->sh == b->sh && a->srs == b->srs && a->swap == b->swap && a->scale == b->scale && a->dw == b->dw && a->dh == b->dh &&
          a->interp == b->interp && a->opaque == b->opaque && a->canvas == b->canvas && a->nw == b->nw && a->nh == b->nh && a->ox == b->ox && a->oy == b->oy && a->blend == b->blend &&
-         a->l2rs == b->l2rs &&          /* (not the blend amount: every track of a launch has its own, lgpu_chain_amounts) */ a->lut == b->lut && (!a->lut || !memcmp(a->lut8, b->lut8, 256)) && a->w == b->w && a->h == b->h && a->rs == b->rs;
+         a->l2rs == b->l2rs &&          /* (not the blend amount: every track of a launch has its own, lgpu_chain_amounts) */ a->lut == b->lut && (!a->lut || !memcmp(a->lut8, b->lut8, 256)) && a->w == b->w && a->h == b->h && a->rs == b->rs &&
+         a->yuv == b->yuv && (!a->yuv || (!memcmp(a->ystr, b->ystr, sizeof a->ystr) && a->usz == b->usz && a->vsz == b->vsz && a->order == b->order && a->which == b->which && a->quality == b->quality));
 }
 // one program, stage by stage through stream-ordered scratch frames, into out (the plane's rowstride)
-int lazy_run_staged(const Lazy *z, uint8_t *out) {
-  const uint8_t *cur = (const uint8_t *)z->src.d;
-  int cw = z->sw, ch = z->sh, crs = z->srs, rc = LGPU_OK;
+int lazy_run_staged(const Lazy *z, uint8_t *out, const uint8_t *src, int srs) {
+  const uint8_t *cur = src;
+  int cw = z->sw, ch = z->sh, crs = srs, rc = LGPU_OK;
   void *tmp[3] = {nullptr, nullptr, nullptr};
   int nt = 0;
   const int last_geo = z->canvas ? LZ_CANVAS : z->scale ? LZ_SCALE : LZ_SWAP;
@@ -669,29 +677,79 @@ int lazy_run_group(Lazy *const *zs, const void *const *hs, int n) {
     if (!pool_take(bytes, &outs[(size_t)i])) { for (int k = 0; k < i; k++) pool_give(outs[(size_t)k]); return LGPU_E_NOMEM; }
   for (int i = 0; i < n; i++) {
     await(zs[i]->src, false);
+    if (zs[i]->yuv) { await(zs[i]->yu, false); await(zs[i]->yv, false); }
     if (zs[i]->blend) await(zs[i]->l2, false);
     if (z0->rs != z0->w * 4) rc = rc ? rc : lgpu_fill(outs[(size_t)i].d, 0, bytes, S());      // the row padding of a fresh plane is zero (calloc in the eager path)
   }
   bool done = false;
+  const bool staged = lgpu_tuning_get("SEAM_STAGED") > 0;
+  // the RGBA frames the later stages start from: the recorded source planes, or -- behind a YUV stage that is not fused -- converted scratch frames
+  std::vector<const uint8_t *> srcp((size_t)n);
+  for (int i = 0; i < n; i++) srcp[(size_t)i] = (const uint8_t *)zs[i]->src.d;
+  int srow = z0->srs;
+  void *scr = nullptr;
+  lgpu_chain_params pr;
+  memset(&pr, 0, sizeof pr);
+  pr.sw = z0->sw; pr.sh = z0->sh; pr.irow = z0->srs; pr.dw = z0->scale ? z0->dw : z0->sw; pr.dh = z0->scale ? z0->dh : z0->sh; pr.irow2 = z0->l2rs; pr.orow = z0->rs;
+  pr.swap_rb = z0->swap ? 1 : 0; pr.interp = (z0->scale ? z0->interp : 0) | LGPU_INTERP_PIXBUF | (z0->blend ? 0 : LGPU_INTERP_NOBLEND) | (z0->scale && z0->opaque ? LGPU_INTERP_OPAQUE : 0); pr.do_blur = 0; pr.bf = z0->bf; pr.use_lut = z0->lut ? 1 : 0;
+  if (!z0->blend) pr.irow2 = z0->rs;
+  if (z0->lut) memcpy(pr.lut8, z0->lut8, 256);
+  std::vector<uint8_t> amounts((size_t)n);
+  for (int i = 0; i < n; i++) amounts[(size_t)i] = (uint8_t)zs[i]->bf;
+  const lgpu_canvas cv = {z0->nw, z0->nh, z0->ox, z0->oy};
+  if (!rc && z0->yuv) {
+    const int strides[3] = {z0->ystr[0], z0->ystr[1], z0->ystr[2]};
+    if (!staged && z0->scale && n <= LGPU_CHAIN_MAX_TRACKS) {
+      // the one-launch form: the conversion rides in the chain's loads (lgpu_chain_yuv420p); every other shape is refused there and takes the two launches below
+      lgpu_yuv_source ys;
+      memset(&ys, 0, sizeof ys);
+      ys.istrides[0] = strides[0]; ys.istrides[1] = strides[1]; ys.istrides[2] = strides[2]; ys.u_size = z0->usz; ys.v_size = z0->vsz;
+      ys.out_order = z0->order; ys.which_tables = z0->which; ys.pb_quality = z0->quality; ys.flags = 0;
+      std::vector<lgpu_chain_yuv_track> yt((size_t)n);
+      for (int i = 0; i < n; i++) {
+        yt[(size_t)i].y_d = (const uint8_t *)zs[i]->src.d; yt[(size_t)i].u_d = (const uint8_t *)zs[i]->yu.d; yt[(size_t)i].v_d = (const uint8_t *)zs[i]->yv.d;
+        yt[(size_t)i].layer2_d = (const uint8_t *)zs[i]->l2.d; yt[(size_t)i].dst_d = (uint8_t *)outs[(size_t)i].d;
+      }
+      const int crc = lgpu_chain_yuv420p(&pr, &ys, z0->canvas ? &cv : nullptr, yt.data(), n, z0->blend ? amounts.data() : nullptr, S());
+      if (crc == LGPU_OK) { done = true; g_lz_chain_launches++; g_lz_chain_tracks += (unsigned long long)n; g_lz_yuv_launches++; g_lz_yuv_tracks += (unsigned long long)n; }
+      else if (crc != LGPU_E_BADARG && crc != LGPU_E_UNSUPPORTED) rc = crc;
+    }
+    if (!rc && !done) {
+      // two launches: the group's conversions in one batch (SEAM_STAGED: one call per track), then the RGBA program -- or straight into the planes when the
+      // conversion is all there is
+      const bool only = !z0->swap && !z0->scale && !z0->canvas && !z0->blend && !z0->lut;
+      const size_t per = (size_t)z0->sw * 4 * z0->sh;
+      if (!only && (rc = lgpu_malloc_ordered(&scr, per * (size_t)n + 64, S()))) scr = nullptr;
+      std::vector<lgpu_yuv_frame> fr((size_t)n);
+      for (int i = 0; i < n; i++) {
+        fr[(size_t)i].y_d = (const uint8_t *)zs[i]->src.d; fr[(size_t)i].u_d = (const uint8_t *)zs[i]->yu.d; fr[(size_t)i].v_d = (const uint8_t *)zs[i]->yv.d;
+        fr[(size_t)i].dst_d = only ? (uint8_t *)outs[(size_t)i].d : (uint8_t *)scr + (size_t)i * per;
+      }
+      const int orow = only ? z0->rs : z0->sw * 4;
+      if (!rc && !staged && n <= LGPU_CHAIN_MAX_TRACKS) {
+        rc = lgpu_yuv420p_to_rgb_batch(n, fr.data(), strides, z0->usz, z0->vsz, orow, z0->sw, z0->sh, 4, z0->order, 0, z0->which, z0->quality, nullptr, 0, S());
+        if (!rc) g_lz_yuv_pre++;
+      } else
+        for (int i = 0; i < n && !rc; i++)
+          rc = lgpu_yuv420p_to_rgb(fr[(size_t)i].y_d, fr[(size_t)i].u_d, fr[(size_t)i].v_d, strides, z0->usz, z0->vsz, fr[(size_t)i].dst_d, orow, z0->sw, z0->sh, 4,
+                                   z0->order, 0, z0->which, z0->quality, nullptr, 0, S());
+      if (only) done = true;
+      for (int i = 0; i < n; i++) srcp[(size_t)i] = (const uint8_t *)fr[(size_t)i].dst_d;
+      srow = z0->sw * 4;
+      pr.irow = srow;
+    }
+  }
   // every shape: with or without a resize stage, with or without a blend (lgpu_chain_amounts); LGPU_SEAM_STAGED / lgpu_tuning_set("SEAM_STAGED", 1): the fallback walk, for tests
-  if (!rc && n <= LGPU_CHAIN_MAX_TRACKS && lgpu_tuning_get("SEAM_STAGED") <= 0) {
-    lgpu_chain_params pr;
-    memset(&pr, 0, sizeof pr);
-    pr.sw = z0->sw; pr.sh = z0->sh; pr.irow = z0->srs; pr.dw = z0->scale ? z0->dw : z0->sw; pr.dh = z0->scale ? z0->dh : z0->sh; pr.irow2 = z0->l2rs; pr.orow = z0->rs;
-    pr.swap_rb = z0->swap ? 1 : 0; pr.interp = (z0->scale ? z0->interp : 0) | LGPU_INTERP_PIXBUF | (z0->blend ? 0 : LGPU_INTERP_NOBLEND) | (z0->scale && z0->opaque ? LGPU_INTERP_OPAQUE : 0); pr.do_blur = 0; pr.bf = z0->bf; pr.use_lut = z0->lut ? 1 : 0;
-    if (!z0->blend) pr.irow2 = z0->rs;
-    if (z0->lut) memcpy(pr.lut8, z0->lut8, 256);
+  if (!rc && !done && n <= LGPU_CHAIN_MAX_TRACKS && !staged) {
     std::vector<lgpu_chain_track> tr((size_t)n);
-    for (int i = 0; i < n; i++) { tr[(size_t)i].src_d = (const uint8_t *)zs[i]->src.d; tr[(size_t)i].layer2_d = (const uint8_t *)zs[i]->l2.d; tr[(size_t)i].dst_d = (uint8_t *)outs[(size_t)i].d; }
-    std::vector<uint8_t> amounts((size_t)n);
-    for (int i = 0; i < n; i++) amounts[(size_t)i] = (uint8_t)zs[i]->bf;
-    const lgpu_canvas cv = {z0->nw, z0->nh, z0->ox, z0->oy};
+    for (int i = 0; i < n; i++) { tr[(size_t)i].src_d = srcp[(size_t)i]; tr[(size_t)i].layer2_d = (const uint8_t *)zs[i]->l2.d; tr[(size_t)i].dst_d = (uint8_t *)outs[(size_t)i].d; }
     const int crc = lgpu_chain_amounts(&pr, z0->canvas ? &cv : nullptr, tr.data(), n, amounts.data(), S());
     if (crc == LGPU_OK) { done = true; g_lz_chain_launches++; g_lz_chain_tracks += (unsigned long long)n; }
     else if (crc != LGPU_E_BADARG && crc != LGPU_E_UNSUPPORTED) rc = crc;          // a shape the fused kernel does not take runs stage by stage below
   }
   if (!rc && !done)
-    for (int i = 0; i < n && !rc; i++) { rc = lazy_run_staged(zs[i], (uint8_t *)outs[(size_t)i].d); g_lz_staged++; }
+    for (int i = 0; i < n && !rc; i++) { rc = lazy_run_staged(zs[i], (uint8_t *)outs[(size_t)i].d, srcp[(size_t)i], srow); g_lz_staged++; }
+  if (scr) lgpu_free_ordered(scr, S());
   if (rc) {                                                                            // the programs stay pending; what was enqueued wrote scratch only
     for (int i = 0; i < n; i++) { outs[(size_t)i].stream = S(); pool_give(outs[(size_t)i]); }
     return rc;
@@ -718,10 +776,17 @@ int lazy_run_group(Lazy *const *zs, const void *const *hs, int n) {
       z->l2h = nullptr;
     }
     if (outs[(size_t)i].d) { outs[(size_t)i].stream = S(); pool_give(outs[(size_t)i]); }          // (the plane vanished meanwhile: cannot happen under the host's own ordering)
-    Dev src = z->src;
-    src.stream = S(); src.nr = 0;                                                       // its last use is the launch just enqueued
+    Dev src = z->src, yu = z->yu, yv = z->yv;
+    const bool yuv = z->yuv;
     delete z;
-    pool_give(src);
+    if (yuv) {
+      // the three source planes go back with the streams that read them kept (a later taker waits for the writer AND these readers)
+      note_use(src, false); note_use(yu, false); note_use(yv, false);
+      pool_give(src); pool_give(yu); pool_give(yv);
+    } else {
+      src.stream = S(); src.nr = 0;                                                     // its last use is the launch just enqueued
+      pool_give(src);
+    }
   }
   return LGPU_OK;
 }
@@ -830,6 +895,53 @@ bool lazy_commit(weed_plant_t *layer, const Layer &l, Lazy *z, int pal, int widt
   lazy_attach(np.pd[0], z);
   if (l.contiguous) pfree(l.pd[0]); else for (int i = 0; i < l.nplanes; i++) pfree(l.pd[i]);      // free_planes without the table (the entry has moved)
   commit_planes(layer, pal, width, height, np);
+  return true;
+}
+
+// convert_layer_palette_full(YUV420P / YVU420P -> RGBA32 / BGRA32) on a pinned layer whose three planes are resident: recorded as stage LZ_YUV of a new program
+// that takes the planes out of the table (owned; external surfaces borrowed) and stands for the new RGBA host plane.  false: not recorded, nothing changed.
+bool lazy_record_yuv(weed_plant_t *layer, const Layer &l, int outpl, int which, int new_gamma, int flags) {
+  if (!g_deferred.load(std::memory_order_relaxed) || !t_pinned || !lazy_pal(outpl) || l.nplanes != 3 || l.width < 2 || (l.width & 1) ||
+      (l.pal != WEED_PALETTE_YUV420P && l.pal != WEED_PALETTE_YVU420P))
+    return false;
+  const int iu = (l.pal == WEED_PALETTE_YVU420P) ? 2 : 1, iv = 3 - iu;            // swap_chroma_planes (:12353)
+  const int ch = plane_h(l, 1);
+  const void *hp[3] = {l.pd[0], l.pd[iu], l.pd[iv]};
+  const size_t need[3] = {(size_t)l.rs[0] * l.height, (size_t)l.rs[iu] * ch, (size_t)l.rs[iv] * ch};
+  for (int p = 0; p < 3; p++) {
+    ResShard &sh = shard_of(hp[p]);
+    std::lock_guard<SpinLock> lk(sh.mu);
+    auto it = sh.m.find(hp[p]);
+    if (it == sh.m.end() || !it->second.d || it->second.lazy || it->second.bytes < need[p] || it->second.lazy_readers > 0) return false;
+  }
+  Dev d[3];
+  for (int p = 0; p < 3; p++) {
+    ResShard &sh = shard_of(hp[p]);
+    std::lock_guard<SpinLock> lk(sh.mu);
+    auto it = sh.m.find(hp[p]);
+    if (it != sh.m.end()) { d[p] = it->second; sh.m.erase(it); }
+  }
+  auto put_back = [&]() {
+    for (int p = 0; p < 3; p++) {
+      if (!d[p].d) continue;
+      ResShard &sh = shard_of(hp[p]);
+      std::lock_guard<SpinLock> lk(sh.mu);
+      sh.m[hp[p]] = d[p];
+    }
+  };
+  if (!d[0].d || !d[1].d || !d[2].d) { put_back(); return false; }
+  Lazy *z = new Lazy;
+  z->src = d[0]; z->yu = d[1]; z->yv = d[2]; z->yuv = true; z->stage = LZ_YUV;
+  z->sw = l.width; z->sh = l.height; z->srs = l.width * 4;
+  z->ystr[0] = l.rs[0]; z->ystr[1] = l.rs[iu]; z->ystr[2] = l.rs[iv]; z->usz = (long)need[1]; z->vsz = (long)need[2];
+  z->order = pal_red_first(outpl) ? 0 : 1; z->which = which; z->quality = g_prefs.pb_quality;
+  if (!lazy_commit(layer, l, z, outpl, l.width, l.height, 0)) { delete z; put_back(); return false; }
+  g_lz_yuv_recorded++;
+  if (new_gamma != l.gamma) set_int(layer, WEED_LEAF_GAMMA_TYPE, new_gamma);
+  if (flags != l.flags) set_int(layer, kLeafHostFlags, flags);
+  g_api.leaf_delete(layer, WEED_LEAF_YUV_CLAMPING);                            // conv_done (:13881-13884)
+  g_api.leaf_delete(layer, WEED_LEAF_YUV_SUBSPACE);
+  g_api.leaf_delete(layer, WEED_LEAF_YUV_SAMPLING);
   return true;
 }
 
@@ -1181,6 +1293,9 @@ static lives_gpu_boolean convert_layer_palette_full_body(lives_gpu_layer_t *laye
       return 1;
     }
   }
+  if (!lutp && (inpl == WEED_PALETTE_YUV420P || inpl == WEED_PALETTE_YVU420P) && lazy_pal(outpl) &&
+      lazy_record_yuv(layer, l, outpl, (iclamping == WEED_YUV_CLAMPING_UNCLAMPED ? 1 : 0) | (l.subspace == WEED_YUV_SUBSPACE_BT709 ? 2 : 0), new_gamma, flags))
+    return 1;                                   // a decoder frame on a pinned layer: recorded, not launched (deferred execution, above)
   NewPlanes np;
   const int owidth = (inpl == WEED_PALETTE_UYVY || inpl == WEED_PALETTE_YUYV) ? l.width * 2 : inpl == WEED_PALETTE_YUV411 ? l.width * 4 : l.width;   // macropixels -> pixels (:13010, :13759)
   if (!alloc_planes(outpl, owidth, l.height, 0, &np)) return 0;
@@ -1575,7 +1690,7 @@ static int resize_pixbuf_body(weed_plant_t *layer, int width, int height, int in
     if (Lazy *z = lazy_detach(l, LZ_SCALE)) {
       if (scale_is_served(l.width, l.height, width, height, interp)) {
         const int prev = z->stage;
-        z->scale = true; z->dw = width; z->dh = height; z->interp = interp; z->stage = LZ_SCALE; z->opaque = has_leaf(layer, kLeafOpaque);
+        z->scale = true; z->dw = width; z->dh = height; z->interp = interp; z->stage = LZ_SCALE; z->opaque = has_leaf(layer, kLeafOpaque) || z->yuv;      // a converted 4:2:0 frame has alpha 255 everywhere
         if (!lazy_commit(layer, l, z, l.pal, width, height, 4)) { z->scale = false; z->opaque = false; z->stage = prev; lazy_reattach(l.pd[0], z); return 0; }
         if (l.gamma != WEED_GAMMA_SRGB) set_int(layer, WEED_LEAF_GAMMA_TYPE, WEED_GAMMA_SRGB);
         return 1;
@@ -1955,6 +2070,14 @@ int lives_gpu_set_deferred(int on) { return g_deferred.exchange(on ? 1 : 0); }
 void lives_gpu_deferred_stats(unsigned long long out[4]) {
   if (!out) return;
   out[0] = g_lz_recorded.load(); out[1] = g_lz_chain_launches.load(); out[2] = g_lz_chain_tracks.load(); out[3] = g_lz_staged.load();
+}
+// the same counters, then [4] YUV420P / YVU420P conversions recorded, [5] one-launch YUV chain launches (lgpu_chain_yuv420p) and [6] the tracks they carried,
+// [7] conversion pre-launches of the two-launch path (lgpu_yuv420p_to_rgb_batch); at most n entries are written
+void lives_gpu_deferred_stats_n(unsigned long long *out, int n) {
+  if (!out || n <= 0) return;
+  const unsigned long long v[8] = {g_lz_recorded.load(), g_lz_chain_launches.load(), g_lz_chain_tracks.load(), g_lz_staged.load(),
+                                   g_lz_yuv_recorded.load(), g_lz_yuv_launches.load(), g_lz_yuv_tracks.load(), g_lz_yuv_pre.load()};
+  for (int i = 0; i < n && i < 8; i++) out[i] = v[i];
 }
 // Run the pending programs of these layers now, on the calling thread's stream: programs of equal shape (the tracks of one plan step) share ONE launch of the
 // fused chain kernel.  The layers stay pinned, nothing is downloaded, the host does not wait.  What a host calls once per tick when the plan steps of its tracks

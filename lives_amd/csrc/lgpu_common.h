@@ -109,6 +109,15 @@ __device__ __forceinline__ uint32_t lut4(const uint8_t *l, uint32_t p) {
   return (uint32_t)l[p & 0xFF] | ((uint32_t)l[(p >> 8) & 0xFF] << 8) | ((uint32_t)l[(p >> 16) & 0xFF] << 16) | ((uint32_t)l[p >> 24] << 24);
 }
 __device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+// K2's per-pixel arithmetic on its paired tables (src/colourspace.c:3445-3554, xyuv2rgb :2351-2356), shared by the converter (yuv.hip, k_yuv420p_to_rgb_s) and the
+// 2:1 chain with a 4:2:0 source (pixbuf.hip, k_pb_half<.., YUV>) so that the two cannot drift apart.  Chroma (2a + b) / 3 on doubled sums:
+// (int)(s / 3. + .5) == (s + 1) / 3 == (s + 1) * 43691 >> 17 for s < 2^15
+__device__ __forceinline__ uint32_t yuv_third(uint32_t s1, uint32_t s2) { return __umul24(s1 + (s2 >> 1) + 1u, 43691u) >> 17; }
+// RGB_Y[y] + {R_Cr, G_Cr}[v] + {G_Cb, B_Cb}[u], >> 16, CLAMP0255
+__device__ __forceinline__ void yuv_rgb(uint32_t yy, uint32_t rcr, uint32_t gcr, uint32_t gcb, uint32_t bcb, uint32_t &r, uint32_t &g, uint32_t &b) {
+  const int sr = (int)(yy + rcr), sg = (int)(yy + gcb + gcr), sb = (int)(yy + bcb);
+  r = (uint32_t)min(max(sr >> 16, 0), 255); g = (uint32_t)min(max(sg >> 16, 0), 255); b = (uint32_t)min(max(sb >> 16, 0), 255);
+}
 // [1 4 6 4 1] on packed 16-bit lanes, a + e + 4 (b + d) + 6 c + k, without a 32-bit multiply: the operands of the vertical pass exceed 24 bits, so `6u * c` became
 // v_mul_lo_u32 (a quarter of the vector rate); ((b + c + d) << 2) + (c << 1) + (a + e + k) is two v_add3 and two v_lshl_add
 __device__ __forceinline__ uint32_t gauss5_taps(uint32_t a, uint32_t b, uint32_t c, uint32_t d, uint32_t e, uint32_t k = 0u) { return ((b + c + d) << 2) + (c << 1) + (a + e + k); }

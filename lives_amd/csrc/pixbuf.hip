@@ -260,6 +260,8 @@ __device__ __forceinline__ uint32_t pb_mad7(uint32_t a, uint32_t c) {
   asm("v_mad_u32_u24 %0, %1, 7, %2" : "=v"(d) : "v"(a), "v"(c));
   return d;
 }
+template <int HYPER, int ALIGNED, int NCH>
+__device__ __forceinline__ void pb_half_hsum(const uint32_t A[4], const uint32_t B[4], const uint32_t xe[4], uint32_t h[8]);
 // one source row of a lane: 4 pixels -> the two H columns of its 4 channels (h[c] = column 2k, h[4 + c] = column 2k + 1)
 // e (ALIGNED strips only, otherwise 0): lane 0 holds pixel P[4k-1] there, lane 63 pixel P[4k+4] (clamped into the row), every other lane 0 -- the two taps the
 // wave shifts cannot deliver.  SWAP: channel 0 is fed from byte 2 and channel 2 from byte 0 (the R <-> B conversion of the chain costs nothing: the three colours
@@ -300,8 +302,14 @@ __device__ __forceinline__ void pb_half_hrow(pb_u4 q, uint32_t h[8], uint32_t e 
     asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(xe[1]) : "v"(am), "v"(e));
     xe[3] = am;
   }
+  pb_half_hsum<HYPER, ALIGNED, OPAQUE ? 3 : 4>(A, B, xe, h);
+}
+
+// the horizontal taps of one source row on channel pairs already apart: A[c] = (pixel 4k, pixel 4k+1), B[c] = (4k+2, 4k+3) of channel c as 16-bit halves
+template <int HYPER, int ALIGNED, int NCH>
+__device__ __forceinline__ void pb_half_hsum(const uint32_t A[4], const uint32_t B[4], const uint32_t xe[4], uint32_t h[8]) {
 #pragma unroll
-  for (int c = 0; c < (OPAQUE ? 3 : 4); c++) {
+  for (int c = 0; c < NCH; c++) {
     if (HYPER) {
       // wave_shr:1 -- the left lane's (P[4k-2], P[4k-1]);  wave_shl:1 -- the right lane's (P[4k+4], P[4k+5]);  lanes 0 / 63 keep xe (0 in strips with feeder lanes)
       const uint32_t bl = ALIGNED ? (uint32_t)__builtin_amdgcn_update_dpp((int)xe[c], (int)B[c], 0x138, 0xF, 0xF, false) : (uint32_t)__builtin_amdgcn_mov_dpp((int)B[c], 0x138, 0xF, 0xF, true);
@@ -373,8 +381,22 @@ __device__ __forceinline__ void pb_half_colours(uint32_t v0, uint32_t v1, uint32
 // the descriptor's range and the hardware drops their store (no exec-mask branch per row).
 // CHAIN: 0 the scaler alone; 1 [R <-> B] -> scale -> chroma blend with layer 2 -> gamma LUT; 2 the same without a layer 2 (LGPU_INTERP_NOBLEND: a track that is
 // not blended with anything -- no layer-2 loads, no blend arithmetic)
-template <int CHAIN, int HYPER, int BLUR, int ALIGNED = 0, int SWAP = 0, int OPAQUE = 0>
-__global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTracks T, const Lut8 lut) {
+// YUV (lgpu_chain_yuv420p): the source is a planar 4:2:0 frame -- luma planes as PbTracks.src, chroma planes in PbYuvSrc -- converted in registers as K2 converts
+// it (yuv.hip, quirks K2-a..e), row pair by row pair, straight into the all-opaque scaler: no RGBA frame is ever written.  Every converted pixel has alpha 255, so
+// OPAQUE is exact.  SWAP then means "the converted frame is BGRA" (the output order with the chain's R <-> B swap folded in).
+struct PbYuvSrc {
+  const uint8_t *u[LGPU_CHAIN_MAX_TRACKS], *v[LGPU_CHAIN_MAX_TRACKS];
+  const int32_t *tables;         // device [5][256] RGB_Y R_Cr G_Cb G_Cr B_Cb (lgpu_conversion_tables of which_tables)
+  int us, vs;                    // chroma rowstrides
+  uint32_t usize, vsize;         // chroma plane bytes: every sample inside; K2's read one past the last row's end is clamped to the last byte
+  int clamped, lowq, fix_edges;  // CLAMP16_240 on the chroma index / pb_quality LOW / LGPU_YUV_FIX_EDGES
+};
+struct PbNoYuv {};
+template <int YUV> struct PbYuvArg { typedef PbNoYuv type; };
+template <> struct PbYuvArg<1> { typedef PbYuvSrc type; };
+
+template <int CHAIN, int HYPER, int BLUR, int ALIGNED = 0, int SWAP = 0, int OPAQUE = 0, int YUV = 0>
+__global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTracks T, const Lut8 lut, const typename PbYuvArg<YUV>::type Y = typename PbYuvArg<YUV>::type()) {
   // the gamma LUT and the blend's alpha scalers.  ONE copy per workgroup, but no workgroup barrier on the frame path: every wave writes the whole of both tables
   // itself (the same bytes) and reads them after its own writes have landed; a slower wave writing the same bytes again changes nothing
   __shared__ __attribute__((aligned(16))) uint8_t s_lut[256];
@@ -542,6 +564,189 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
   const int d = (band & 1) ? -1 : 1;
   const int ystart = d > 0 ? ylo : yhi, vstart = d > 0 ? vr0 : vr1;
   const int S0 = d > 0 ? 2 * ylo - 1 : 2 * yhi + 2;           // source rows are consumed in the order S0, S0 + d, S0 + 2 d, ...
+  if constexpr (YUV) {
+    static_assert(CHAIN && OPAQUE && !BLUR && !ALIGNED, "the 4:2:0 source: the chain's all-opaque form, no gaussian, strips with feeder lanes");
+    // K2's tables, paired as in k_yuv420p_to_rgb_s: RGB_Y, {R_Cr, G_Cr}[v], {G_Cb, B_Cb}[u] with CLAMP16_240 / the 0..255 clamp folded into the chroma index
+    __shared__ uint32_t s_ty[256];
+    __shared__ pb_u2 s_rg[256], s_gb[256];
+    // The source rows of output row y are 2y - 1 .. 2y + 2: K2's row pairs (2p - 1, 2p) for p = y and y + 1 (pair 0 is row 0 twice, pair dh the trailing row H - 1
+    // twice -- the scaler's clamp).  A lane's quad kc covers chroma columns 2kc, 2kc + 1; every chroma row it reads is ONE 4-byte window, columns 2kc - 1 .. 2kc + 2.
+    const __amdgpu_buffer_rsrc_t r_u = srd(Y.u[track], Y.usize), r_v = srd(Y.v[track], Y.vsize);
+    const int dh = A.dh;
+    const uint32_t c_off = 2u * (uint32_t)kc - (kc ? 1u : 0u);      // kc == 0: the window starts at column 0 and column -1 is filled in afterwards
+    struct Raw { uint32_t ya, yb, u0, v0, u1, v1, e0, e1; };
+    auto win = [&](const __amdgpu_buffer_rsrc_t &r, int row, int stride, uint32_t size) -> uint32_t {
+      const uint32_t o = (uint32_t)__builtin_amdgcn_readfirstlane(row * stride);
+      uint32_t w = 0u;
+      if (o + c_off + 4u <= size) w = __builtin_amdgcn_raw_buffer_load_b32(r, (int)c_off, (int)o, 0);
+      else {        // the plane's last bytes (K2 reads one sample past the last row's end and clamps that to the last byte; a buffer load would return 0)
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const uint32_t q = min(o + c_off + (uint32_t)i, size - 1u);
+          w |= (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r, (int)q, 0, 0) << (8 * i);
+        }
+      }
+      return kc ? w : (w << 8) | (w & 0xFFu);                     // column -1 := column 0
+    };
+    auto yrow = [&](int row) -> uint32_t { return __builtin_amdgcn_raw_buffer_load_b32(r_src, (int)(4u * (uint32_t)kc), __builtin_amdgcn_readfirstlane(row * A.irow), 0); };
+    auto yload = [&](int p) -> Raw {
+      Raw w = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+      p = __builtin_amdgcn_readfirstlane(p);
+      if (p > 0 && p < dh) {
+        w.ya = yrow(2 * p - 1); w.yb = yrow(2 * p);
+        w.u0 = win(r_u, p - 1, Y.us, Y.usize); w.v0 = win(r_v, p - 1, Y.vs, Y.vsize); w.u1 = win(r_u, p, Y.us, Y.usize); w.v1 = win(r_v, p, Y.vs, Y.vsize);
+        w.e0 = __builtin_amdgcn_raw_buffer_load_b8(r_v, 0, __builtin_amdgcn_readfirstlane(p * Y.vs), 0);      // V(r + 1, 0): the reference's frozen "last V"
+      } else if (p == 0) {
+        w.ya = yrow(0); w.u0 = win(r_u, 0, Y.us, Y.usize); w.v0 = win(r_v, 0, Y.vs, Y.vsize);
+      } else {
+        const int r = dh - 1;
+        w.ya = yrow(A.sh - 1); w.u1 = win(r_u, r, Y.us, Y.usize); w.v1 = win(r_v, r, Y.vs, Y.vsize);
+        if (!Y.fix_edges) {       // the 1-thread reference's last row: the left pixel's luma from row 0, its chroma walk from chroma row 0 seeded with row r's column 0
+          w.yb = yrow(0); w.u0 = win(r_u, 0, Y.us, Y.usize); w.v0 = win(r_v, 0, Y.vs, Y.vsize);
+          w.e0 = __builtin_amdgcn_raw_buffer_load_b8(r_u, 0, __builtin_amdgcn_readfirstlane(r * Y.us), 0);
+          w.e1 = __builtin_amdgcn_raw_buffer_load_b8(r_v, 0, __builtin_amdgcn_readfirstlane(r * Y.vs), 0);
+        }
+      }
+      return w;
+    };
+    auto at = [](uint32_t w, int j) -> uint32_t { return (w >> (8 * (j + 1))) & 0xFFu; };      // chroma column 2kc + j, j = -1 .. 2
+    auto lu = [](uint32_t w, int i) -> uint32_t { return (w >> (8 * i)) & 0xFFu; };           // luma column 4kc + i
+    auto bl = [&](uint32_t s1, uint32_t s2) -> uint32_t { return Y.lowq ? s1 >> 1 : yuv_third(s1, s2); };
+    auto rclamp = [&](uint32_t w) -> uint32_t { return kc == kmax ? (w & 0x00FFFFFFu) | ((w << 8) & 0xFF000000u) : w; };      // column hw := hw - 1
+    auto px = [&](uint32_t y, uint32_t iu, uint32_t iv, uint32_t *c) {
+      const pb_u2 rg = s_rg[iv], gb = s_gb[iu];
+      uint32_t r, g, b;
+      yuv_rgb(s_ty[y], rg.x, rg.y, gb.x, gb.y, r, g, b);
+      c[0] = SWAP ? b : r; c[1] = g; c[2] = SWAP ? r : b;
+    };
+    // pair p -> the H columns of its first consumed row (hf) and its second (hs_): top first walking down, bottom first walking up
+    const uint32_t xe0[4] = {0u, 0u, 0u, 0u};
+    // The chroma walk below is yuv.hip's yuv420_cell() (and k_yuv420p_to_rgb_s's fast cell) on a 4-byte window: row 0, the row pair with its (2a + b) / 3 blend,
+    // the left pixel's U rebuilt from the first row, the frozen V(r + 1, 0), the read one past the last pair's end, the 1-thread trailing row.  A change to one of
+    // those quirks there must be made here too; tests/test_chain_yuv.py holds both against the oracle's K2 bit for bit.
+    auto cvt = [&](Raw w, int p, uint32_t hf[8], uint32_t hs_[8]) __attribute__((always_inline)) {
+      uint32_t t[4][3], b[4][3];
+      p = __builtin_amdgcn_readfirstlane(p);
+      if (p > 0 && p < dh) {
+        // rows (2p - 1, 2p), chroma rows r = p - 1 and r + 1 (:3445-3554; yuv.hip yuv420_cell)
+        if (!kc) w.v1 = (w.v1 & ~0xFFu) | (w.v0 & 0xFFu);           // left pixel of column 0: V(r, 0) in place of V(r + 1, -1)
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+          const uint32_t u_rk = at(w.u0, j), v_rk = at(w.v0, j), v_r1k = at(w.v1, j);
+          const uint32_t su = u_rk + at(w.u0, j - 1), iul = bl(su, su);      // the left pixel's U: second row rebuilt from the first (:3461)
+          const uint32_t s1v = v_rk + at(w.v1, j - 1), s2v = v_r1k + w.e0;
+          const uint32_t s1u = u_rk + at(w.u0, j + 1), s2u = at(w.u1, j) + at(w.u1, j + 1);
+          const uint32_t s1w = v_rk + at(w.v0, j + 1), s2w = v_r1k + at(w.v1, j + 1);
+          px(lu(w.ya, 2 * j), iul, bl(s1v, s2v), t[2 * j]);
+          px(lu(w.yb, 2 * j), iul, bl(s2v, s1v), b[2 * j]);
+          px(lu(w.ya, 2 * j + 1), bl(s1u, s2u), bl(s1w, s2w), t[2 * j + 1]);
+          px(lu(w.yb, 2 * j + 1), bl(s2u, s1u), bl(s2w, s1w), b[2 * j + 1]);
+        }
+      } else {
+        if (p == 0) {
+          // row 0 (:3399-3443): neighbours clamped into the row
+          const uint32_t u0 = rclamp(w.u0), v0 = rclamp(w.v0);
+#pragma unroll
+          for (int j = 0; j < 2; j++) {
+            px(lu(w.ya, 2 * j), (at(u0, j) + at(u0, j - 1)) >> 1, (at(v0, j) + at(v0, j - 1)) >> 1, t[2 * j]);
+            px(lu(w.ya, 2 * j + 1), (at(u0, j) + at(u0, j + 1)) >> 1, (at(v0, j) + at(v0, j + 1)) >> 1, t[2 * j + 1]);
+          }
+        } else {
+          // the trailing row H - 1 (:3556-3592)
+          const uint32_t u1 = rclamp(w.u1), v1 = rclamp(w.v1);
+#pragma unroll
+          for (int j = 0; j < 2; j++) {
+            if (Y.fix_edges) px(lu(w.ya, 2 * j), (at(u1, j) + at(u1, j - 1)) >> 1, (at(v1, j) + at(v1, j - 1)) >> 1, t[2 * j]);
+            else {
+              const bool c0 = !kc && !j, c2 = kc != 0;                 // chroma column 0 / >= 2
+              const uint32_t tu = c0 ? w.e0 : at(w.u0, j), tv = c0 ? w.e1 : at(w.v0, j);
+              const uint32_t lu_ = c2 ? at(w.u0, j - 1) : w.e0, lv_ = c2 ? at(w.v0, j - 1) : w.e1;
+              px(lu(w.yb, 2 * j), (tu + lu_) >> 1, (tv + lv_) >> 1, t[2 * j]);
+            }
+            px(lu(w.ya, 2 * j + 1), (at(u1, j) + at(u1, j + 1)) >> 1, (at(v1, j) + at(v1, j + 1)) >> 1, t[2 * j + 1]);
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) { b[i][0] = t[i][0]; b[i][1] = t[i][1]; b[i][2] = t[i][2]; }
+      }
+      uint32_t At[4], Bt[4], Ab[4], Bb[4];
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        At[c] = t[0][c] | (t[1][c] << 16); Bt[c] = t[2][c] | (t[3][c] << 16);
+        Ab[c] = b[0][c] | (b[1][c] << 16); Bb[c] = b[2][c] | (b[3][c] << 16);
+      }
+      At[3] = Bt[3] = Ab[3] = Bb[3] = 0u;
+      if (edge_strip) {
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+          if (k < 0) {        // left of the frame: pixel 0 repeated
+            At[c] = Bt[c] = __builtin_amdgcn_perm(At[c], At[c], 0x01000100u); Ab[c] = Bb[c] = __builtin_amdgcn_perm(Ab[c], Ab[c], 0x01000100u);
+          }
+          if (k > kmax) {     // right of the frame: the last pixel repeated
+            At[c] = Bt[c] = __builtin_amdgcn_perm(Bt[c], Bt[c], 0x03020302u); Ab[c] = Bb[c] = __builtin_amdgcn_perm(Bb[c], Bb[c], 0x03020302u);
+          }
+        }
+      }
+      if (d > 0) { pb_half_hsum<HYPER, 0, 3>(At, Bt, xe0, hf); pb_half_hsum<HYPER, 0, 3>(Ab, Bb, xe0, hs_); }
+      else { pb_half_hsum<HYPER, 0, 3>(Ab, Bb, xe0, hf); pb_half_hsum<HYPER, 0, 3>(At, Bt, xe0, hs_); }
+    };
+
+    const int p0 = d > 0 ? ylo : yhi + 1;                     // the pair of output row ystart's first two source rows; step r adds pair p0 + d (r + 1)
+    Raw ca = yload(p0), cb = yload(p0 + d), na = cb;
+    pb_u2 l2, nl2;
+    l2.x = 0; l2.y = 0; nl2 = l2;
+    if (CHAIN == 1) l2 = load_l2(d > 0 ? y0 : y0 + rows - 1);
+    {       // this wave's copy of the tables, requested while the first rows are in flight (as the LUT and the blend's scalers; no workgroup barrier)
+      const int clo = Y.clamped ? 16 : 0, chi = Y.clamped ? 240 : 255;
+      uint32_t ty[4], ra[4], rb[4], ga[4], gb[4];
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int e = lane + 64 * i, ec = e < clo ? clo : e > chi ? chi : e;
+        ty[i] = (uint32_t)Y.tables[e]; ra[i] = (uint32_t)Y.tables[256 + ec]; rb[i] = (uint32_t)Y.tables[768 + ec]; ga[i] = (uint32_t)Y.tables[512 + ec]; gb[i] = (uint32_t)Y.tables[1024 + ec];
+      }
+      reinterpret_cast<uint32_t *>(s_lut)[lane] = lut.w[lane];
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const uint2 kk = A.kscale[lane + 64 * i];
+        pb_u2 kv; kv.x = kk.x; kv.y = kk.y;
+        s_k[lane + 64 * i] = kv;
+        pb_u2 q; q.x = ra[i]; q.y = rb[i];
+        pb_u2 s; s.x = ga[i]; s.y = gb[i];
+        s_ty[lane + 64 * i] = ty[i]; s_rg[lane + 64 * i] = q; s_gb[lane + 64 * i] = s;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    }
+    uint32_t carry[8], hr[8], hs[8];
+    cvt(ca, p0, hr, hs);
+#pragma unroll
+    for (int i = 0; i < 8; i++) if ((i & 3) != 3) carry[i] = HYPER ? pb_mad7(hs[i], hr[i]) : hs[i];
+    auto one = [&](int r, Raw &cur, pb_u2 &cl2, Raw &nxt, pb_u2 &xl2) __attribute__((always_inline)) {
+      const int yy = d > 0 ? ystart + r : ystart - r;
+      if (r + 1 < rows) {
+        nxt = yload(p0 + d * (r + 2));
+        if (CHAIN == 1) xl2 = load_l2(yy + d);
+      }
+      cvt(cur, p0 + d * (r + 1), hr, hs);
+      uint32_t v[8];
+#pragma unroll
+      for (int i = 0; i < 8; i++) {
+        if ((i & 3) == 3) { v[i] = 0u; continue; }
+        if (HYPER) { v[i] = pb_mad7(hr[i], carry[i] + hs[i]); carry[i] = pb_mad7(hs[i], hr[i]); }
+        else { v[i] = carry[i] + hr[i]; carry[i] = hs[i]; }
+      }
+      constexpr int sh_ = HYPER ? 8 : 2;
+      store_row(yy, finish(v[0] >> sh_, v[1] >> sh_, v[2] >> sh_, 0xFF000000u, cl2.x), finish(v[4] >> sh_, v[5] >> sh_, v[6] >> sh_, 0xFF000000u, cl2.y));
+    };
+    int r = 0;
+    for (; r + 1 < rows; r += 2) {
+      one(r, cb, l2, na, nl2);
+      one(r + 1, na, nl2, cb, l2);
+    }
+    if (r < rows) one(r, cb, l2, na, nl2);
+    return;
+  }
   // carry[i] = (outer tap) * H[first row] + (inner tap) * H[second row] of a scaled row: the half that is known before its last two source rows arrive
   uint32_t carry[8], hr[8], hs[8];
   pb_u4 q0 = load_row(S0), q1 = load_row(S0 + d), qa = load_row(S0 + 2 * d), qb = load_row(S0 + 3 * d);
@@ -1720,13 +1925,13 @@ static void pb_half_bands(PbHalfArgs *a, int bands) {
   a->bands = bands; a->th = a->dh / bands; a->rem = a->dh - a->th * bands;
 }
 
-static void pb_half_geometry(PbHalfArgs *a, int ntracks, int blur = 0, int opaque = 0) {
+static void pb_half_geometry(PbHalfArgs *a, int ntracks, int blur = 0, int opaque = 0, int yuv = 0) {
   // strips of 64 storing lanes on 128-byte lines (k_pb_half<.., ALIGNED>; the two outer taps of a strip from one extra 4-byte load in lanes 0 and 63, which ride into
   // the lane exchange for free).  Round 3 measured them 3 % lighter on traffic and 13 % heavier on arithmetic: a draw.  With round 4's arithmetic (buffer addressing,
   // five-operation reciprocal, no register moves, the edge taps through DPP's kept destination) they win clearly: 16 tracks 166.5 -> 155.0 us, 8 tracks 85.7 -> 81.1,
   // one frame equal (profiles/r04/al_ab1.txt, interleaved).  LGPU_PBH_ALIGNED=0 keeps the feeder-lane strips.
-  a->aligned = blur ? 0 : 1;
-  if (!blur && tune(TUNE_PBH_ALIGNED) >= 0) a->aligned = tune(TUNE_PBH_ALIGNED) ? 1 : 0;
+  a->aligned = (blur || yuv) ? 0 : 1;           // (the 4:2:0 source: the all-opaque arithmetic exists for the strips with feeder lanes)
+  if (!blur && !yuv && tune(TUNE_PBH_ALIGNED) >= 0) a->aligned = tune(TUNE_PBH_ALIGNED) ? 1 : 0;
   a->strips = (int)cdiv((unsigned)a->dw, blur ? 120 : a->aligned ? 128 : 124);
   a->cgroups = (a->strips + 3) / 4;
   a->ntracks = ntracks;
@@ -2287,4 +2492,96 @@ extern "C" int lgpu_chain_amounts(const lgpu_chain_params *params, const lgpu_ca
   if (canvas) return chain_canvas_impl(&p0, canvas, tracks, ntracks, stream, amounts, true);
   if ((rc = lgpu_chain_check(&p0, tracks, ntracks))) return rc;
   return pb_chain(&p0, nullptr, tracks, ntracks, (hipStream_t)stream, amounts);
+}
+
+// lgpu_chain_yuv420p: the 2:1 chain that starts at decoded 4:2:0 frames -- K2's conversion in registers -> the exact 2:1 scaler (all-opaque arithmetic) [-> letterbox]
+// [-> chroma blend with layer 2] -> gamma LUT, one launch for every track, no RGBA intermediate.  Every argument is checked before anything is enqueued.
+extern "C" int lgpu_chain_yuv420p(const lgpu_chain_params *pr, const lgpu_yuv_source *ys, const lgpu_canvas *cv, const lgpu_chain_yuv_track *tracks, int ntracks,
+                                  const uint8_t *amounts, void *stream) {
+  int rc = ensure_init();
+  if (rc) return rc;
+  LGPU_REQUIRE(pr && ys && tracks && ntracks > 0 && ntracks <= LGPU_CHAIN_MAX_TRACKS, "params, source and 1..64 tracks required");
+  LGPU_REQUIRE(pr->interp & LGPU_INTERP_PIXBUF, "lgpu_chain_yuv420p serves the gdk-pixbuf arithmetic (LGPU_INTERP_PIXBUF)");
+  const bool noblend = (pr->interp & LGPU_INTERP_NOBLEND) != 0;
+  LGPU_REQUIRE(amounts || noblend, "null amounts");
+  LGPU_REQUIRE(pr->sw >= 2 && !(pr->sw & 1) && pr->sh >= 1 && pr->dw > 0 && pr->dh > 0, "empty geometry or an odd 4:2:0 width");
+  LGPU_REQUIRE(ys->out_order == 0 || ys->out_order == 1, "out_order is 0 (RGBA) or 1 (BGRA)");
+  LGPU_REQUIRE(ys->which_tables >= 0 && ys->which_tables <= 3, "which_tables is 0..3");
+  LGPU_REQUIRE(ys->pb_quality >= 1 && ys->pb_quality <= 3, "pb_quality is 1 (LOW), 2 (MED) or 3 (HIGH)");
+  LGPU_REQUIRE(!(ys->flags & ~LGPU_YUV_FIX_EDGES), "unknown flags");
+  const int hw = pr->sw >> 1, hh = (pr->sh + 1) >> 1, lys = ys->istrides[0], us = ys->istrides[1], vs = ys->istrides[2];
+  LGPU_REQUIRE(lys >= pr->sw && us >= hw && vs >= hw, "plane rowstride smaller than a row");
+  LGPU_REQUIRE(ys->u_size >= (long)(hh - 1) * us + hw && ys->v_size >= (long)(hh - 1) * vs + hw, "chroma plane smaller than its (sw / 2) x (sh / 2) samples");
+  const int cw = cv ? cv->nwidth : pr->dw, ch = cv ? cv->nheight : pr->dh;
+  if (cv)
+    LGPU_REQUIRE(cv->nwidth >= pr->dw && cv->nheight >= pr->dh && cv->offs_x >= 0 && cv->offs_y >= 0 && cv->offs_x + pr->dw <= cv->nwidth &&
+                 cv->offs_y + pr->dh <= cv->nheight, "the scaled frame must lie inside the canvas");
+  LGPU_REQUIRE(pr->orow >= cw * 4 && (noblend || pr->irow2 >= cw * 4), "rowstride smaller than a row");
+  LGPU_REQUIRE(((pr->orow | (noblend ? 0 : pr->irow2)) & 3) == 0, "rowstrides must be multiples of 4");
+  uintptr_t db = (uintptr_t)pr->orow | (uintptr_t)(noblend ? 0 : pr->irow2);
+  for (int i = 0; i < ntracks; i++) {
+    const lgpu_chain_yuv_track &t = tracks[i];
+    LGPU_REQUIRE(t.y_d && t.u_d && t.v_d && t.dst_d && (noblend || t.layer2_d), "null track pointer");
+    LGPU_REQUIRE((((uintptr_t)t.dst_d | (uintptr_t)(noblend ? nullptr : t.layer2_d)) & 3) == 0, "destination and layer 2 must be 4-byte aligned");
+    LGPU_REQUIRE((const uint8_t *)t.dst_d != t.y_d && (const uint8_t *)t.dst_d != t.u_d && (const uint8_t *)t.dst_d != t.v_d, "the chain cannot run in place");
+    db |= (uintptr_t)t.dst_d | (uintptr_t)(noblend ? nullptr : t.layer2_d);
+  }
+  // the one-launch form; anything else is refused, never run some other way
+  if (pr->do_blur) { set_error("lgpu_chain_yuv420p: the gaussian is not offered with a 4:2:0 source"); return LGPU_E_UNSUPPORTED; }
+  const int interp = pr->interp & 0xFF;
+  if ((interp != 2 && interp != 3) || pr->sw != 2 * pr->dw || pr->sh != 2 * pr->dh || (pr->sw & 3) || (cv && (cv->offs_x & 1)) || (db & 7)) {
+    set_error("lgpu_chain_yuv420p: one launch serves the exact 2:1 reduction (HYPER / BILINEAR, sw %% 4 == 0, sh even, even canvas offs_x, 8-byte aligned destination)");
+    return LGPU_E_UNSUPPORTED;
+  }
+  const long long lim = 1ll << 31;
+  if ((long long)pr->sh * lys >= lim || ys->u_size >= lim || ys->v_size >= lim || (long long)ch * pr->orow >= lim || (!noblend && (long long)ch * pr->irow2 >= lim)) {
+    set_error("lgpu_chain_yuv420p: planes of 2 GiB or more");
+    return LGPU_E_UNSUPPORTED;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  PbPin pin;
+  if ((rc = pb_table(interp, pr->sw, pr->sh, pr->dw, pr->dh, st, &pin))) return rc;
+  PbHalfArgs a;
+  if (!pb_half_ok(pin.t, interp, pr->sw, pr->sh, pr->dw, pr->dh, 0, db, &a.hyper, &a.ashift)) {
+    set_error("lgpu_chain_yuv420p: the scaler's table is not the exact 2:1 outer product");
+    return LGPU_E_UNSUPPORTED;
+  }
+  if ((rc = pb_opaque_check())) return rc;
+  if ((rc = get_kscale(&a.kscale))) return rc;
+  a.sw = pr->sw; a.sh = pr->sh; a.irow = lys; a.dw = pr->dw; a.dh = pr->dh; a.orow = pr->orow;
+  a.swap_rb = (ys->out_order ^ (pr->swap_rb ? 1 : 0)) & 1; a.blend = 1; a.irow2 = noblend ? pr->orow : pr->irow2; a.use_lut = pr->use_lut ? 1 : 0;
+  a.bf = 0; a.bf_d = nullptr; a.bf_tracks = 1; a.nt_out = 1;
+  a.row_major = -1;
+  a.bgroup = 0;
+  pb_half_geometry(&a, ntracks, 0, 0, 1);
+  a.row_major = ((long long)a.cgroups * a.bands * ntracks >= (long long)device_cus() * 8 + 1) ? 2 : 1;
+  a.bgroup = (a.bands % 8 == 0) ? a.bands / 8 : 1;
+  a.cw = a.ch = a.ox = a.oy = 0; a.bar_blocks = 0;
+  if (cv) { a.cw = cv->nwidth; a.ch = cv->nheight; a.ox = cv->offs_x; a.oy = cv->offs_y; a.bar_blocks = (int)cdiv((unsigned)(a.cw * a.ch - a.dw * a.dh), 1024u); }
+  a.main_blocks = (int)pb_half_grid(a);
+  a.bar_first = (a.bar_blocks * ntracks + 7) & ~7;
+  PbTracks T;
+  PbYuvSrc Y;
+  for (int i = 0; i < ntracks; i++) {
+    T.src[i] = tracks[i].y_d; T.l2[i] = noblend ? tracks[i].dst_d : tracks[i].layer2_d; T.dst[i] = tracks[i].dst_d; T.bf[i] = amounts ? amounts[i] : 0;
+    Y.u[i] = tracks[i].u_d; Y.v[i] = tracks[i].v_d;
+  }
+  Y.tables = device_tables()->yuv2rgb[ys->which_tables & 3];
+  Y.us = us; Y.vs = vs; Y.usize = (uint32_t)ys->u_size; Y.vsize = (uint32_t)ys->v_size;
+  Y.clamped = !(ys->which_tables & 1); Y.lowq = ys->pb_quality == 1; Y.fix_edges = (ys->flags & LGPU_YUV_FIX_EDGES) ? 1 : 0;
+  const Lut8 l = pack_lut(pr->use_lut ? pr->lut8 : nullptr);
+  const dim3 grid((unsigned)(a.main_blocks + a.bar_first));
+  // No dynamic LDS: pb_chain_half's cap of five workgroups per CU (profiles/r04/occupancy_sweep.txt) was measured for the memory-bound RGBA kernel; this one is
+  // bound by its arithmetic and its 85-93 registers already hold it to five waves per SIMD.  The cap has not been measured for it.
+#define PBY_LAUNCH(CH, HY, SW) hipLaunchKernelGGL((k_pb_half<CH, HY, 0, 0, SW, 1, 1>), grid, dim3(256), 0, st, a, T, l, Y)
+  if (noblend) {
+    if (a.hyper) { if (a.swap_rb) PBY_LAUNCH(2, 1, 1); else PBY_LAUNCH(2, 1, 0); }
+    else { if (a.swap_rb) PBY_LAUNCH(2, 0, 1); else PBY_LAUNCH(2, 0, 0); }
+  } else {
+    if (a.hyper) { if (a.swap_rb) PBY_LAUNCH(1, 1, 1); else PBY_LAUNCH(1, 1, 0); }
+    else { if (a.swap_rb) PBY_LAUNCH(1, 0, 1); else PBY_LAUNCH(1, 0, 0); }
+  }
+#undef PBY_LAUNCH
+  LGPU_CHECK_LAUNCH();
+  return LGPU_OK;
 }

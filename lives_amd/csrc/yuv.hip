@@ -84,6 +84,7 @@ struct YuvCtx {
   }
 };
 
+// (the same walk runs in registers in pixbuf.hip's k_pb_half<.., YUV>, the 2:1 chain from a 4:2:0 source: a quirk changed here must change there too)
 // one (unit, chroma column k) cell of the 4:2:0 walk: 2 pixels of row 0, a 2 x 2 quad of a row pair, or 2 pixels of the trailing row
 // units: 0 = row 0; p >= 1 = rows (2p-1, 2p) while 2p <= H-1; then (even H) the trailing row H-1
 __device__ __forceinline__ void yuv420_cell(const YuvArgs &a, const YuvCtx &c, int unit, int k, int hw, int npairs) {
@@ -289,13 +290,13 @@ __global__ __launch_bounds__(1024) void k_yuv420p_to_rgb_s(YuvArgs a, Lut8 lut, 
   auto at = [](win_t w, int j) -> uint32_t { return (uint32_t)(w >> (8 * (j + 1))) & 0xFFu; };
   auto yat = [](ywin_t w, int j) -> uint32_t { return (uint32_t)(w >> (8 * j)) & 0xFFu; };
   // (2a + b) / 3 on doubled sums, (int)(s / 3. + .5) == (s + 1) / 3 == (s + 1) * 43691 >> 17 for s < 2^15, as the LDS address of the 8-byte table entry
-  auto blend = [&](uint32_t s1, uint32_t s2, uint32_t base) -> uint32_t { return ((__umul24(s1 + (s2 >> 1) + 1u, 43691u) >> 17) << 3) + base; };
+  auto blend = [&](uint32_t s1, uint32_t s2, uint32_t base) -> uint32_t { return (yuv_third(s1, s2) << 3) + base; };
   const uint32_t bu = sbase + kYsOffGB, bv = sbase + kYsOffRG;
   auto pixel = [&](uint32_t yv, uint32_t ua, uint32_t va) -> uint32_t {
     const uint32_t yy = *(lds_u32)(uintptr_t)(sbase + kYsOffTy + (yv << 2));
     const u32x2v rg = *(lds_u64)(uintptr_t)va, gb = *(lds_u64)(uintptr_t)ua;
-    const int sr = (int)(yy + rg.x), sg = (int)(yy + gb.x + rg.y), sb = (int)(yy + gb.y);
-    uint32_t r_ = (uint32_t)min(max(sr >> 16, 0), 255), g_ = (uint32_t)min(max(sg >> 16, 0), 255), b_ = (uint32_t)min(max(sb >> 16, 0), 255);
+    uint32_t r_, g_, b_;
+    yuv_rgb(yy, rg.x, rg.y, gb.x, gb.y, r_, g_, b_);
     if (LUT) {
       r_ = *(lds_u8)(uintptr_t)(sbase + kYsOffLut + r_); g_ = *(lds_u8)(uintptr_t)(sbase + kYsOffLut + g_); b_ = *(lds_u8)(uintptr_t)(sbase + kYsOffLut + b_);
     }

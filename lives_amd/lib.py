@@ -36,6 +36,16 @@ class YuvFrame(ctypes.Structure):
     _fields_ = [("y_d", vp), ("u_d", vp), ("v_d", vp), ("dst_d", vp)]
 
 
+class ChainYuvTrack(ctypes.Structure):
+    """lgpu_chain_yuv_track"""
+    _fields_ = [("y_d", vp), ("u_d", vp), ("v_d", vp), ("layer2_d", vp), ("dst_d", vp)]
+
+
+class YuvSource(ctypes.Structure):
+    """lgpu_yuv_source"""
+    _fields_ = [("istrides", ci * 3), ("u_size", cl), ("v_size", cl), ("out_order", ci), ("which_tables", ci), ("pb_quality", ci), ("flags", ci)]
+
+
 class CompLayer(ctypes.Structure):
     """lgpu_comp_layer (include/lives_gpu.h)"""
     _fields_ = [("src_d", ctypes.c_void_p), ("irow", ctypes.c_int), ("width", ctypes.c_int), ("height", ctypes.c_int),
@@ -140,6 +150,7 @@ PROTOTYPES = {
     "lgpu_rgb_to_yuv_batch": [vp, ci, ci, ci, ci, ci, vp, vp, ci, ci, ci, ci, vp],
     "lgpu_yuv_to_rgb_batch": [vp, vp, ci, ci, ci, ci, vp, ci, ci, ci, ci, ci, vp],
     "lgpu_chain_amounts": [vp, vp, vp, ci, vp, vp],
+    "lgpu_chain_yuv420p": [vp, vp, vp, vp, ci, vp, vp],
     "lgpu_pixbuf_scale_check": [ci, ci, ci, ci, ci, ci, vp],
     "lgpu_pixbuf_scale_batch": [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp],
     "lgpu_fx_batch": [ctypes.POINTER(FxParams), ctypes.POINTER(FxFrame), ci, vp],

@@ -392,6 +392,35 @@ def chain_amounts(params, tracks, amounts, canvas=None):
     lib.call("lgpu_chain_amounts", ctypes.byref(params), ctypes.byref(cv) if cv is not None else None, tracks, len(tracks), am, stream_ptr())
 
 
+def chain_yuv_tracks(ys, us, vs, layer2s, dsts):
+    """lgpu_chain_yuv_track[]: the planes of each track's 4:2:0 source (pass u / v swapped for YVU420P), layer 2 (None: LGPU_INTERP_NOBLEND) and destination"""
+    n = len(ys)
+    arr = (lib.ChainYuvTrack * n)()
+    for i in range(n):
+        arr[i].y_d, arr[i].u_d, arr[i].v_d = ys[i].data_ptr(), us[i].data_ptr(), vs[i].data_ptr()
+        arr[i].layer2_d, arr[i].dst_d = (layer2s[i].data_ptr() if layer2s is not None else None), dsts[i].data_ptr()
+    return arr
+
+
+def yuv_source(istrides, u_size, v_size, out_order=0, which_tables=0, pb_quality=2, flags=0):
+    """lgpu_yuv_source"""
+    s = lib.YuvSource()
+    s.istrides[0], s.istrides[1], s.istrides[2] = istrides
+    s.u_size, s.v_size, s.out_order, s.which_tables, s.pb_quality, s.flags = u_size, v_size, out_order, which_tables, pb_quality, flags
+    return s
+
+
+def chain_yuv420p(params, src, tracks, amounts, canvas=None, check=True):
+    """lgpu_chain_yuv420p: the chain of lgpu_chain_amounts starting at 4:2:0 frames, one launch; canvas = (nwidth, nheight, offs_x, offs_y) or None.
+    check=False returns the library's code instead of raising (tests of the refusals)"""
+    am = (ctypes.c_uint8 * len(tracks))(*[int(a) & 0xFF for a in amounts]) if amounts is not None else None      # None: with LGPU_INTERP_NOBLEND (0x400) in params.interp
+    cv = lib.Canvas(*canvas) if canvas is not None else None
+    args = (ctypes.byref(params), ctypes.byref(src), ctypes.byref(cv) if cv is not None else None, tracks, len(tracks), am, stream_ptr())
+    if not check:
+        return lib.load().lgpu_chain_yuv420p(*args)
+    return lib.call("lgpu_chain_yuv420p", *args)
+
+
 def stream_probe(params, tracks, reps):
     """lgpu_debug_stream_probe: the chain's algorithmic bytes as a bare stream on the same frames, ms for `reps` launches (destinations left dirty)"""
     ms = ctypes.c_float()
