@@ -1358,10 +1358,9 @@ __global__ __launch_bounds__((CW + 2) * 64, (CW + 2) / 2) void k_sep2p(SepArgs a
     t.set(a, wk);
     gx = a.hpos[t.tx0]; gy = a.vpos[t.ty0];
   };
-  auto issue = [&](int wk, int slot, int gx, int gy) {
+  auto issue_window = [&](int wk, int slot, int gx, int gy) {
     S2pTile t;
     t.set(a, wk);
-    const int tw = min(kTileW, a.dw - t.tx0), thh = min(a.th, a.dh - t.ty0);
     const int sx0a = gx & ~3, sy0 = gy & ~1;
     uint8_t *win = smem + slot * L.win;
     const uint8_t *src = trk.src[t.track];
@@ -1375,6 +1374,13 @@ __global__ __launch_bounds__((CW + 2) * 64, (CW + 2) / 2) void k_sep2p(SepArgs a
         if (ch >= (uint32_t)cpr) { ch -= (uint32_t)cpr; off += dwrap; }
       }
     } else s2p_issue_border(a.sw, a.sh, a.irow, a.swt, src, sx0a, sy0, lane, win, nreq, nchunks, mcpr);
+    sx0a_f = sx0a;
+  };
+  // a tile's tables go to their slot only once the compute waves are done with the tile two before it: its vertical pass reads them after B
+  auto issue_tables = [&](int wk, int slot) {
+    S2pTile t;
+    t.set(a, wk);
+    const int tw = min(kTileW, a.dw - t.tx0), thh = min(a.th, a.dh - t.ty0);
     const int ox = t.tx0 + (lane < tw ? lane : tw - 1);
     uint8_t *hc = smem + L.hc + slot * L.hcslot, *vc = smem + L.vc + slot * L.vcslot;
     __builtin_amdgcn_global_load_lds((h8s_gptr)(a.hpos + ox), (h8s_lptr)hc, 4, 0, 0);
@@ -1390,7 +1396,6 @@ __global__ __launch_bounds__((CW + 2) * 64, (CW + 2) / 2) void k_sep2p(SepArgs a
         if (i < nvc) __builtin_amdgcn_global_load_lds((h8s_gptr)g, (h8s_lptr)(vc + q * 256), 4, 0, 0);
       }
     }
-    sx0a_f = sx0a;
   };
   auto land = [&](int slot) {                                    // my window in flight has to be complete before the barrier that publishes it
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1410,17 +1415,21 @@ __global__ __launch_bounds__((CW + 2) * 64, (CW + 2) / 2) void k_sep2p(SepArgs a
   int gx = 0, gy = 0;
   if (first < wend) {
     geom(first, gx, gy);
-    issue(first, m, gx, gy);
+    issue_window(first, m, gx, gy);
+    issue_tables(first, m);
     if (first + 2 * wstride < wend) geom(first + 2 * wstride, gx, gy);
   }
   if (m == 0) land(0);
   int i = 0;
   for (; work < wend; work += wstride, i++) {
     H8S_BARRIER();                                                                   // A(i)
-    if (((i + 1) & 1) == m && work + wstride < wend) land((i + 1) & 1);
+    if (((i + 1) & 1) == m && work + wstride < wend) {
+      if (i >= 1) issue_tables(work + wstride, (i + 1) & 1);      // the slot held tile i - 1's tables, read until its vertical pass ended before A(i)
+      land((i + 1) & 1);
+    }
     H8S_BARRIER();                                                                   // B(i)
     if ((i & 1) == m && work + 2 * wstride < wend) {
-      issue(work + 2 * wstride, i & 1, gx, gy);
+      issue_window(work + 2 * wstride, i & 1, gx, gy);
       if (work + 4 * wstride < wend) geom(work + 4 * wstride, gx, gy);
     }
   }

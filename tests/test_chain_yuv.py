@@ -1,58 +1,23 @@
 """lgpu_chain_yuv420p: the 2:1 chain that starts at decoded planar 4:2:0 frames (K2's conversion in registers -> the exact 2:1 scaler -> [letterbox] -> [chroma blend]
 -> [gamma LUT], one launch) against the oracle's composition of the single stages, orc_yuv420p_to_rgb -> orc_pixbuf_scale -> [orc_letterbox] -> [orc_blend_chroma]
 -> [orc_gamma_apply]; at size against the two-launch form lgpu_yuv420p_to_rgb_batch + lgpu_chain_amounts; and its refusals."""
-import ctypes
-
 import numpy as np
 import pytest
 
 from oracle import pyoracle as po
+from tests.chain_ref import oracle_chain, planes
 from tests.util import align, dev, host
 
 pytestmark = pytest.mark.gpu
 P = po.P
 PIXBUF, NOBLEND = 0x100, 0x400
 E_BADARG, E_UNSUPPORTED = -2, -3
-BLACK = np.array([0, 0, 0, 255], np.uint8)
 
 
 def gamma_lut(orc):
     lut = np.zeros(256, np.uint8)
     assert orc.orc_gamma_lut8(1.0, po.GAMMA_SRGB, po.GAMMA_LINEAR, 1.4, P(lut)) == 1
     return lut
-
-
-def planes(rng, sw, sh, pad, tight):
-    """one 4:2:0 source: luma rows of sw + pad[0] bytes, chroma rows of sw / 2 + pad[1] / pad[2]; tight: each chroma plane ends with its last sample, so that K2's
-    read one past the last row's end is clamped to the plane's last byte"""
-    hw, hh = sw // 2, sh // 2
-    ys, us, vs = sw + pad[0], hw + pad[1], hw + pad[2]
-    usz = (hh - 1) * us + hw if tight else hh * us
-    vsz = (hh - 1) * vs + hw if tight else hh * vs
-    Y = rng.integers(0, 256, (sh, ys), dtype=np.uint8)
-    U = rng.integers(0, 256, usz, dtype=np.uint8)
-    V = rng.integers(0, 256, vsz, dtype=np.uint8)
-    return Y, U, V, (ys, us, vs)
-
-
-def oracle_chain(orc, Y, U, V, strides, sw, sh, interp, order, wt, q, fix, l2, amount, lut, canvas):
-    dw, dh = sw // 2, sh // 2
-    rgba = np.zeros((sh, sw * 4), np.uint8)
-    st = (ctypes.c_int * 3)(*strides)
-    orc.orc_yuv420p_to_rgb(P(Y), P(U), P(V), st, U.size, V.size, P(rgba), sw * 4, sw, sh, 4, order, 0, wt, q, None, fix)
-    out = np.zeros((dh, dw * 4), np.uint8)
-    assert orc.orc_pixbuf_scale(P(rgba), sw * 4, sw, sh, P(out), dw * 4, dw, dh, 4, interp) == 0
-    w, h = dw, dh
-    if canvas:
-        w, h = canvas[0], canvas[1]
-        big = np.zeros((h, w * 4), np.uint8)
-        orc.orc_letterbox(P(out), dw * 4, dw, dh, P(big), w * 4, w, h, 4, P(BLACK))
-        out = big
-    if l2 is not None:
-        orc.orc_blend_chroma(P(out), w * 4, P(l2), l2.strides[0], P(out), w * 4, w, h, 4, 0, amount)
-    if lut is not None:
-        orc.orc_gamma_apply(P(out), w * 4, w, h, 4, 0, P(lut))
-    return out
 
 
 def centred(n, size):

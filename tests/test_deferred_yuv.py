@@ -106,6 +106,37 @@ def test_sixteen_decoder_frames_one_launch(seam, orc, deferred):
         assert (results[0][i][1] == want).all(), "deferred == oracle, track %d" % i
 
 
+@pytest.mark.parametrize("n,launches", [(20, 1), (70, 2)])
+def test_more_than_sixteen_decoder_frames(seam, orc, deferred, n, launches):
+    """one tick of 20 / 70 pinned YUV420P / YVU420P tracks, one flush: lgpu_chain_yuv420p launches of at most LGPU_CHAIN_MAX_TRACKS tracks -- one of 20, then 64 + 6 --
+    nothing staged, no conversion pre-launch, every track equal to the oracle"""
+    L, wh, H = seam
+    rng = np.random.default_rng(0xD6 + n)
+    sw, sh, dw, dh = 128, 72, 64, 36
+    srcs = [yuv_planes(rng, sw, sh, pad=(8, 4, 12)) for _ in range(n)]
+    l2s = [frame(rng, dw, dh, 4, alpha_mix=True) for _ in range(n)]
+    pals = [YUV420P if i % 3 else YVU420P for i in range(n)]
+    amounts = [(17 * i + 5) % 256 for i in range(n)]
+    lays = [yuv_layer(wh, pals[i], sw, sh, *srcs[i]) for i in range(n)]
+    l2l = [wh.new_layer(RGBA32, dw, dh, [a], gamma=1) for a in l2s]
+    for a in lays + l2l:
+        assert L.lives_gpu_layer_pin(a) == 0
+    s0 = stats(L)
+    for i in range(n):
+        plan_step(L, wh, H, lays[i], l2l[i], dw, dh, None, amounts[i], 2)
+    assert L.lives_gpu_layers_flush((ctypes.c_void_p * n)(*lays), n) == 0
+    d = delta(s0, stats(L))
+    assert d[4] == n, "every conversion was recorded"
+    assert (d[1], d[2], d[3], d[5], d[6], d[7]) == (launches, n, 0, launches, n, 0), "%d launches of lgpu_chain_yuv420p for %d tracks: %s" % (launches, n, d)
+    lut = srgb_to(orc, 2)
+    for i in range(n):
+        assert L.lives_gpu_layer_sync(lays[i]) == 0
+        want = oracle_track(orc, *srcs[i], sw, sh, l2s[i], dw, dh, None, amounts[i], lut)
+        assert (view(wh, lays[i])[:, :dw * 4] == want).all(), "track %d of %d" % (i, n)
+    for a in lays + l2l:
+        assert L.lives_gpu_layer_unpin(a) == 0
+
+
 SHAPES = [
     # sw, sh, dw, dh, canvas, with layer 2, gamma target, note
     (262, 150, 128, 72, None, True, 2, "not 2:1"),

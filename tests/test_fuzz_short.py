@@ -30,3 +30,17 @@ def test_chain_forms_on_random_geometry(gpu):
     import fuzz_chain
     ran, tracks, bad = fuzz_chain.run(600, 77)
     assert ran > 400 and tracks > 800 and bad == 0
+
+
+@pytest.mark.gpu
+def test_chain_forms_on_random_geometry_many_tracks(gpu):
+    """tools/fuzz_chain.py with up to 64 tracks a launch: the 4:2:0 mode (lgpu_chain_yuv420p on random geometry, pitches, settings, band heights; 400 cases) and the
+    RGBA mode with max_tracks = 64 (200 cases)"""
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import fuzz_chain
+    ran, tracks, many, bad = fuzz_chain.run_yuv(400, 420)
+    assert bad == 0 and ran == 400 and many >= 400 // 3 and tracks > 4000, (ran, tracks, many, bad)
+    ran, tracks, bad = fuzz_chain.run(200, 64, max_tracks=64)
+    assert bad == 0 and ran > 100 and tracks > 2000, (ran, tracks, bad)
