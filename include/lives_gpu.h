@@ -437,6 +437,25 @@ typedef struct { const uint8_t *y_d, *u_d, *v_d; const uint8_t *layer2_d; uint8_
 typedef struct { int istrides[3]; long u_size, v_size; int out_order; int which_tables; int pb_quality; int flags; } lgpu_yuv_source;
 int lgpu_chain_yuv420p(const lgpu_chain_params *params, const lgpu_yuv_source *src, const lgpu_canvas *canvas, const lgpu_chain_yuv_track *tracks, int ntracks,
                        const uint8_t *amounts, void *stream);
+/* the chain ENDING at a YUV consumer (a playback plugin's or an encoder's palette: the reference's last convert_layer_palette_full of a tick, src/player.c:1364):
+   [R <-> B when params->swap_rb] -> scale [-> chroma blend] [-> gamma LUT] -> the K4 conversion (lgpu_rgb_to_yuv with in_alpha = 1, out_alpha = 0, every quirk kept:
+   U of a pair's first pixel and V of its second, YUYV without its upper chroma clamp, the 4:2:0 chroma walk cavg(row 2k + 2, row 2k + 1) with the last chroma row
+   from row dh - 1 alone), ONE launch for every track; the RGBA result is never written.  The bytes are those of lgpu_chain_amounts into an RGBA frame followed by
+   lgpu_rgb_to_yuv(.., sink->in_order, 1, .., sink->out_fmt, 0, sink->which_tables) on it.  Conventions of lgpu_chain_amounts (LGPU_INTERP_PIXBUF required;
+   LGPU_INTERP_NOBLEND: no layer 2, amounts may be NULL); params->orow is ignored in favour of sink->orow.  sink: out_fmt 2 UYVY / 3 YUYV (dst_d[0] alone) / 4 YUV420P
+   (dst_d[0..2] = Y, U, V; YVU420P: pass the chroma planes swapped) in lgpu_rgb_to_yuv's numbering; which_tables bit 0 unclamped, bit 1 BT.709 (4:2:0 only); in_order:
+   the byte order of the chain's RESULT, 0 RGBA / 1 BGRA.  Every argument is checked before anything is enqueued: LGPU_E_BADARG (null planes, 0 or 65 tracks, out_fmt
+   outside 2..5, in_order > 1, BT.709 with UYVY / YUYV, an odd dw, strides below a row's bytes, no PIXBUF, null amounts with a blend).  Only the one-launch form is
+   served: exact 2:1 (sw == 2 dw, sh == 2 dh), HYPER or BILINEAR, dw % 4 == 0, dh even for 4:2:0 (any dh for UYVY / YUYV), sink->orow[0] % 8 == 0 and chroma
+   rowstrides % 4 == 0, sink planes and source rows 16-byte aligned, layer-2 rows 8-byte aligned, no gaussian.  LGPU_E_UNSUPPORTED otherwise -- this includes, for now,
+   out_fmt 5 (YUV422P), an odd dh with 4:2:0, a letterbox canvas (the entry point takes none: chroma rows would straddle the bar / frame edge) and a YUV420P SOURCE
+   combined with the sink; run lgpu_chain_amounts + lgpu_rgb_to_yuv_batch then.  Nothing is written in either case.  The first call with a new (which_tables, in_order)
+   pair builds a 12 KB device table with a blocking allocation and copy outside `stream` (as the first chain call of a geometry does): make that call before a stream
+   capture begins.  The tables are kept until the process ends. */
+typedef struct { int out_fmt; int which_tables; int in_order; int orow[3]; } lgpu_chain_sink;
+typedef struct { const uint8_t *src_d, *layer2_d; uint8_t *dst_d[3]; } lgpu_chain_sink_track;
+int lgpu_chain_to_yuv(const lgpu_chain_params *params, const lgpu_chain_sink *sink, const lgpu_chain_sink_track *tracks, int ntracks, const uint8_t *amounts,
+                      void *stream);
 
 /* ---- timing helper: HIP events on `stream` around `reps` launches of the last-configured chain; used by
    bench.py to measure the kernel's average launch duration on the stream it is launched on. */

@@ -156,7 +156,12 @@ int lives_gpu_layer_set_opaque(lives_gpu_layer_t *layer, int on);
    reference's own calls).  A decoder's YUV420P / YVU420P frame converted to RGBA32 / BGRA32 without a gamma change is recorded the same way (the program takes the
    three planes; external surfaces of lives_gpu_layer_pin_device are only read): a flush then runs the group as ONE lgpu_chain_yuv420p launch in the exact 2:1
    shape, as at most two launches otherwise (the batched conversion, then lgpu_chain_amounts).  Results are those of the eager calls, bit for bit
-   (tests/test_deferred.py, tests/test_deferred_yuv.py).  What a stage can refuse is checked when it is recorded;
+   (tests/test_deferred.py, tests/test_deferred_yuv.py).  The LAST call of a tick records too: convert_layer_palette[_full] of the RGBA32 / BGRA32 frame to the
+   consumer's YUV420P / YVU420P / UYVY / YUYV (the hand-over to a playback plugin or an encoder, src/player.c:1364) without a gamma change on the way is the stage
+   LZ_SINK (a needed gamma change -- no target named on a layer that is not SRGB, or another target -- keeps the eager path).  The program then stands for up to
+   three host planes, and a read, sync or seam call on any of them runs it.  A flush runs programs of equal shape that end there as ONE lgpu_chain_to_yuv launch in
+   the exact 2:1 shape (no RGBA frame is written), as the chain group followed by ONE lgpu_rgb_to_yuv_batch per 16 tracks otherwise, and programs of the sink stage
+   alone as that batch (tests/test_deferred_sink.py).  What a stage can refuse is checked when it is recorded;
    device failures at run time surface at the flush / sync that runs the program.  lives_gpu_set_deferred(0) launches every call by itself (returns the old value). */
 int lives_gpu_set_deferred(int on);
 int lives_gpu_layers_flush(lives_gpu_layer_t *const *layers, int nlayers);
@@ -164,7 +169,9 @@ int lives_gpu_layers_flush(lives_gpu_layer_t *const *layers, int nlayers);
 void lives_gpu_deferred_stats(unsigned long long out[4]);
 /* the four counters above, then [4] YUV420P / YVU420P -> RGBA32 / BGRA32 conversions recorded (convert_layer_palette on a pinned layer, no gamma change), [5] one-launch
    YUV chain launches (lgpu_chain_yuv420p) and [6] the tracks they carried, [7] conversion pre-launches of the two-launch path (lgpu_yuv420p_to_rgb_batch for a group whose
-   shape the one-launch form does not take); at most n entries are written */
+   shape the one-launch form does not take), [8] sink conversions recorded (LZ_SINK), [9] sink launches -- a lgpu_chain_to_yuv launch (also counted in [1]) or one
+   lgpu_rgb_to_yuv_batch / lgpu_rgb_to_yuv -- and [10] the tracks they carried, [11] how many of [9] were fused lgpu_chain_to_yuv launches; at most n entries are
+   written */
 void lives_gpu_deferred_stats_n(unsigned long long *out, int n);
 /* (for livesgpu_fx.so) record an in-place "chroma blend" of the pending plane dst_host with the resident plane layer2_host; 1 = recorded, 0 = run the kernel */
 int lives_gpu_deferred_blend_chroma(const void *dst_host, int orow, int width, int height, int palette, const void *layer2_host, int irow2, int bf);

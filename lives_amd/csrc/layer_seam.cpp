@@ -26,6 +26,7 @@
 #include <atomic>
 #include <mutex>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 #include "../../include/lives_gpu.h"
 #include "../../include/lives_gpu_layer.h"
@@ -318,7 +319,11 @@ void res_drop_range(const void *base, size_t bytes) {
       if (h >= (uintptr_t)base && h < (uintptr_t)base + bytes) { gone.push_back(it->second); it = sh.m.erase(it); } else ++it;
     }
   }
-  for (auto &b : gone) pool_give(b);
+  for (size_t i = 0; i < gone.size(); i++) {
+    bool seen = false;                  // the planes of one sink program share its Lazy: discarded once
+    for (size_t k = 0; k < i && gone[i].lazy; k++) seen = seen || gone[k].lazy == gone[i].lazy;
+    if (!seen) pool_give(gone[i]);
+  }
 }
 int lives_gpu_layer_unpin_impl(weed_plant_t *layer);
 struct PinScope {
@@ -588,7 +593,10 @@ lives_gpu_boolean decline(weed_plant_t *layer) {
 // lives_gpu_set_deferred(0) switches the recording off (every call launches its own kernels, as before round 6); tests compare the two.
 // LZ_YUV: a decoder's YUV420P / YVU420P frame converted to RGBA32 / BGRA32 (K2, no gamma change) -- the program then owns (or, for surfaces of
 // lives_gpu_layer_pin_device, borrows) the three source planes and stands for the new RGBA host plane; the stages above are recorded on top of it.
-enum { LZ_NONE = 0, LZ_YUV = 1, LZ_SWAP = 2, LZ_SCALE = 3, LZ_CANVAS = 4, LZ_BLEND = 5, LZ_LUT = 6 };
+// LZ_SINK: the RGBA32 / BGRA32 frame converted to the consumer's YUV palette (K4: YUV420P / YVU420P / UYVY / YUYV, no gamma change) -- the last stage a program
+// can take.  The program then stands for up to THREE host planes: each has its own table entry pointing at the one Lazy (sph: the planes in the conversion's
+// Y, U, V order), so a read, sync or seam call on ANY of them runs it, and whichever entry is dropped first takes the others with it (lazy_discard).
+enum { LZ_NONE = 0, LZ_YUV = 1, LZ_SWAP = 2, LZ_SCALE = 3, LZ_CANVAS = 4, LZ_BLEND = 5, LZ_LUT = 6, LZ_SINK = 7 };
 struct Lazy {
   Dev src;                          // the frame the program starts from (owned: goes back to the pool when the program has run, unless external)
   int sw = 0, sh = 0, srs = 0;
@@ -601,10 +609,13 @@ struct Lazy {
   int w = 0, h = 0, rs = 0;         // the plane the program stands for
   // LZ_YUV: src is the luma plane; yu / yv the chroma planes (U, V order: a YVU420P layer's planes are swapped when recorded)
   bool yuv = false; Dev yu, yv; int ystr[3] = {0, 0, 0}; long usz = 0, vsz = 0; int order = 0, which = 0, quality = 2;
+  // LZ_SINK: K4 on the w x h RGBA plane above (sww x shh of it: 4:2:0 truncates to even sides) into snp planes of sors / sbytes, registered under host planes sph
+  bool sink = false; int sfmt = 0, swhich = 0, sorder = 0, snp = 0, sww = 0, shh = 0, sors[3] = {0, 0, 0}; size_t sbytes[3] = {0, 0, 0}; const void *sph[3] = {nullptr, nullptr, nullptr};
 };
 std::atomic<int> g_deferred{1};
 std::atomic<unsigned long long> g_lz_recorded{0}, g_lz_chain_launches{0}, g_lz_chain_tracks{0}, g_lz_staged{0};      // lives_gpu_deferred_stats
 std::atomic<unsigned long long> g_lz_yuv_recorded{0}, g_lz_yuv_launches{0}, g_lz_yuv_tracks{0}, g_lz_yuv_pre{0};        // lives_gpu_deferred_stats_n [4..7]
+std::atomic<unsigned long long> g_lz_sink_recorded{0}, g_lz_sink_launches{0}, g_lz_sink_tracks{0}, g_lz_sink_fused{0};    // lives_gpu_deferred_stats_n [8..11]
 std::mutex g_lazy_mu;               // one program (group) runs at a time; never taken with a table lock held
 bool lazy_pal(int pal) { return pal == WEED_PALETTE_RGBA32 || pal == WEED_PALETTE_BGRA32; }
 
@@ -618,6 +629,13 @@ void lazy_unread(Lazy *z) {          // (no lock held) the program no longer rea
 }
 void lazy_discard(Lazy *z) {
   if (!z) return;
+  if (z->sink)                          // the entries of the program's other planes point at it too: they go with it (the caller has taken its own out already)
+    for (int p = 0; p < z->snp; p++) {
+      ResShard &sh = shard_of(z->sph[p]);
+      std::lock_guard<SpinLock> lk(sh.mu);
+      auto it = sh.m.find(z->sph[p]);
+      if (it != sh.m.end() && it->second.lazy == z) sh.m.erase(it);
+    }
   lazy_unread(z);
   Dev src = z->src, yu = z->yu, yv = z->yv;
   const bool yuv = z->yuv;
@@ -629,7 +647,9 @@ bool lazy_same_shape(const Lazy *a, const Lazy *b) {
   return a->sw == b->sw && a->sh == b->sh && a->srs == b->srs && a->swap == b->swap && a->scale == b->scale && a->dw == b->dw && a->dh == b->dh &&
          a->interp == b->interp && a->opaque == b->opaque && a->canvas == b->canvas && a->nw == b->nw && a->nh == b->nh && a->ox == b->ox && a->oy == b->oy && a->blend == b->blend &&
          a->l2rs == b->l2rs &&          /* (not the blend amount: every track of a launch has its own, lgpu_chain_amounts) */ a->lut == b->lut && (!a->lut || !memcmp(a->lut8, b->lut8, 256)) && a->w == b->w && a->h == b->h && a->rs == b->rs &&
-         a->yuv == b->yuv && (!a->yuv || (!memcmp(a->ystr, b->ystr, sizeof a->ystr) && a->usz == b->usz && a->vsz == b->vsz && a->order == b->order && a->which == b->which && a->quality == b->quality));
+         a->yuv == b->yuv && (!a->yuv || (!memcmp(a->ystr, b->ystr, sizeof a->ystr) && a->usz == b->usz && a->vsz == b->vsz && a->order == b->order && a->which == b->which && a->quality == b->quality)) &&
+         a->sink == b->sink && (!a->sink || (a->sfmt == b->sfmt && a->swhich == b->swhich && a->sorder == b->sorder && a->snp == b->snp && a->sww == b->sww && a->shh == b->shh &&
+                                             !memcmp(a->sors, b->sors, sizeof a->sors)));
 }
 // one program, stage by stage through stream-ordered scratch frames, into out (the plane's rowstride)
 int lazy_run_staged(const Lazy *z, uint8_t *out, const uint8_t *src, int srs) {
@@ -666,20 +686,16 @@ int lazy_run_staged(const Lazy *z, uint8_t *out, const uint8_t *src, int srs) {
   for (int i = 0; i < nt; i++) lgpu_free_ordered(tmp[i], S());
   return rc;
 }
-// run n pending programs of ONE shape (g_lazy_mu held by the caller; hs[i]: the host plane zs[i] is registered under).  Afterwards the planes are ordinary
-// resident planes whose last writer is the calling thread's stream.
-int lazy_run_group(Lazy *const *zs, const void *const *hs, int n) {
+// the RGBA stages of n programs of one shape into outp[i] (rowstride z0->rs): one fused launch where the shape allows, else stage by stage
+int lazy_run_rgba(Lazy *const *zs, int n, uint8_t *const *outp) {
   const Lazy *z0 = zs[0];
   const size_t bytes = (size_t)z0->rs * z0->h;
-  std::vector<Dev> outs((size_t)n);
   int rc = LGPU_OK;
-  for (int i = 0; i < n; i++)
-    if (!pool_take(bytes, &outs[(size_t)i])) { for (int k = 0; k < i; k++) pool_give(outs[(size_t)k]); return LGPU_E_NOMEM; }
   for (int i = 0; i < n; i++) {
     await(zs[i]->src, false);
     if (zs[i]->yuv) { await(zs[i]->yu, false); await(zs[i]->yv, false); }
     if (zs[i]->blend) await(zs[i]->l2, false);
-    if (z0->rs != z0->w * 4) rc = rc ? rc : lgpu_fill(outs[(size_t)i].d, 0, bytes, S());      // the row padding of a fresh plane is zero (calloc in the eager path)
+    if (z0->rs != z0->w * 4) rc = rc ? rc : lgpu_fill(outp[i], 0, bytes, S());      // the row padding of a fresh plane is zero (calloc in the eager path)
   }
   bool done = false;
   const bool staged = lgpu_tuning_get("SEAM_STAGED") > 0;
@@ -708,7 +724,7 @@ int lazy_run_group(Lazy *const *zs, const void *const *hs, int n) {
       std::vector<lgpu_chain_yuv_track> yt((size_t)n);
       for (int i = 0; i < n; i++) {
         yt[(size_t)i].y_d = (const uint8_t *)zs[i]->src.d; yt[(size_t)i].u_d = (const uint8_t *)zs[i]->yu.d; yt[(size_t)i].v_d = (const uint8_t *)zs[i]->yv.d;
-        yt[(size_t)i].layer2_d = (const uint8_t *)zs[i]->l2.d; yt[(size_t)i].dst_d = (uint8_t *)outs[(size_t)i].d;
+        yt[(size_t)i].layer2_d = (const uint8_t *)zs[i]->l2.d; yt[(size_t)i].dst_d = outp[i];
       }
       const int crc = lgpu_chain_yuv420p(&pr, &ys, z0->canvas ? &cv : nullptr, yt.data(), n, z0->blend ? amounts.data() : nullptr, S());
       if (crc == LGPU_OK) { done = true; g_lz_chain_launches++; g_lz_chain_tracks += (unsigned long long)n; g_lz_yuv_launches++; g_lz_yuv_tracks += (unsigned long long)n; }
@@ -723,7 +739,7 @@ int lazy_run_group(Lazy *const *zs, const void *const *hs, int n) {
       std::vector<lgpu_yuv_frame> fr((size_t)n);
       for (int i = 0; i < n; i++) {
         fr[(size_t)i].y_d = (const uint8_t *)zs[i]->src.d; fr[(size_t)i].u_d = (const uint8_t *)zs[i]->yu.d; fr[(size_t)i].v_d = (const uint8_t *)zs[i]->yv.d;
-        fr[(size_t)i].dst_d = only ? (uint8_t *)outs[(size_t)i].d : (uint8_t *)scr + (size_t)i * per;
+        fr[(size_t)i].dst_d = only ? outp[i] : (uint8_t *)scr + (size_t)i * per;
       }
       const int orow = only ? z0->rs : z0->sw * 4;
       if (!rc && !staged && n <= LGPU_CHAIN_MAX_TRACKS) {
@@ -742,30 +758,52 @@ int lazy_run_group(Lazy *const *zs, const void *const *hs, int n) {
   // every shape: with or without a resize stage, with or without a blend (lgpu_chain_amounts); LGPU_SEAM_STAGED / lgpu_tuning_set("SEAM_STAGED", 1): the fallback walk, for tests
   if (!rc && !done && n <= LGPU_CHAIN_MAX_TRACKS && !staged) {
     std::vector<lgpu_chain_track> tr((size_t)n);
-    for (int i = 0; i < n; i++) { tr[(size_t)i].src_d = srcp[(size_t)i]; tr[(size_t)i].layer2_d = (const uint8_t *)zs[i]->l2.d; tr[(size_t)i].dst_d = (uint8_t *)outs[(size_t)i].d; }
+    for (int i = 0; i < n; i++) { tr[(size_t)i].src_d = srcp[(size_t)i]; tr[(size_t)i].layer2_d = (const uint8_t *)zs[i]->l2.d; tr[(size_t)i].dst_d = outp[i]; }
     const int crc = lgpu_chain_amounts(&pr, z0->canvas ? &cv : nullptr, tr.data(), n, amounts.data(), S());
     if (crc == LGPU_OK) { done = true; g_lz_chain_launches++; g_lz_chain_tracks += (unsigned long long)n; }
     else if (crc != LGPU_E_BADARG && crc != LGPU_E_UNSUPPORTED) rc = crc;          // a shape the fused kernel does not take runs stage by stage below
   }
   if (!rc && !done)
-    for (int i = 0; i < n && !rc; i++) { rc = lazy_run_staged(zs[i], (uint8_t *)outs[(size_t)i].d, srcp[(size_t)i], srow); g_lz_staged++; }
+    for (int i = 0; i < n && !rc; i++) { rc = lazy_run_staged(zs[i], outp[i], srcp[(size_t)i], srow); g_lz_staged++; }
   if (scr) lgpu_free_ordered(scr, S());
+  return rc;
+}
+int lazy_run_sink(Lazy *const *zs, int n, Dev (*souts)[3]);
+// run n pending programs of ONE shape (g_lazy_mu held by the caller; hs[i]: the host plane zs[i] is registered under; a program that ends in LZ_SINK names its planes itself, Lazy::sph).  Afterwards the planes are ordinary
+// resident planes whose last writer is the calling thread's stream.
+int lazy_run_group(Lazy *const *zs, const void *const *hs, int n) {
+  const Lazy *z0 = zs[0];
+  const bool sink = z0->sink;
+  const int np = sink ? z0->snp : 1;
+  std::vector<Dev> outs((size_t)n * 3);                                               // [track][plane]
+  int rc = LGPU_OK;
+  for (int i = 0; i < n && !rc; i++)
+    for (int p = 0; p < np && !rc; p++)
+      if (!pool_take(sink ? z0->sbytes[p] : (size_t)z0->rs * z0->h, &outs[(size_t)i * 3 + p])) rc = LGPU_E_NOMEM;
+  if (!rc && sink) rc = lazy_run_sink(zs, n, reinterpret_cast<Dev (*)[3]>(outs.data()));
+  else if (!rc) {
+    std::vector<uint8_t *> outp((size_t)n);
+    for (int i = 0; i < n; i++) outp[(size_t)i] = (uint8_t *)outs[(size_t)i * 3].d;
+    rc = lazy_run_rgba(zs, n, outp.data());
+  }
   if (rc) {                                                                            // the programs stay pending; what was enqueued wrote scratch only
-    for (int i = 0; i < n; i++) { outs[(size_t)i].stream = S(); pool_give(outs[(size_t)i]); }
+    for (Dev &o : outs) if (o.d) { o.stream = S(); pool_give(o); }
     return rc;
   }
   for (int i = 0; i < n; i++) {
     Lazy *z = zs[i];
-    {
-      ResShard &sh = shard_of(hs[i]);
+    for (int p = 0; p < np; p++) {
+      const void *h = sink ? z->sph[p] : hs[i];
+      Dev &o = outs[(size_t)i * 3 + p];
+      ResShard &sh = shard_of(h);
       std::lock_guard<SpinLock> lk(sh.mu);
-      auto it = sh.m.find(hs[i]);
+      auto it = sh.m.find(h);
       if (it != sh.m.end() && it->second.lazy == z) {
         Dev &e = it->second;
         const int readers = e.lazy_readers;
-        e = outs[(size_t)i];
+        e = o;
         e.stream = S(); e.nr = 0; e.lazy = nullptr; e.lazy_readers = readers;
-        outs[(size_t)i] = Dev();
+        o = Dev();
       }
     }
     if (z->blend && z->l2h) {
@@ -775,7 +813,7 @@ int lazy_run_group(Lazy *const *zs, const void *const *hs, int n) {
       if (l2 != sh.m.end()) { note_use(l2->second, false); if (l2->second.lazy_readers > 0) l2->second.lazy_readers--; }
       z->l2h = nullptr;
     }
-    if (outs[(size_t)i].d) { outs[(size_t)i].stream = S(); pool_give(outs[(size_t)i]); }          // (the plane vanished meanwhile: cannot happen under the host's own ordering)
+    for (int p = 0; p < np; p++) { Dev &o = outs[(size_t)i * 3 + p]; if (o.d) { o.stream = S(); pool_give(o); o = Dev(); } }          // (the plane vanished meanwhile: cannot happen under the host's own ordering)
     Dev src = z->src, yu = z->yu, yv = z->yv;
     const bool yuv = z->yuv;
     delete z;
@@ -789,6 +827,73 @@ int lazy_run_group(Lazy *const *zs, const void *const *hs, int n) {
     }
   }
   return LGPU_OK;
+}
+// n pending programs of ONE shape that end in LZ_SINK, into souts[track][plane] (the conversion's Y, U, V order).  The form is chosen by tools/bench_sink_chain.py's
+// measurement (profiles/r08/sink_chain.md: 16 x 4K -> 1080p, blend + LUT, the fused launch 157 us against 185 for the two launches to YUV420P, 147 against 187 to
+// UYVY, rounds within 2 us of each other): whatever fits lgpu_chain_to_yuv's one-launch form takes it -- ONE launch, no RGBA frame; every other shape runs its RGBA
+// stages as the chain group into scratch frames, followed by ONE lgpu_rgb_to_yuv_batch per 16 tracks; a program of the sink stage alone is that batch on the
+// resident frames.  SEAM_STAGED: stage by stage and one conversion per track, for tests.
+int lazy_run_sink(Lazy *const *zs, int n, Dev (*souts)[3]) {
+  const Lazy *z0 = zs[0];
+  const bool staged = lgpu_tuning_get("SEAM_STAGED") > 0;
+  const bool rgba_stages = z0->yuv || z0->swap || z0->scale || z0->canvas || z0->blend || z0->lut;
+  int rc = LGPU_OK;
+  const int row_bytes[3] = {z0->sfmt == 4 ? z0->sww : z0->sww * 2, z0->sww >> 1, z0->sww >> 1};
+  for (int i = 0; i < n && !rc; i++)
+    for (int p = 0; p < z0->snp && !rc; p++)
+      if (z0->sors[p] != row_bytes[p]) rc = lgpu_fill(souts[i][p].d, 0, z0->sbytes[p], S());      // the row padding of a fresh plane is zero (calloc in the eager path)
+  if (rc) return rc;
+  if (!staged && z0->scale && !z0->canvas && !z0->yuv && z0->sww == z0->w && z0->shh == z0->h && n <= LGPU_CHAIN_MAX_TRACKS) {
+    for (int i = 0; i < n; i++) { await(zs[i]->src, false); if (zs[i]->blend) await(zs[i]->l2, false); }
+    lgpu_chain_params pr;
+    memset(&pr, 0, sizeof pr);
+    pr.sw = z0->sw; pr.sh = z0->sh; pr.irow = z0->srs; pr.dw = z0->dw; pr.dh = z0->dh; pr.irow2 = z0->blend ? z0->l2rs : 0; pr.orow = 0;
+    pr.swap_rb = z0->swap ? 1 : 0; pr.interp = z0->interp | LGPU_INTERP_PIXBUF | (z0->blend ? 0 : LGPU_INTERP_NOBLEND); pr.use_lut = z0->lut ? 1 : 0;
+    if (z0->lut) memcpy(pr.lut8, z0->lut8, 256);
+    lgpu_chain_sink sk;
+    memset(&sk, 0, sizeof sk);
+    sk.out_fmt = z0->sfmt; sk.which_tables = z0->swhich; sk.in_order = z0->sorder;
+    for (int p = 0; p < z0->snp; p++) sk.orow[p] = z0->sors[p];
+    std::vector<lgpu_chain_sink_track> tr((size_t)n);
+    std::vector<uint8_t> amounts((size_t)n);
+    for (int i = 0; i < n; i++) {
+      memset(&tr[(size_t)i], 0, sizeof tr[0]);
+      tr[(size_t)i].src_d = (const uint8_t *)zs[i]->src.d; tr[(size_t)i].layer2_d = (const uint8_t *)zs[i]->l2.d;
+      for (int p = 0; p < z0->snp; p++) tr[(size_t)i].dst_d[p] = (uint8_t *)souts[i][p].d;
+      amounts[(size_t)i] = (uint8_t)zs[i]->bf;
+    }
+    const int crc = lgpu_chain_to_yuv(&pr, &sk, tr.data(), n, z0->blend ? amounts.data() : nullptr, S());
+    if (crc == LGPU_OK) {
+      g_lz_chain_launches++; g_lz_chain_tracks += (unsigned long long)n; g_lz_sink_launches++; g_lz_sink_tracks += (unsigned long long)n; g_lz_sink_fused++;
+      return LGPU_OK;
+    }
+    if (crc != LGPU_E_BADARG && crc != LGPU_E_UNSUPPORTED) return crc;            // a shape outside the one-launch form takes the two launches below
+  }
+  // the RGBA frames the conversion reads: the programs' results in scratch, or -- a program of the sink stage alone -- the resident frames themselves
+  std::vector<const uint8_t *> rgba((size_t)n);
+  int rrow = z0->srs;
+  void *scr = nullptr;
+  if (rgba_stages) {
+    const size_t per = ((size_t)z0->rs * z0->h + 63) & ~(size_t)63;
+    if ((rc = lgpu_malloc_ordered(&scr, per * (size_t)n + 64, S()))) return rc;
+    std::vector<uint8_t *> outp((size_t)n);
+    for (int i = 0; i < n; i++) { outp[(size_t)i] = (uint8_t *)scr + (size_t)i * per; rgba[(size_t)i] = outp[(size_t)i]; }
+    rc = lazy_run_rgba(zs, n, outp.data());
+    rrow = z0->rs;
+  } else
+    for (int i = 0; i < n; i++) { await(zs[i]->src, false); rgba[(size_t)i] = (const uint8_t *)zs[i]->src.d; }
+  int ors[4] = {z0->sors[0], z0->sors[1], z0->sors[2], 0};
+  for (int i0 = 0; i0 < n && !rc; i0 += (staged ? 1 : LGPU_FX_MAX_FRAMES)) {
+    const int m = staged ? 1 : std::min(n - i0, (int)LGPU_FX_MAX_FRAMES);
+    uint8_t *dp[LGPU_FX_MAX_FRAMES * 4];
+    memset(dp, 0, sizeof dp);
+    for (int i = 0; i < m; i++) for (int p = 0; p < z0->snp; p++) dp[i * 4 + p] = (uint8_t *)souts[i0 + i][p].d;
+    if (staged) rc = lgpu_rgb_to_yuv(rgba[(size_t)i0], rrow, z0->sww, z0->shh, z0->sorder, 1, dp, ors, z0->sfmt, 0, z0->swhich, S());
+    else rc = lgpu_rgb_to_yuv_batch(rgba.data() + i0, rrow, z0->sww, z0->shh, z0->sorder, 1, dp, ors, z0->sfmt, 0, z0->swhich, m, S());
+    if (!rc) { g_lz_sink_launches++; g_lz_sink_tracks += (unsigned long long)m; }
+  }
+  if (scr) lgpu_free_ordered(scr, S());
+  return rc;
 }
 // the pending program of plane h, if any, runs now (on the calling thread's stream)
 bool lazy_materialise(const void *h) {
@@ -1041,8 +1146,10 @@ lives_gpu_boolean rgb_layer_to_yuv(weed_plant_t *layer, const Layer &l_in, int o
   int new_gamma = WEED_GAMMA_UNKNOWN;
   const bool inline_gamma = (outpl == WEED_PALETTE_UYVY || outpl == WEED_PALETTE_YUYV);
   const uint16_t *lut16 = nullptr;
+  bool gamma_change = false;                      // the conversion needs a gamma change on the way: not recorded as LZ_SINK
   if (g_prefs.apply_gamma && l.gamma != WEED_GAMMA_UNKNOWN) {
     new_gamma = tgt_gamma != WEED_GAMMA_UNKNOWN ? tgt_gamma : osubspace == WEED_YUV_SUBSPACE_BT709 ? WEED_GAMMA_BT709 : WEED_GAMMA_SRGB;
+    gamma_change = new_gamma != l.gamma;
     if (!inline_gamma) {
       if (new_gamma != l.gamma && !lives_gpu_gamma_convert_layer(new_gamma, layer)) return decline(layer);
       if (!read_layer(layer, &l)) return 0;
@@ -1066,6 +1173,40 @@ lives_gpu_boolean rgb_layer_to_yuv(weed_plant_t *layer, const Layer &l_in, int o
   const int which = (oclamping == WEED_YUV_CLAMPING_UNCLAMPED ? 1 : 0) | ((fmt >= 4 && use_osub && osubspace == WEED_YUV_SUBSPACE_BT709) ? 2 : 0);
   const int lwidth = (fmt == 2 || fmt == 3) ? width >> 1 : width;                   // UYVY / YUYV layers count macropixels
   NewPlanes np;
+  // RGBA32 / BGRA32 on a pinned layer to the sink's palette with no gamma change on the way: recorded as the program's last stage, LZ_SINK, not launched (deferred
+  // execution, above).  A needed gamma change keeps the eager path below.  For UYVY / YUYV that is a matter of arithmetic (they take the 16-bit LUT inline there).
+  // For the planar sinks it is only a limit of this stage: the lives_gpu_gamma_convert_layer above may itself have been recorded (LZ_LUT) and is materialised by the
+  // eager conversion; LZ_LUT followed by LZ_SINK would be the same bytes (8-bit LUT, then K4) and could be recorded -- gamma_change, taken before that call, rules it out.
+  const bool sink_pal = outpl == WEED_PALETTE_YUV420P || outpl == WEED_PALETTE_YVU420P || outpl == WEED_PALETTE_UYVY || outpl == WEED_PALETTE_YUYV;
+  if (sink_pal && !gamma_change && lazy_pal(l.pal)) {
+    if (Lazy *z = lazy_detach(l, LZ_SINK)) {
+      if (!alloc_planes(outpl, lwidth, height, 0, &np)) { lazy_reattach(l.pd[0], z); return 0; }
+      z->sink = true; z->stage = LZ_SINK; z->sfmt = fmt; z->swhich = which; z->sorder = order; z->snp = np.n; z->sww = width; z->shh = height;
+      for (int p = 0; p < np.n; p++) { z->sors[p] = np.rs[p]; z->sbytes[p] = np.sz[p]; z->sph[p] = np.pd[p]; }
+      g_lz_recorded++; g_lz_sink_recorded++;
+      for (int p = 0; p < np.n; p++) {                                               // one entry per plane, all pointing at the program
+        Dev e, old;
+        e.lazy = z; e.bytes = np.sz[p]; e.stream = kIdle;
+        {
+          ResShard &sh = shard_of(np.pd[p]);
+          std::lock_guard<SpinLock> lk(sh.mu);
+          Dev &slot = sh.m[np.pd[p]];
+          old = slot;
+          slot = e;
+        }
+        if (old.d || old.lazy) pool_give(old);
+      }
+      if (l.contiguous) pfree(l.pd[0]); else for (int i = 0; i < l.nplanes; i++) pfree(l.pd[i]);      // free_planes without the table (the entry has moved)
+      if (outpl == WEED_PALETTE_YVU420P) { uint8_t *t = np.pd[1]; np.pd[1] = np.pd[2]; np.pd[2] = t; }   // swap_chroma_planes (:13890)
+      commit_planes(layer, outpl, lwidth, height, np);
+      if (flags != l.flags) set_int(layer, kLeafHostFlags, flags);
+      set_int(layer, WEED_LEAF_YUV_CLAMPING, oclamping);
+      if (inline_gamma && new_gamma != WEED_GAMMA_UNKNOWN) set_int(layer, WEED_LEAF_GAMMA_TYPE, new_gamma);                                   // (== l.gamma here)
+      set_int(layer, WEED_LEAF_YUV_SUBSPACE, l.gamma == WEED_GAMMA_BT709 ? WEED_YUV_SUBSPACE_BT709 : WEED_YUV_SUBSPACE_YCBCR);
+      if (fmt >= 4 || !has_leaf(layer, WEED_LEAF_YUV_SAMPLING)) set_int(layer, WEED_LEAF_YUV_SAMPLING, WEED_YUV_SAMPLING_DEFAULT);
+      return 1;
+    }
+  }
   if (!alloc_planes(outpl, lwidth, height, 0, &np)) return 0;
   Work w;
   const uint8_t *d_in = w.in(l.pd[0], (size_t)l.rs[0] * l.height, 0);
@@ -2072,12 +2213,15 @@ void lives_gpu_deferred_stats(unsigned long long out[4]) {
   out[0] = g_lz_recorded.load(); out[1] = g_lz_chain_launches.load(); out[2] = g_lz_chain_tracks.load(); out[3] = g_lz_staged.load();
 }
 // the same counters, then [4] YUV420P / YVU420P conversions recorded, [5] one-launch YUV chain launches (lgpu_chain_yuv420p) and [6] the tracks they carried,
-// [7] conversion pre-launches of the two-launch path (lgpu_yuv420p_to_rgb_batch); at most n entries are written
+// [7] conversion pre-launches of the two-launch path (lgpu_yuv420p_to_rgb_batch), [8] sink conversions recorded (LZ_SINK), [9] sink launches (a fused
+// lgpu_chain_to_yuv launch, also counted in [1], or one lgpu_rgb_to_yuv_batch / lgpu_rgb_to_yuv) and [10] the tracks they carried, [11] those of [9] that were fused lgpu_chain_to_yuv launches (the others converted an
+// RGBA frame); at most n entries are written
 void lives_gpu_deferred_stats_n(unsigned long long *out, int n) {
   if (!out || n <= 0) return;
-  const unsigned long long v[8] = {g_lz_recorded.load(), g_lz_chain_launches.load(), g_lz_chain_tracks.load(), g_lz_staged.load(),
-                                   g_lz_yuv_recorded.load(), g_lz_yuv_launches.load(), g_lz_yuv_tracks.load(), g_lz_yuv_pre.load()};
-  for (int i = 0; i < n && i < 8; i++) out[i] = v[i];
+  const unsigned long long v[12] = {g_lz_recorded.load(), g_lz_chain_launches.load(), g_lz_chain_tracks.load(), g_lz_staged.load(),
+                                    g_lz_yuv_recorded.load(), g_lz_yuv_launches.load(), g_lz_yuv_tracks.load(), g_lz_yuv_pre.load(),
+                                    g_lz_sink_recorded.load(), g_lz_sink_launches.load(), g_lz_sink_tracks.load(), g_lz_sink_fused.load()};
+  for (int i = 0; i < n && i < 12; i++) out[i] = v[i];
 }
 // Run the pending programs of these layers now, on the calling thread's stream: programs of equal shape (the tracks of one plan step) share ONE launch of the
 // fused chain kernel.  The layers stay pinned, nothing is downloaded, the host does not wait.  What a host calls once per tick when the plan steps of its tracks
@@ -2091,26 +2235,31 @@ int lives_gpu_layers_flush(lives_gpu_layer_t *const *layers, int nlayers) {
     for (int p = 0; p < l.nplanes; p++) hs.push_back(l.pd[p]);
   }
   std::lock_guard<std::mutex> run(g_lazy_mu);
-  std::vector<Lazy *> zs(hs.size(), nullptr);
-  for (size_t i = 0; i < hs.size(); i++) {
-    ResShard &sh = shard_of(hs[i]);
-    std::lock_guard<SpinLock> lk(sh.mu);
-    auto it = sh.m.find(hs[i]);
-    if (it != sh.m.end()) zs[i] = it->second.lazy;
+  // every pending program ONCE, under the first of its planes listed: a program that ends in LZ_SINK is registered under up to three host planes, and a layer may
+  // be listed twice.  Running a group deletes its programs, so no pointer may be looked at again after its group has run.
+  std::vector<Lazy *> zs;
+  std::vector<const void *> zh;
+  {
+    std::unordered_set<const Lazy *> seen;
+    for (size_t i = 0; i < hs.size(); i++) {
+      Lazy *z = nullptr;
+      {
+        ResShard &sh = shard_of(hs[i]);
+        std::lock_guard<SpinLock> lk(sh.mu);
+        auto it = sh.m.find(hs[i]);
+        if (it != sh.m.end()) z = it->second.lazy;
+      }
+      if (z && seen.insert(z).second) { zs.push_back(z); zh.push_back(hs[i]); }
+    }
   }
   int rc = LGPU_OK;
-  std::vector<char> done(hs.size(), 0);
-  for (size_t i = 0; i < hs.size(); i++) {
-    if (!zs[i] || done[i]) continue;
+  std::vector<char> done(zs.size(), 0);
+  for (size_t i = 0; i < zs.size(); i++) {
+    if (done[i]) continue;
     std::vector<Lazy *> gz;
     std::vector<const void *> gh;
-    for (size_t k = i; k < hs.size() && (int)gz.size() < LGPU_CHAIN_MAX_TRACKS; k++)
-      if (zs[k] && !done[k] && lazy_same_shape(zs[i], zs[k])) {
-        bool dup = false;
-        for (Lazy *q : gz) dup = dup || q == zs[k];
-        done[k] = 1;
-        if (!dup) { gz.push_back(zs[k]); gh.push_back(hs[k]); }
-      }
+    for (size_t k = i; k < zs.size() && (int)gz.size() < LGPU_CHAIN_MAX_TRACKS; k++)
+      if (!done[k] && lazy_same_shape(zs[i], zs[k])) { done[k] = 1; gz.push_back(zs[k]); gh.push_back(zh[k]); }
     const int r = lazy_run_group(gz.data(), gh.data(), (int)gz.size());
     if (r && !rc) rc = r;
   }

@@ -118,6 +118,20 @@ __device__ __forceinline__ void yuv_rgb(uint32_t yy, uint32_t rcr, uint32_t gcr,
   const int sr = (int)(yy + rcr), sg = (int)(yy + gcb + gcr), sb = (int)(yy + bcb);
   r = (uint32_t)min(max(sr >> 16, 0), 255); g = (uint32_t)min(max(sg >> 16, 0), 255); b = (uint32_t)min(max(sb >> 16, 0), 255);
 }
+// init_average's clamped chroma average (src/colourspace.c:190-216; palette.hip has the table form, cavg_lds, and compares the two over all 65,536 pairs when the
+// table is built: cavg_forms_checked()).
+// fa(x) WITHOUT the table: d = x - 128 is exact in float, 255 / 244 = KHI + KLO to 48 bits, and fmaf(d, KHI, d * KLO) rounds the exact d * KHI + fl(d * KLO) once --
+// for all 256 bytes the float the double division gives (k_build_cavgc compares the two forms entry by entry; tests/test_gpu_parity.py::test_chroma_average_table).
+// Four vector operations instead of an LDS gather: for kernels whose LDS pipe is full of table gathers (YUV411 -> RGB: 67 % bank-conflict cycles).
+__device__ __forceinline__ float cavg_fa_arith(float d) { return __fmaf_rn(d, 0x1.0b8a7ep+0f, __fmul_rn(d, -0x1.92e2ap-28f)); }
+__device__ __forceinline__ int cavg_arith(int clamped, int x, int y) {
+  if (!clamped) {
+    const int c = (((x - 128) + (y - 128)) >> 1) + 128;
+    return c > 255 ? 255 : c < 0 ? 0 : c;
+  }
+  const float fc = __fmaf_rn(__fadd_rn(cavg_fa_arith((float)(x - 128)), cavg_fa_arith((float)(y - 128))), 0.4375f, 128.f);
+  return (int)__builtin_amdgcn_fmed3f(fc, 16.f, 240.f);
+}
 // [1 4 6 4 1] on packed 16-bit lanes, a + e + 4 (b + d) + 6 c + k, without a 32-bit multiply: the operands of the vertical pass exceed 24 bits, so `6u * c` became
 // v_mul_lo_u32 (a quarter of the vector rate); ((b + c + d) << 2) + (c << 1) + (a + e + k) is two v_add3 and two v_lshl_add
 __device__ __forceinline__ uint32_t gauss5_taps(uint32_t a, uint32_t b, uint32_t c, uint32_t d, uint32_t e, uint32_t k = 0u) { return ((b + c + d) << 2) + (c << 1) + (a + e + k); }

@@ -60,18 +60,7 @@ __device__ __forceinline__ int cavg_lds(int clamped, const float *s_fa, int x, i
   const float fc = __fmaf_rn(__fadd_rn(s_fa[x], s_fa[y]), 0.4375f, 128.f);
   return (int)__builtin_amdgcn_fmed3f(fc, 16.f, 240.f);       // > 240 -> 240, < 16 -> 16, else truncated: one v_med3_f32 instead of two compares and two v_cndmask_b32_e32 (which issue at 1 / 4.6 rate)
 }
-// fa(x) WITHOUT the table: d = x - 128 is exact in float, 255 / 244 = KHI + KLO to 48 bits, and fmaf(d, KHI, d * KLO) rounds the exact d * KHI + fl(d * KLO) once --
-// for all 256 bytes the float the double division gives (k_build_cavgc compares the two forms entry by entry; tests/test_gpu_parity.py::test_chroma_average_table).
-// Four vector operations instead of an LDS gather: for kernels whose LDS pipe is full of table gathers (YUV411 -> RGB: 67 % bank-conflict cycles).
-__device__ __forceinline__ float cavg_fa_arith(float d) { return __fmaf_rn(d, 0x1.0b8a7ep+0f, __fmul_rn(d, -0x1.92e2ap-28f)); }
-__device__ __forceinline__ int cavg_arith(int clamped, int x, int y) {
-  if (!clamped) {
-    const int c = (((x - 128) + (y - 128)) >> 1) + 128;
-    return c > 255 ? 255 : c < 0 ? 0 : c;
-  }
-  const float fc = __fmaf_rn(__fadd_rn(cavg_fa_arith((float)(x - 128)), cavg_fa_arith((float)(y - 128))), 0.4375f, 128.f);
-  return (int)__builtin_amdgcn_fmed3f(fc, 16.f, 240.f);
-}
+// (cavg_fa_arith / cavg_arith -- fa(x) WITHOUT the table -- live in lgpu_common.h: the 2:1 chain's YUV420P sink, pixbuf.hip, averages with them too)
 __device__ unsigned int d_cavg_forms_differ = 0;
 __device__ const uint8_t *d_cavgc = nullptr;
 // built with the fma form (cavg_lds) the kernels use; tests/test_gpu_parity.py::test_chroma_average_table compares all 65,536 entries with the reference's table
@@ -1399,6 +1388,8 @@ __global__ __launch_bounds__(kBlock) void k_yuv_repack(RepackArgs a) {
 using namespace lgpu;
 
 // per-device table of the clamped chroma average (see d_cavgc above); called by every entry point whose kernels average chroma
+static int ensure_cavgc();
+namespace lgpu { int cavg_forms_checked() { return ensure_cavgc(); } }      // for kernels elsewhere that average with cavg_arith (pixbuf.hip: the chain's 4:2:0 sink)
 static int ensure_cavgc() {
   static std::mutex mu;
   static uint8_t *tab[64] = {};

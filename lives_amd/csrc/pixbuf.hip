@@ -395,8 +395,41 @@ struct PbNoYuv {};
 template <int YUV> struct PbYuvArg { typedef PbNoYuv type; };
 template <> struct PbYuvArg<1> { typedef PbYuvSrc type; };
 
-template <int CHAIN, int HYPER, int BLUR, int ALIGNED = 0, int SWAP = 0, int OPAQUE = 0, int YUV = 0>
-__global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTracks T, const Lut8 lut, const typename PbYuvArg<YUV>::type Y = typename PbYuvArg<YUV>::type()) {
+// SINK (lgpu_chain_to_yuv): the chain ENDS at a YUV consumer -- the two finished pixels of a lane (after blend and LUT, alpha dropped) are converted with K4's
+// arithmetic (palette.hip: the nine rgb2yuv table sums >> 16 as a short, upper clamp then lower, Y 16..235 / chroma 16..240 or 0..255) and stored as luma and chroma;
+// the RGBA frame is never written.  1: packed 4:2:2, one macropixel = one dword per lane and row (PbSinkDst.fmt 2 UYVY / 3 YUYV, which keeps rgb2yuyv's lost upper
+// chroma clamp); U of the pair's first pixel, V of its second; row-local.  2: planar 4:2:0 -- luma every row, chroma by the reference's in-place walk
+// (src/colourspace.c:6302-6315, palette.hip k_rgb_to_yuv420_s): chroma row k = cavg(row 2k + 2, row 2k + 1) for k < dh / 2 - 1, the last chroma row is row dh - 1's
+// alone, row 0's chroma is never kept -- i.e. the rows pair up as 0 | (1, 2) (3, 4) .. (dh - 3, dh - 2) | dh - 1.  A wave walks its band row by row, so the first row of
+// a pair (the odd one walking down, the even one walking up) leaves its clamped U and V in two registers for the next row.  BAND BOUNDARIES LIE AT ODD ROWS in this
+// form (band 0 and the last band of odd height, the others even; PbSinkDst.pairs: whole row pairs per band, PBH_TH requests are rounded to that): no band then
+// needs a row it does not produce itself -- a boundary at an even row would cost two more source rows and a layer-2 row per ~5-row band.
+// Tables: the nine tables as TWO LDS tables of 8-byte entries per colour byte, {Y, U} for the pair's first pixel and {Y, V} for its second (12 KB, staged once per
+// workgroup from a device table that already has this shape and the byte order of the chain's result folded in: six 8-byte loads per thread, one barrier, before any
+// wave leaves).  Six ds_read_b64 per lane and row instead of palette.hip's six ds_read_b128 of {Y, U, V, 0}: half the LDS bytes.  The indices are pixel data, so the
+// gathers conflict like random ones: a ds_read_b64 is served in two groups of 32 lanes over 64 banks, 32 random 8-byte entries on 32 bank pairs -- three to four
+// deep at worst, ~12 clocks per gather, ~70 per wave and row against the ~330 clocks of LDS pipe a CU has per wave and row at the RGBA chain's pace (estimates
+// from the bank rules, not counters; measured end to end in profiles/r08/sink_chain.md).
+// Stores: a lane has 2 luma bytes per row and 1 + 1 chroma bytes per row pair; short and byte stores cost 12x / 25x a 16-byte store per byte, so a quad of lanes
+// collects its bytes in its first lane over two DPP quad permutes -- 8-byte luma stores, 4-byte chroma stores (the frame's last, half-filled quad: 4 / 2 bytes,
+// edge strips only).  The chroma average is the table-free cavg_arith (4 vector operations, twice per two rows; no second table in LDS).
+struct PbSinkDst {
+  uint8_t *u[LGPU_CHAIN_MAX_TRACKS], *v[LGPU_CHAIN_MAX_TRACKS];      // 4:2:0: the chroma planes (luma / the packed frame is PbTracks.dst, its rowstride PbHalfArgs.orow)
+  const uint2 *tab;              // device [2][3][256]: {Y, U} then {Y, V} contributions per byte of the chain's result (get_sink_tables)
+  int urow, vrow;
+  int fmt;                       // 2 UYVY, 3 YUYV, 4 YUV420P
+  int unclamped;
+  int pairs;                     // 4:2:0: the (dh - 2) / 2 inner row pairs, dealt evenly to the bands; band 0 adds row 0, the last band row dh - 1
+};
+template <int YUV, int SINK> struct PbExtraArg { typedef PbSinkDst type; };
+template <> struct PbExtraArg<0, 0> { typedef PbYuvArg<0>::type type; };
+template <> struct PbExtraArg<1, 0> { typedef PbYuvArg<1>::type type; };
+template <int SINK> struct PbSinkLds { pb_u2 t[6 * 256]; };
+template <> struct PbSinkLds<0> {};
+
+template <int CHAIN, int HYPER, int BLUR, int ALIGNED = 0, int SWAP = 0, int OPAQUE = 0, int YUV = 0, int SINK = 0>
+__global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTracks T, const Lut8 lut, const typename PbExtraArg<YUV, SINK>::type Y = typename PbExtraArg<YUV, SINK>::type()) {
+  static_assert(!SINK || (CHAIN && !BLUR && !YUV && !OPAQUE && ALIGNED), "the YUV sink: the chain on strips of 64 quads (a quad of lanes = 8 luma bytes on an 8-byte boundary)");
   // the gamma LUT and the blend's alpha scalers.  ONE copy per workgroup, but no workgroup barrier on the frame path: every wave writes the whole of both tables
   // itself (the same bytes) and reads them after its own writes have landed; a slower wave writing the same bytes again changes nothing
   __shared__ __attribute__((aligned(16))) uint8_t s_lut[256];
@@ -404,6 +437,16 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
   // ALIGNED (no blur): strips of 64 quads, no feeder lanes -- a wave's row is 1024 source bytes and 512 result bytes on 128-byte lines; the two taps beyond the
   // strip come from one extra 4-byte load per source row in lanes 0 and 63
   constexpr int kHalo = BLUR ? 2 : ALIGNED ? 0 : 1, kCols = 64 - 2 * kHalo;      // lanes that only feed their neighbours on each side / lanes that store
+  __shared__ PbSinkLds<SINK> s_sink;
+  if constexpr (SINK) {           // the sink's tables: the whole workgroup, before a wave without work leaves (the only workgroup barrier of this form; no letterbox bars in it)
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+      const uint2 e = Y.tab[threadIdx.x + 256 * i];
+      pb_u2 w; w.x = e.x; w.y = e.y;
+      s_sink.t[threadIdx.x + 256 * i] = w;
+    }
+    __syncthreads();
+  }
   if (CHAIN && blockIdx.x < (unsigned)A.bar_first) {
     // letterbox bars (letterbox_layer's black canvas, src/colourspace.c:15417-15503, under the rest of the chain): opaque black -> chroma blend with layer 2 -> LUT
     stage_lut(s_lut, lut);
@@ -477,7 +520,15 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
   const int k = strip * kCols - kHalo + lane;             // this lane's source quad: pixels 4k .. 4k + 3 -> output columns 2k, 2k + 1
   const int kmax = (A.sw >> 2) - 1;
   const int kc = k < 0 ? 0 : k > kmax ? kmax : k;
-  const int y0 = band * A.th + min(band, A.rem), rows = A.th + (band < A.rem ? 1 : 0);
+  int y0_ = band * A.th + min(band, A.rem), rows_ = A.th + (band < A.rem ? 1 : 0);
+  if constexpr (SINK == 2) {      // boundaries at odd rows: row 0 | whole row pairs | row dh - 1
+    // band b owns the inner row pairs [b P / bands, (b + 1) P / bands): heights that differ by one pair ALTERNATE along the frame, so that the runs of neighbouring
+    // bands the XCDs take (PbHalfArgs.bgroup) weigh the same (taller bands first, as PbHalfArgs.rem deals them, gave four XCDs 6-row bands and four 4-row ones)
+    const int p_lo = (int)((uint32_t)(band * Y.pairs) / (uint32_t)A.bands), p_hi = (int)((uint32_t)((band + 1) * Y.pairs) / (uint32_t)A.bands);
+    y0_ = band ? 1 + 2 * p_lo : 0;
+    rows_ = (band == A.bands - 1 ? A.dh : 1 + 2 * p_hi) - y0_;
+  }
+  const int y0 = y0_, rows = rows_;
   const bool out_lane = lane >= kHalo && lane < 64 - kHalo && k <= kmax;
   const bool edge_strip = strip == 0 || (strip + 1) * kCols + kHalo >= kmax;        // wave-uniform: some lanes of this strip lie outside the frame
   // BLUR: a band whose scaled rows (its own and the two above / below) keep clear of the frame's first and last row walks in straight-line code (further down).  There
@@ -499,6 +550,8 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
   const __amdgpu_buffer_rsrc_t r_src = srd(T.src[track], (uint32_t)A.sh * (uint32_t)A.irow);
   const __amdgpu_buffer_rsrc_t r_dst = srd(T.dst[track], (uint32_t)out_rows * (uint32_t)A.orow);
   const __amdgpu_buffer_rsrc_t r_l2 = srd(CHAIN == 1 ? (const void *)T.l2[track] : (const void *)T.src[track], CHAIN == 1 ? (uint32_t)out_rows * (uint32_t)A.irow2 : 16u);
+  __amdgpu_buffer_rsrc_t r_su = r_dst, r_sv = r_dst;
+  if constexpr (SINK == 2) { r_su = srd(Y.u[track], (uint32_t)(A.dh >> 1) * (uint32_t)Y.urow); r_sv = srd(Y.v[track], (uint32_t)(A.dh >> 1) * (uint32_t)Y.vrow); }
   const uint32_t lane_off = fastp ? (k < 0 ? 4u : k > kmax ? 16u * (uint32_t)(kmax + 1) + 12u : 16u * (uint32_t)(k + 1)) : 16u * (uint32_t)kc;
   const int row_adj = __builtin_amdgcn_readfirstlane(fastp ? -16 : 0);      // fastp: the lane offsets are written against 16 bytes before the row
   auto load_row = [&](int sy) -> pb_u4 {
@@ -564,6 +617,63 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
   const int d = (band & 1) ? -1 : 1;
   const int ystart = d > 0 ? ylo : yhi, vstart = d > 0 ? vr0 : vr1;
   const int S0 = d > 0 ? 2 * ylo - 1 : 2 * yhi + 2;           // source rows are consumed in the order S0, S0 + d, S0 + 2 d, ...
+  // the sink's store (SINK): p0, p1 = the lane's two finished pixels of output row y
+  int sk_cu = 0, sk_cv = 0;       // 4:2:0: the clamped U / V of the row pair's first row
+  auto sink_row = [&](int y, uint32_t p0, uint32_t p1) __attribute__((always_inline)) {
+    if constexpr (SINK) {
+      const pb_u2 *tu = s_sink.t, *tv = s_sink.t + 768;
+      const pb_u2 a0 = tu[p0 & 0xFF], b0 = tu[256 + ((p0 >> 8) & 0xFF)], c0 = tu[512 + ((p0 >> 16) & 0xFF)];
+      const pb_u2 a1 = tv[p1 & 0xFF], b1 = tv[256 + ((p1 >> 8) & 0xFF)], c1 = tv[512 + ((p1 >> 16) & 0xFF)];
+      // (int) sum >> 16 IS the reference's short; upper clamp then lower = the median, the bounds being ordered
+      const int min_y = Y.unclamped ? 0 : 16, max_y = Y.unclamped ? 255 : 235, min_uv = min_y, max_uv = Y.unclamped ? 255 : 240;
+      const int ya = (int)(a0.x + b0.x + c0.x) >> 16, yb = (int)(a1.x + b1.x + c1.x) >> 16;
+      const int ur = (int)(a0.y + b0.y + c0.y) >> 16, vr = (int)(a1.y + b1.y + c1.y) >> 16;
+      const uint32_t y0c = (uint32_t)min(max(ya, min_y), max_y), y1c = (uint32_t)min(max(yb, min_y), max_y);
+      y = __builtin_amdgcn_readfirstlane(y);
+      if constexpr (SINK == 1) {
+        // rgb2yuyv lost its `else`: only the lower chroma clamp, then the byte cast (src/colourspace.c:2183-2191)
+        const int ul = max(ur, min_uv), vl = max(vr, min_uv);
+        const uint32_t uu = (uint32_t)(Y.fmt == 3 ? ul : min(ul, max_uv)) & 0xFFu, vv = (uint32_t)(Y.fmt == 3 ? vl : min(vl, max_uv)) & 0xFFu;
+        const uint32_t w = Y.fmt == 3 ? (y0c | (uu << 8) | (y1c << 16) | (vv << 24)) : (uu | (y0c << 8) | (vv << 16) | (y1c << 24));
+        const uint32_t off = out_lane ? 4u * (uint32_t)k : 0xFFFFFFF0u;
+        __builtin_amdgcn_raw_buffer_store_b32(w, r_dst, (int)off, __builtin_amdgcn_readfirstlane(y * A.orow), 2);
+      } else {
+        // quad permutes: [1 1 3 3] -- the even lanes take their right neighbour's value; [2 3 2 3] -- lane 0 of a quad takes lane 2's
+        const bool lead = out_lane && !(k & 3), full = k + 3 <= kmax;      // strips start at multiples of 64 quads: k & 3 == lane & 3
+        const uint32_t yy = y0c | (y1c << 8);
+        const uint32_t t = yy | ((uint32_t)__builtin_amdgcn_mov_dpp((int)yy, 0xF5, 0xF, 0xF, true) << 16);
+        pb_u2 o;
+        o.x = t; o.y = (uint32_t)__builtin_amdgcn_mov_dpp((int)t, 0xEE, 0xF, 0xF, true);
+        const int yo = __builtin_amdgcn_readfirstlane(y * A.orow);
+        __builtin_amdgcn_raw_buffer_store_b64(o, r_dst, (int)(lead && full ? 2u * (uint32_t)k : 0xFFFFFFF0u), yo, 2);
+        if (edge_strip) __builtin_amdgcn_raw_buffer_store_b32(t, r_dst, (int)(lead && !full ? 2u * (uint32_t)k : 0xFFFFFFF0u), yo, 2);      // dw % 8 == 4: the frame's last two pairs
+        if (y != 0) {                                                  // row 0's chroma is never kept
+          const int cl = !Y.unclamped;
+          int cu = min(max(ur, min_uv), max_uv), cv = min(max(vr, min_uv), max_uv);
+          const bool last = y == A.dh - 1;
+          if (!last && (y & 1) == (d > 0 ? 1 : 0)) { sk_cu = cu; sk_cv = cv; }      // the pair's first row on this walk
+          else {
+            if (!last) {                                                // cavg(row 2k + 2, row 2k + 1): the argument order of the reference
+              if (y & 1) { cu = cavg_arith(cl, sk_cu, cu); cv = cavg_arith(cl, sk_cv, cv); }
+              else { cu = cavg_arith(cl, cu, sk_cu); cv = cavg_arith(cl, cv, sk_cv); }
+            }
+            const uint32_t uv = (uint32_t)cu | ((uint32_t)cv << 16);
+            const uint32_t q = uv | ((uint32_t)__builtin_amdgcn_mov_dpp((int)uv, 0xF5, 0xF, 0xF, true) << 8);        // u(k) u(k + 1) v(k) v(k + 1)
+            const uint32_t q2 = (uint32_t)__builtin_amdgcn_mov_dpp((int)q, 0xEE, 0xF, 0xF, true);
+            const int kr = (y - 1) >> 1, uo = __builtin_amdgcn_readfirstlane(kr * Y.urow), vo = __builtin_amdgcn_readfirstlane(kr * Y.vrow);
+            const uint32_t co = lead && full ? (uint32_t)k : 0xFFFFFFF0u;
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_amdgcn_perm(q2, q, 0x05040100u), r_su, (int)co, uo, 2);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_amdgcn_perm(q2, q, 0x07060302u), r_sv, (int)co, vo, 2);
+            if (edge_strip) {
+              const uint32_t ce = lead && !full ? (uint32_t)k : 0xFFFFFFF0u;
+              __builtin_amdgcn_raw_buffer_store_b16((unsigned short)(q & 0xFFFFu), r_su, (int)ce, uo, 2);
+              __builtin_amdgcn_raw_buffer_store_b16((unsigned short)(q >> 16), r_sv, (int)ce, vo, 2);
+            }
+          }
+        }
+      }
+    }
+  };
   if constexpr (YUV) {
     static_assert(CHAIN && OPAQUE && !BLUR && !ALIGNED, "the 4:2:0 source: the chain's all-opaque form, no gaussian, strips with feeder lanes");
     // K2's tables, paired as in k_yuv420p_to_rgb_s: RGB_Y, {R_Cr, G_Cr}[v], {G_Cb, B_Cb}[u] with CLAMP16_240 / the 0..255 clamp folded into the chroma index
@@ -808,6 +918,8 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
       }
       uint32_t cc[2][3], al[2];
       scale_row(ca, cb, cea, ceb, cc, al);
+      if constexpr (SINK) sink_row(yy, finish(cc[0][0], cc[0][1], cc[0][2], al[0], cl2.x), finish(cc[1][0], cc[1][1], cc[1][2], al[1], cl2.y));
+      else
       store_row(yy, finish(cc[0][0], cc[0][1], cc[0][2], al[0], cl2.x), finish(cc[1][0], cc[1][1], cc[1][2], al[1], cl2.y));
     };
     int r = 0;
@@ -2582,6 +2694,143 @@ extern "C" int lgpu_chain_yuv420p(const lgpu_chain_params *pr, const lgpu_yuv_so
     else { if (a.swap_rb) PBY_LAUNCH(1, 0, 1); else PBY_LAUNCH(1, 0, 0); }
   }
 #undef PBY_LAUNCH
+  LGPU_CHECK_LAUNCH();
+  return LGPU_OK;
+}
+
+// the sink's tables (k_pb_half<.., SINK>): rgb2yuv[which_tables] as {Y, U} and {Y, V} contributions per byte POSITION of the chain's result -- in_order 1 (BGRA): byte 0
+// is blue -- one device table per (device, which_tables, in_order).  Like the file's other lazily built tables (get_kscale, pb_table) the FIRST use of a pair does a
+// blocking hipMalloc + hipMemcpy outside `stream` (a stream capture must have met the pair before it begins), and the eight 12 KB tables live until the process ends.
+namespace lgpu { int cavg_forms_checked(); }      // palette.hip: cavg_arith against the table form, all 65,536 pairs, once per device
+static int get_sink_tables(int which_tables, int in_order, const uint2 **out) {
+  static std::mutex mu;
+  static std::map<std::tuple<int, int, int>, uint2 *> tabs;
+  int dev = 0;
+  LGPU_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lk(mu);
+  const auto key = std::make_tuple(dev, which_tables & 3, in_order & 1);
+  auto it = tabs.find(key);
+  if (it == tabs.end()) {
+    std::vector<int32_t> t(9 * 256);
+    int rc = lgpu_conversion_tables(which_tables & 3, t.data(), nullptr);
+    if (rc) return rc;
+    std::vector<uint2> h(6 * 256);
+    for (int c = 0; c < 3; c++) {
+      const int ch = (in_order & 1) ? 2 - c : c;           // the colour in byte c of a finished pixel
+      for (int e = 0; e < 256; e++) {
+        h[c * 256 + e] = make_uint2((uint32_t)t[ch * 256 + e], (uint32_t)t[(3 + ch) * 256 + e]);
+        h[768 + c * 256 + e] = make_uint2((uint32_t)t[ch * 256 + e], (uint32_t)t[(6 + ch) * 256 + e]);
+      }
+    }
+    uint2 *d = nullptr;
+    LGPU_HIP(hipMalloc((void **)&d, h.size() * sizeof(uint2)));
+    if (hipMemcpy(d, h.data(), h.size() * sizeof(uint2), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); set_error("get_sink_tables: upload failed"); return LGPU_E_HIP; }
+    it = tabs.emplace(key, d).first;
+  }
+  *out = it->second;
+  return LGPU_OK;
+}
+
+// lgpu_chain_to_yuv: the 2:1 chain that ENDS at a YUV consumer -- [R <-> B] -> the exact 2:1 scaler [-> chroma blend with layer 2] [-> gamma LUT] -> K4's conversion
+// (lgpu_rgb_to_yuv, every quirk kept) to UYVY / YUYV / YUV420P, one launch for every track; the RGBA result is never written.  Every argument is checked before
+// anything is enqueued.
+extern "C" int lgpu_chain_to_yuv(const lgpu_chain_params *pr, const lgpu_chain_sink *sk, const lgpu_chain_sink_track *tracks, int ntracks, const uint8_t *amounts,
+                                 void *stream) {
+  int rc = ensure_init();
+  if (rc) return rc;
+  LGPU_REQUIRE(pr && sk && tracks && ntracks > 0 && ntracks <= LGPU_CHAIN_MAX_TRACKS, "params, sink and 1..64 tracks required");
+  LGPU_REQUIRE(pr->interp & LGPU_INTERP_PIXBUF, "lgpu_chain_to_yuv serves the gdk-pixbuf arithmetic (LGPU_INTERP_PIXBUF)");
+  const bool noblend = (pr->interp & LGPU_INTERP_NOBLEND) != 0;
+  LGPU_REQUIRE(amounts || noblend, "null amounts");
+  LGPU_REQUIRE(sk->out_fmt >= 2 && sk->out_fmt <= 5, "out_fmt must be 2 (UYVY), 3 (YUYV), 4 (4:2:0 planar) or 5 (4:2:2 planar)");
+  LGPU_REQUIRE(sk->in_order == 0 || sk->in_order == 1, "in_order is 0 (RGBA) or 1 (BGRA)");
+  LGPU_REQUIRE(sk->which_tables >= 0 && sk->which_tables <= 3, "which_tables is 0..3");
+  LGPU_REQUIRE(sk->out_fmt >= 4 || !(sk->which_tables & 2), "only the 4:2:0 / 4:2:2 conversions take a BT.709 subspace (as lgpu_rgb_to_yuv)");
+  LGPU_REQUIRE(pr->sw > 0 && pr->sh > 0 && pr->dw > 0 && pr->dh > 0 && !(pr->dw & 1), "empty geometry or an odd destination width");
+  LGPU_REQUIRE(pr->sw < 32768 && pr->sh < 32768, "frame sides must stay below 32768 (16.16 positions)");
+  const bool planar = sk->out_fmt >= 4;
+  const int nplanes = planar ? 3 : 1, cwid = pr->dw >> 1;
+  LGPU_REQUIRE(pr->irow >= pr->sw * 4 && (noblend || pr->irow2 >= pr->dw * 4), "rowstride smaller than a row");
+  LGPU_REQUIRE(sk->orow[0] >= (planar ? pr->dw : pr->dw * 2) && (!planar || (sk->orow[1] >= cwid && sk->orow[2] >= cwid)), "sink rowstride smaller than a row");
+  LGPU_REQUIRE(((pr->irow | (noblend ? 0 : pr->irow2)) & 3) == 0, "rowstrides must be multiples of 4");
+  uintptr_t sb = (uintptr_t)pr->irow, lb = noblend ? 0 : (uintptr_t)pr->irow2, pb = 0;
+  for (int i = 0; i < ntracks; i++) {
+    const lgpu_chain_sink_track &t = tracks[i];
+    LGPU_REQUIRE(t.src_d && (noblend || t.layer2_d), "null track pointer");
+    for (int k = 0; k < nplanes; k++) { LGPU_REQUIRE(t.dst_d[k], "null destination plane"); LGPU_REQUIRE(t.dst_d[k] != t.src_d, "the chain cannot run in place"); pb |= (uintptr_t)t.dst_d[k]; }
+    LGPU_REQUIRE((((uintptr_t)t.src_d | (uintptr_t)(noblend ? nullptr : t.layer2_d)) & 3) == 0, "frames must be 4-byte aligned");
+    sb |= (uintptr_t)t.src_d; lb |= (uintptr_t)(noblend ? nullptr : t.layer2_d);
+  }
+  // the one-launch form; anything else is refused, never run some other way
+  const int interp = pr->interp & 0xFF;
+  if (pr->do_blur) { set_error("lgpu_chain_to_yuv: the gaussian is not offered with a YUV sink"); return LGPU_E_UNSUPPORTED; }
+  if (sk->out_fmt == 5) { set_error("lgpu_chain_to_yuv: YUV422P is not served (lgpu_chain_amounts + lgpu_rgb_to_yuv_batch)"); return LGPU_E_UNSUPPORTED; }
+  if ((interp != 2 && interp != 3) || pr->sw != 2 * pr->dw || pr->sh != 2 * pr->dh || (pr->dw & 3) || (planar && (pr->dh & 1)) || (sb & 15) || (lb & 7) || (pb & 15) ||
+      (sk->orow[0] & 7) || (planar && ((sk->orow[1] | sk->orow[2]) & 3))) {
+    set_error("lgpu_chain_to_yuv: one launch serves the exact 2:1 reduction (HYPER / BILINEAR, dw %% 4 == 0, dh even for 4:2:0, 16-byte aligned source rows and sink planes, "
+              "8-byte aligned layer-2 rows, luma / packed rowstride %% 8 == 0, chroma rowstrides %% 4 == 0)");
+    return LGPU_E_UNSUPPORTED;
+  }
+  const long long lim = 1ll << 31;
+  if ((long long)pr->sh * pr->irow >= lim || (long long)pr->dh * sk->orow[0] >= lim || (!noblend && (long long)pr->dh * pr->irow2 >= lim)) {
+    set_error("lgpu_chain_to_yuv: planes of 2 GiB or more");
+    return LGPU_E_UNSUPPORTED;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  PbPin pin;
+  if ((rc = pb_table(interp, pr->sw, pr->sh, pr->dw, pr->dh, st, &pin))) return rc;
+  PbHalfArgs a;
+  if (!pb_half_ok(pin.t, interp, pr->sw, pr->sh, pr->dw, pr->dh, sb, lb, &a.hyper, &a.ashift)) {
+    set_error("lgpu_chain_to_yuv: the scaler's table is not the exact 2:1 outer product");
+    return LGPU_E_UNSUPPORTED;
+  }
+  PbSinkDst S;
+  if (planar && (rc = cavg_forms_checked())) return rc;
+  if ((rc = get_sink_tables(sk->which_tables, sk->in_order, &S.tab))) return rc;
+  if ((rc = get_kscale(&a.kscale))) return rc;
+  a.sw = pr->sw; a.sh = pr->sh; a.irow = pr->irow; a.dw = pr->dw; a.dh = pr->dh; a.orow = sk->orow[0];
+  a.swap_rb = pr->swap_rb ? 1 : 0; a.blend = 1; a.irow2 = noblend ? pr->irow : pr->irow2; a.use_lut = pr->use_lut ? 1 : 0;
+  a.bf = 0; a.bf_d = nullptr; a.bf_tracks = amounts ? 1 : 0; a.nt_out = 1;
+  a.row_major = -1; a.bgroup = 0;
+  pb_half_geometry(&a, ntracks);
+  // Launch-shape switches: PBH_TH and PBH_OCC are honoured; PBH_ALIGNED = 0 is OVERRIDDEN (the sink form exists on strips of 64 quads only: a quad of lanes must
+  // start on an 8-byte luma boundary); PBH_ORDER and PBH_GROUP are NOT consulted -- the work order is pb_chain_half's default for the launch's size.  For the 4:2:0
+  // form a.th / a.rem (pb_half_bands) are not what the kernel walks: only a.bands counts, the rows of a band come from PbSinkDst.pairs.
+  if (!a.aligned) { a.aligned = 1; a.strips = (int)cdiv((unsigned)a.dw, 128u); a.cgroups = (a.strips + 3) / 4; }
+  S.pairs = 0;
+  if (planar) {
+    // band boundaries at odd rows: the (dh - 2) / 2 inner row pairs dealt to the bands, row 0 with the first band, row dh - 1 with the last (k_pb_half's comment)
+    const int pairs = (a.dh - 2) / 2;
+    pb_half_bands(&a, std::min(a.bands, std::max(1, pairs)));
+    S.pairs = pairs;
+  }
+  a.row_major = ((long long)a.cgroups * a.bands * ntracks >= (long long)device_cus() * 8 + 1) ? 2 : 1;      // as pb_chain_half
+  a.bgroup = (a.bands % 8 == 0) ? a.bands / 8 : 1;
+  a.cw = a.ch = a.ox = a.oy = 0; a.bar_blocks = 0;
+  a.main_blocks = (int)pb_half_grid(a);
+  a.bar_first = 0;
+  PbTracks T;
+  for (int i = 0; i < ntracks; i++) {
+    T.src[i] = tracks[i].src_d; T.l2[i] = noblend ? tracks[i].src_d : tracks[i].layer2_d; T.dst[i] = tracks[i].dst_d[0]; T.bf[i] = amounts ? amounts[i] : 0;
+    S.u[i] = planar ? tracks[i].dst_d[1] : nullptr; S.v[i] = planar ? tracks[i].dst_d[2] : nullptr;
+  }
+  S.urow = planar ? sk->orow[1] : 0; S.vrow = planar ? sk->orow[2] : 0; S.fmt = sk->out_fmt; S.unclamped = sk->which_tables & 1;
+  const Lut8 l = pack_lut(pr->use_lut ? pr->lut8 : nullptr);
+  const dim3 grid((unsigned)a.main_blocks);
+  // Workgroups per CU: pb_chain_half's five for launches of more than one generation, held by unused DYNAMIC LDS -- less the 12 KB of static LDS the sink's tables
+  // take, so that the count stays what it was (5 x (14.25 KB static + 17 KB dynamic) fits 160 KB, six do not)
+  int occ = ((long long)a.cgroups * a.bands * ntracks > (long long)device_cus() * 8) ? 5 : 0;
+  if (tune(TUNE_PBH_OCC) >= 0) occ = tune(TUNE_PBH_OCC);
+  const size_t per_wg = occ > 0 && occ < 16 ? (size_t)(160 * 1024) / (size_t)occ : 0, held = 3072 + sizeof(PbSinkLds<1>);
+  const size_t occ_lds = per_wg > held ? per_wg - held : 0;
+#define PBS_LAUNCH(CH, HY, SW, SK) hipLaunchKernelGGL((k_pb_half<CH, HY, 0, 1, SW, 0, 0, SK>), grid, dim3(256), occ_lds, st, a, T, l, S)
+#define PBS_SWAP(CH, HY, SK) do { if (a.swap_rb) PBS_LAUNCH(CH, HY, 1, SK); else PBS_LAUNCH(CH, HY, 0, SK); } while (0)
+#define PBS_HYPER(CH, SK) do { if (a.hyper) PBS_SWAP(CH, 1, SK); else PBS_SWAP(CH, 0, SK); } while (0)
+  if (planar) { if (noblend) PBS_HYPER(2, 2); else PBS_HYPER(1, 2); }
+  else { if (noblend) PBS_HYPER(2, 1); else PBS_HYPER(1, 1); }
+#undef PBS_HYPER
+#undef PBS_SWAP
+#undef PBS_LAUNCH
   LGPU_CHECK_LAUNCH();
   return LGPU_OK;
 }

@@ -225,6 +225,20 @@ def rgb_to_yuv(src, dst_planes, width, height, in_order, in_alpha, out_fmt, out_
              out_fmt, int(out_alpha), which_tables, stream_ptr())
 
 
+def rgb_to_yuv_batch(srcs, dst_planes, width, height, in_order, in_alpha, out_fmt, out_alpha, which_tables):
+    """lgpu_rgb_to_yuv_batch: K4 on up to 16 frames of one geometry in one launch; srcs: 2-D uint8 device tensors, dst_planes: a list of plane tensors per frame
+    (strides are taken from frame 0)"""
+    n = len(srcs)
+    sp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in srcs])
+    dp = (ctypes.c_void_p * (4 * n))()
+    for f in range(n):
+        for k, t in enumerate(dst_planes[f]):
+            dp[4 * f + k] = t.data_ptr()
+    ds = (ctypes.c_int * 4)(*([t.stride(0) for t in dst_planes[0]] + [0] * (4 - len(dst_planes[0]))))
+    lib.call("lgpu_rgb_to_yuv_batch", ctypes.addressof(sp), srcs[0].stride(0), width, height, in_order, int(in_alpha), ctypes.addressof(dp), ctypes.addressof(ds),
+             out_fmt, int(out_alpha), which_tables, n, stream_ptr())
+
+
 def rgb_to_yuv_lut16(src, dst, width, height, in_order, in_alpha, out_fmt, unclamped, lut16):
     """K4 with the 16-bit gamma LUT inline (UYVY / YUYV only); lut16: device tensor of 65536 16-bit entries"""
     assert lut16.is_cuda and lut16.numel() == 65536 and lut16.element_size() == 2
@@ -419,6 +433,37 @@ def chain_yuv420p(params, src, tracks, amounts, canvas=None, check=True):
     if not check:
         return lib.load().lgpu_chain_yuv420p(*args)
     return lib.call("lgpu_chain_yuv420p", *args)
+
+
+def chain_sink(out_fmt, orow, which_tables=0, in_order=0):
+    """lgpu_chain_sink: out_fmt 2 UYVY / 3 YUYV / 4 YUV420P, orow = the rowstrides of the sink's planes (one or three)"""
+    s = lib.ChainSink()
+    s.out_fmt, s.which_tables, s.in_order = out_fmt, which_tables, in_order
+    for k, v in enumerate(orow):
+        s.orow[k] = int(v)
+    return s
+
+
+def chain_sink_tracks(srcs, layer2s, dst_planes):
+    """lgpu_chain_sink_track[]: source, layer 2 (None: LGPU_INTERP_NOBLEND) and the sink's planes of each track (one tensor for UYVY / YUYV; Y, U, V for YUV420P --
+    pass the chroma planes swapped for YVU420P)"""
+    n = len(srcs)
+    arr = (lib.ChainSinkTrack * n)()
+    for i in range(n):
+        arr[i].src_d, arr[i].layer2_d = srcs[i].data_ptr(), (layer2s[i].data_ptr() if layer2s is not None else None)
+        for k, t in enumerate(dst_planes[i]):
+            arr[i].dst_d[k] = t.data_ptr()
+    return arr
+
+
+def chain_to_yuv(params, sink, tracks, amounts, check=True):
+    """lgpu_chain_to_yuv: the chain of lgpu_chain_amounts ending at a YUV sink, one launch and no RGBA frame.  check=False returns the library's code instead of
+    raising (tests of the refusals)"""
+    am = (ctypes.c_uint8 * max(1, len(tracks)))(*[int(a) & 0xFF for a in amounts]) if amounts is not None else None      # None: with LGPU_INTERP_NOBLEND (0x400) in params.interp
+    args = (ctypes.byref(params), ctypes.byref(sink), tracks, len(tracks), am, stream_ptr())
+    if not check:
+        return lib.load().lgpu_chain_to_yuv(*args)
+    return lib.call("lgpu_chain_to_yuv", *args)
 
 
 def stream_probe(params, tracks, reps):
