@@ -448,14 +448,31 @@ int lgpu_chain_yuv420p(const lgpu_chain_params *params, const lgpu_yuv_source *s
    outside 2..5, in_order > 1, BT.709 with UYVY / YUYV, an odd dw, strides below a row's bytes, no PIXBUF, null amounts with a blend).  Only the one-launch form is
    served: exact 2:1 (sw == 2 dw, sh == 2 dh), HYPER or BILINEAR, dw % 4 == 0, dh even for 4:2:0 (any dh for UYVY / YUYV), sink->orow[0] % 8 == 0 and chroma
    rowstrides % 4 == 0, sink planes and source rows 16-byte aligned, layer-2 rows 8-byte aligned, no gaussian.  LGPU_E_UNSUPPORTED otherwise -- this includes, for now,
-   out_fmt 5 (YUV422P), an odd dh with 4:2:0, a letterbox canvas (the entry point takes none: chroma rows would straddle the bar / frame edge) and a YUV420P SOURCE
-   combined with the sink; run lgpu_chain_amounts + lgpu_rgb_to_yuv_batch then.  Nothing is written in either case.  The first call with a new (which_tables, in_order)
+   out_fmt 5 (YUV422P), an odd dh with 4:2:0 and a letterbox canvas (the entry point takes none: chroma rows would straddle the bar / frame edge); run
+   lgpu_chain_amounts + lgpu_rgb_to_yuv_batch then.  A YUV420P SOURCE in front of the sink is lgpu_chain_yuv420p_to_yuv below.  Nothing is written in either case.  The first call with a new (which_tables, in_order)
    pair builds a 12 KB device table with a blocking allocation and copy outside `stream` (as the first chain call of a geometry does): make that call before a stream
    capture begins.  The tables are kept until the process ends. */
 typedef struct { int out_fmt; int which_tables; int in_order; int orow[3]; } lgpu_chain_sink;
 typedef struct { const uint8_t *src_d, *layer2_d; uint8_t *dst_d[3]; } lgpu_chain_sink_track;
 int lgpu_chain_to_yuv(const lgpu_chain_params *params, const lgpu_chain_sink *sink, const lgpu_chain_sink_track *tracks, int ntracks, const uint8_t *amounts,
                       void *stream);
+/* both ends at once -- a tick from decoded planar 4:2:0 frames to a YUV consumer: the K2 conversion -> [R <-> B] -> scale [-> chroma blend] [-> gamma LUT] -> the K4
+   conversion, and neither RGBA frame is ever written.  The bytes are those of lgpu_yuv420p_to_rgb (src's out_order, which_tables, pb_quality, flags), then
+   lgpu_chain_amounts (PIXBUF, optional NOBLEND, LUT), then lgpu_rgb_to_yuv(.., sink->in_order, 1, .., sink->out_fmt, 0, sink->which_tables).  src is read as by
+   lgpu_chain_yuv420p, sink as by lgpu_chain_to_yuv (params->irow and params->orow are ignored in favour of src->istrides and sink->orow); the two table choices are
+   independent; YVU420P on either end: pass the planes swapped.  sink->in_order states the byte order of the chain's result, which is src->out_order ^
+   params->swap_rb: anything else is LGPU_E_BADARG, like every argument either parent refuses (null planes, 0 or 65 tracks, table / format / quality numbers out of
+   range, unknown flags, BT.709 with UYVY / YUYV, odd sw or dw, strides or chroma planes too small, no PIXBUF, null amounts with a blend) and a destination plane
+   that is one of the track's source planes.  Only the one-launch form is served: exact 2:1 (sw == 2 dw, sh == 2 dh), HYPER or BILINEAR, dw % 4 == 0 (so sw % 8 == 0),
+   dh even for 4:2:0, sink->orow[0] % 8 == 0 and chroma rowstrides % 4 == 0, sink planes 16-byte aligned, layer-2 rows 8-byte aligned, no gaussian, no canvas (the
+   signature takes none), no YUV422P.  LGPU_E_UNSUPPORTED otherwise: run lgpu_chain_yuv420p + lgpu_rgb_to_yuv_batch then.  Nothing is written in either case.  Up to
+   32 tracks go as one launch, 33..64 as two on `stream` (the kernel's arguments: four chroma pointers per track).  As in lgpu_chain_to_yuv, the first call with a
+   new (sink->which_tables, sink->in_order) pair builds a 12 KB device table with a blocking allocation and copy outside `stream`: make that call before a stream
+   capture begins. */
+#define LGPU_CHAIN_TRANSCODE_TRACKS 32   /* tracks per launch of lgpu_chain_yuv420p_to_yuv */
+typedef struct { const uint8_t *y_d, *u_d, *v_d; const uint8_t *layer2_d; uint8_t *dst_d[3]; } lgpu_chain_yuv_sink_track;
+int lgpu_chain_yuv420p_to_yuv(const lgpu_chain_params *params, const lgpu_yuv_source *src, const lgpu_chain_sink *sink, const lgpu_chain_yuv_sink_track *tracks,
+                              int ntracks, const uint8_t *amounts, void *stream);
 
 /* ---- timing helper: HIP events on `stream` around `reps` launches of the last-configured chain; used by
    bench.py to measure the kernel's average launch duration on the stream it is launched on. */

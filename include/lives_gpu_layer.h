@@ -170,8 +170,10 @@ void lives_gpu_deferred_stats(unsigned long long out[4]);
 /* the four counters above, then [4] YUV420P / YVU420P -> RGBA32 / BGRA32 conversions recorded (convert_layer_palette on a pinned layer, no gamma change), [5] one-launch
    YUV chain launches (lgpu_chain_yuv420p) and [6] the tracks they carried, [7] conversion pre-launches of the two-launch path (lgpu_yuv420p_to_rgb_batch for a group whose
    shape the one-launch form does not take), [8] sink conversions recorded (LZ_SINK), [9] sink launches -- a lgpu_chain_to_yuv launch (also counted in [1]) or one
-   lgpu_rgb_to_yuv_batch / lgpu_rgb_to_yuv -- and [10] the tracks they carried, [11] how many of [9] were fused lgpu_chain_to_yuv launches; at most n entries are
-   written */
+   lgpu_rgb_to_yuv_batch / lgpu_rgb_to_yuv -- and [10] the tracks they carried, [11] how many of [9] were fused launches, [12] launches that ran from YUV planes to
+   YUV planes (lgpu_chain_yuv420p_to_yuv: a group of programs that start at a YUV420P / YVU420P conversion, have the exact 2:1 scale, no canvas and end in the sink;
+   each is also counted in [1], [5], [9] and [11] with its tracks in [2], [6] and [10], and makes no pre-launch [7]); at most n entries are written (callers that pass
+   n = 12 see what they saw before) */
 void lives_gpu_deferred_stats_n(unsigned long long *out, int n);
 /* (for livesgpu_fx.so) record an in-place "chroma blend" of the pending plane dst_host with the resident plane layer2_host; 1 = recorded, 0 = run the kernel */
 int lives_gpu_deferred_blend_chroma(const void *dst_host, int orow, int width, int height, int palette, const void *layer2_host, int irow2, int bf);

@@ -616,6 +616,7 @@ std::atomic<int> g_deferred{1};
 std::atomic<unsigned long long> g_lz_recorded{0}, g_lz_chain_launches{0}, g_lz_chain_tracks{0}, g_lz_staged{0};      // lives_gpu_deferred_stats
 std::atomic<unsigned long long> g_lz_yuv_recorded{0}, g_lz_yuv_launches{0}, g_lz_yuv_tracks{0}, g_lz_yuv_pre{0};        // lives_gpu_deferred_stats_n [4..7]
 std::atomic<unsigned long long> g_lz_sink_recorded{0}, g_lz_sink_launches{0}, g_lz_sink_tracks{0}, g_lz_sink_fused{0};    // lives_gpu_deferred_stats_n [8..11]
+std::atomic<unsigned long long> g_lz_transcode{0};                                                                          // lives_gpu_deferred_stats_n [12]
 std::mutex g_lazy_mu;               // one program (group) runs at a time; never taken with a table lock held
 bool lazy_pal(int pal) { return pal == WEED_PALETTE_RGBA32 || pal == WEED_PALETTE_BGRA32; }
 
@@ -843,6 +844,47 @@ int lazy_run_sink(Lazy *const *zs, int n, Dev (*souts)[3]) {
     for (int p = 0; p < z0->snp && !rc; p++)
       if (z0->sors[p] != row_bytes[p]) rc = lgpu_fill(souts[i][p].d, 0, z0->sbytes[p], S());      // the row padding of a fresh plane is zero (calloc in the eager path)
   if (rc) return rc;
+  // Which sink formats (2 UYVY, 3 YUYV, 4 4:2:0) a group that starts at YUV planes takes as ONE lgpu_chain_yuv420p_to_yuv launch: those for which
+  // tools/bench_transcode_chain.py shows the launch ahead of lgpu_chain_yuv420p + lgpu_rgb_to_yuv_batch by more than the round-to-round spread of the latter.
+  // profiles/r09/transcode_chain.md (16 x 4K -> 1080p, blend + LUT, five interleaved rounds): to UYVY 214.3 us against 244.7 for the two launches (spread 0.2 us) --
+  // taken, and YUYV with it (the same instantiation); to YUV420P 258.9 us against 243.4 (spread 1.9 us) -- the 4:2:0 form's 98-105 registers hold it to four waves per
+  // SIMD -- so 4:2:0 keeps today's two launches.
+  const bool transcode_fused = z0->sfmt == 2 || z0->sfmt == 3;
+  if (transcode_fused && !staged && z0->yuv && z0->scale && !z0->canvas && z0->sww == z0->w && z0->shh == z0->h && n <= LGPU_CHAIN_MAX_TRACKS) {
+    // from YUV planes to YUV planes: ONE launch, neither RGBA frame exists.  The source planes are awaited as in lazy_run_rgba; lazy_run_group gives them back with
+    // their reader streams kept.
+    for (int i = 0; i < n; i++) { await(zs[i]->src, false); await(zs[i]->yu, false); await(zs[i]->yv, false); if (zs[i]->blend) await(zs[i]->l2, false); }
+    lgpu_chain_params pr;
+    memset(&pr, 0, sizeof pr);
+    pr.sw = z0->sw; pr.sh = z0->sh; pr.irow = z0->ystr[0]; pr.dw = z0->dw; pr.dh = z0->dh; pr.irow2 = z0->blend ? z0->l2rs : 0; pr.orow = 0;
+    pr.swap_rb = z0->swap ? 1 : 0; pr.interp = z0->interp | LGPU_INTERP_PIXBUF | (z0->blend ? 0 : LGPU_INTERP_NOBLEND); pr.use_lut = z0->lut ? 1 : 0;
+    if (z0->lut) memcpy(pr.lut8, z0->lut8, 256);
+    lgpu_yuv_source ys;
+    memset(&ys, 0, sizeof ys);
+    ys.istrides[0] = z0->ystr[0]; ys.istrides[1] = z0->ystr[1]; ys.istrides[2] = z0->ystr[2]; ys.u_size = z0->usz; ys.v_size = z0->vsz;
+    ys.out_order = z0->order; ys.which_tables = z0->which; ys.pb_quality = z0->quality; ys.flags = 0;
+    lgpu_chain_sink sk;
+    memset(&sk, 0, sizeof sk);
+    sk.out_fmt = z0->sfmt; sk.which_tables = z0->swhich; sk.in_order = z0->sorder;
+    for (int p = 0; p < z0->snp; p++) sk.orow[p] = z0->sors[p];
+    std::vector<lgpu_chain_yuv_sink_track> tr((size_t)n);
+    std::vector<uint8_t> amounts((size_t)n);
+    for (int i = 0; i < n; i++) {
+      memset(&tr[(size_t)i], 0, sizeof tr[0]);
+      tr[(size_t)i].y_d = (const uint8_t *)zs[i]->src.d; tr[(size_t)i].u_d = (const uint8_t *)zs[i]->yu.d; tr[(size_t)i].v_d = (const uint8_t *)zs[i]->yv.d;
+      tr[(size_t)i].layer2_d = (const uint8_t *)zs[i]->l2.d;
+      for (int p = 0; p < z0->snp; p++) tr[(size_t)i].dst_d[p] = (uint8_t *)souts[i][p].d;
+      amounts[(size_t)i] = (uint8_t)zs[i]->bf;
+    }
+    const int crc = lgpu_chain_yuv420p_to_yuv(&pr, &ys, &sk, tr.data(), n, z0->blend ? amounts.data() : nullptr, S());
+    if (crc == LGPU_OK) {
+      const unsigned long long nl = (unsigned long long)((n + LGPU_CHAIN_TRANSCODE_TRACKS - 1) / LGPU_CHAIN_TRANSCODE_TRACKS);      // the call's launches
+      g_lz_chain_launches += nl; g_lz_chain_tracks += (unsigned long long)n; g_lz_yuv_launches += nl; g_lz_yuv_tracks += (unsigned long long)n;
+      g_lz_sink_launches += nl; g_lz_sink_tracks += (unsigned long long)n; g_lz_sink_fused += nl; g_lz_transcode += nl;
+      return LGPU_OK;
+    }
+    if (crc != LGPU_E_BADARG && crc != LGPU_E_UNSUPPORTED) return crc;            // a shape outside the one-launch form takes today's launches below
+  }
   if (!staged && z0->scale && !z0->canvas && !z0->yuv && z0->sww == z0->w && z0->shh == z0->h && n <= LGPU_CHAIN_MAX_TRACKS) {
     for (int i = 0; i < n; i++) { await(zs[i]->src, false); if (zs[i]->blend) await(zs[i]->l2, false); }
     lgpu_chain_params pr;
@@ -2215,13 +2257,15 @@ void lives_gpu_deferred_stats(unsigned long long out[4]) {
 // the same counters, then [4] YUV420P / YVU420P conversions recorded, [5] one-launch YUV chain launches (lgpu_chain_yuv420p) and [6] the tracks they carried,
 // [7] conversion pre-launches of the two-launch path (lgpu_yuv420p_to_rgb_batch), [8] sink conversions recorded (LZ_SINK), [9] sink launches (a fused
 // lgpu_chain_to_yuv launch, also counted in [1], or one lgpu_rgb_to_yuv_batch / lgpu_rgb_to_yuv) and [10] the tracks they carried, [11] those of [9] that were fused lgpu_chain_to_yuv launches (the others converted an
-// RGBA frame); at most n entries are written
+// RGBA frame), [12] launches that ran from YUV planes to YUV planes (lgpu_chain_yuv420p_to_yuv; each is also counted in [1], [5], [9] and [11]); at most n entries
+// are written
 void lives_gpu_deferred_stats_n(unsigned long long *out, int n) {
   if (!out || n <= 0) return;
-  const unsigned long long v[12] = {g_lz_recorded.load(), g_lz_chain_launches.load(), g_lz_chain_tracks.load(), g_lz_staged.load(),
+  const unsigned long long v[13] = {g_lz_recorded.load(), g_lz_chain_launches.load(), g_lz_chain_tracks.load(), g_lz_staged.load(),
                                     g_lz_yuv_recorded.load(), g_lz_yuv_launches.load(), g_lz_yuv_tracks.load(), g_lz_yuv_pre.load(),
-                                    g_lz_sink_recorded.load(), g_lz_sink_launches.load(), g_lz_sink_tracks.load(), g_lz_sink_fused.load()};
-  for (int i = 0; i < n && i < 12; i++) out[i] = v[i];
+                                    g_lz_sink_recorded.load(), g_lz_sink_launches.load(), g_lz_sink_tracks.load(), g_lz_sink_fused.load(),
+                                    g_lz_transcode.load()};
+  for (int i = 0; i < n && i < 13; i++) out[i] = v[i];
 }
 // Run the pending programs of these layers now, on the calling thread's stream: programs of equal shape (the tracks of one plan step) share ONE launch of the
 // fused chain kernel.  The layers stay pinned, nothing is downloaded, the host does not wait.  What a host calls once per tick when the plan steps of its tracks

@@ -384,13 +384,14 @@ __device__ __forceinline__ void pb_half_colours(uint32_t v0, uint32_t v1, uint32
 // YUV (lgpu_chain_yuv420p): the source is a planar 4:2:0 frame -- luma planes as PbTracks.src, chroma planes in PbYuvSrc -- converted in registers as K2 converts
 // it (yuv.hip, quirks K2-a..e), row pair by row pair, straight into the all-opaque scaler: no RGBA frame is ever written.  Every converted pixel has alpha 255, so
 // OPAQUE is exact.  SWAP then means "the converted frame is BGRA" (the output order with the chain's R <-> B swap folded in).
-struct PbYuvSrc {
-  const uint8_t *u[LGPU_CHAIN_MAX_TRACKS], *v[LGPU_CHAIN_MAX_TRACKS];
+template <int NT> struct PbYuvSrcT {     // NT: track capacity (the form with both a 4:2:0 source and a sink carries fewer, see PbYuvSink)
+  const uint8_t *u[NT], *v[NT];
   const int32_t *tables;         // device [5][256] RGB_Y R_Cr G_Cb G_Cr B_Cb (lgpu_conversion_tables of which_tables)
   int us, vs;                    // chroma rowstrides
   uint32_t usize, vsize;         // chroma plane bytes: every sample inside; K2's read one past the last row's end is clamped to the last byte
   int clamped, lowq, fix_edges;  // CLAMP16_240 on the chroma index / pb_quality LOW / LGPU_YUV_FIX_EDGES
 };
+typedef PbYuvSrcT<LGPU_CHAIN_MAX_TRACKS> PbYuvSrc;
 struct PbNoYuv {};
 template <int YUV> struct PbYuvArg { typedef PbNoYuv type; };
 template <> struct PbYuvArg<1> { typedef PbYuvSrc type; };
@@ -413,15 +414,27 @@ template <> struct PbYuvArg<1> { typedef PbYuvSrc type; };
 // Stores: a lane has 2 luma bytes per row and 1 + 1 chroma bytes per row pair; short and byte stores cost 12x / 25x a 16-byte store per byte, so a quad of lanes
 // collects its bytes in its first lane over two DPP quad permutes -- 8-byte luma stores, 4-byte chroma stores (the frame's last, half-filled quad: 4 / 2 bytes,
 // edge strips only).  The chroma average is the table-free cavg_arith (4 vector operations, twice per two rows; no second table in LDS).
-struct PbSinkDst {
-  uint8_t *u[LGPU_CHAIN_MAX_TRACKS], *v[LGPU_CHAIN_MAX_TRACKS];      // 4:2:0: the chroma planes (luma / the packed frame is PbTracks.dst, its rowstride PbHalfArgs.orow)
+template <int NT> struct PbSinkDstT {
+  uint8_t *u[NT], *v[NT];      // 4:2:0: the chroma planes (luma / the packed frame is PbTracks.dst, its rowstride PbHalfArgs.orow)
   const uint2 *tab;              // device [2][3][256]: {Y, U} then {Y, V} contributions per byte of the chain's result (get_sink_tables)
   int urow, vrow;
   int fmt;                       // 2 UYVY, 3 YUYV, 4 YUV420P
   int unclamped;
   int pairs;                     // 4:2:0: the (dh - 2) / 2 inner row pairs, dealt evenly to the bands; band 0 adds row 0, the last band row dh - 1
 };
+typedef PbSinkDstT<LGPU_CHAIN_MAX_TRACKS> PbSinkDst;
+// YUV + SINK (lgpu_chain_yuv420p_to_yuv): both ends at once.  Four chroma pointer arrays of 64 tracks beside PbTracks, Lut8 and PbHalfArgs come to 4120 bytes of kernel
+// arguments, over HIP's documented 4 KB for a __global__ function's arguments; this form therefore carries kPbTranscodeTracks tracks per launch (3096 bytes) and the
+// entry point splits a longer tick into launches of that many.
+constexpr int kPbTranscodeTracks = LGPU_CHAIN_TRANSCODE_TRACKS;
+struct PbYuvSink { PbYuvSrcT<kPbTranscodeTracks> y; PbSinkDstT<kPbTranscodeTracks> s; };
+template <class E> __device__ __forceinline__ const E &pb_ysrc(const E &e) { return e; }
+template <class E> __device__ __forceinline__ const E &pb_sink(const E &e) { return e; }
+__device__ __forceinline__ const PbYuvSrcT<kPbTranscodeTracks> &pb_ysrc(const PbYuvSink &e) { return e.y; }
+__device__ __forceinline__ const PbSinkDstT<kPbTranscodeTracks> &pb_sink(const PbYuvSink &e) { return e.s; }
 template <int YUV, int SINK> struct PbExtraArg { typedef PbSinkDst type; };
+template <> struct PbExtraArg<1, 1> { typedef PbYuvSink type; };
+template <> struct PbExtraArg<1, 2> { typedef PbYuvSink type; };
 template <> struct PbExtraArg<0, 0> { typedef PbYuvArg<0>::type type; };
 template <> struct PbExtraArg<1, 0> { typedef PbYuvArg<1>::type type; };
 template <int SINK> struct PbSinkLds { pb_u2 t[6 * 256]; };
@@ -429,19 +442,24 @@ template <> struct PbSinkLds<0> {};
 
 template <int CHAIN, int HYPER, int BLUR, int ALIGNED = 0, int SWAP = 0, int OPAQUE = 0, int YUV = 0, int SINK = 0>
 __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTracks T, const Lut8 lut, const typename PbExtraArg<YUV, SINK>::type Y = typename PbExtraArg<YUV, SINK>::type()) {
-  static_assert(!SINK || (CHAIN && !BLUR && !YUV && !OPAQUE && ALIGNED), "the YUV sink: the chain on strips of 64 quads (a quad of lanes = 8 luma bytes on an 8-byte boundary)");
+  static_assert(!SINK || (CHAIN && !BLUR && (YUV ? OPAQUE && !ALIGNED : !OPAQUE && ALIGNED)),
+                "the YUV sink: the chain on strips of 64 quads (a quad of lanes = 8 luma bytes on an 8-byte boundary), or behind the 4:2:0 source on its strips with feeder lanes");
+  const auto &YS = pb_ysrc(Y);
+  const auto &SK = pb_sink(Y);
   // the gamma LUT and the blend's alpha scalers.  ONE copy per workgroup, but no workgroup barrier on the frame path: every wave writes the whole of both tables
   // itself (the same bytes) and reads them after its own writes have landed; a slower wave writing the same bytes again changes nothing
   __shared__ __attribute__((aligned(16))) uint8_t s_lut[256];
   __shared__ pb_u2 s_k[256];
   // ALIGNED (no blur): strips of 64 quads, no feeder lanes -- a wave's row is 1024 source bytes and 512 result bytes on 128-byte lines; the two taps beyond the
   // strip come from one extra 4-byte load per source row in lanes 0 and 63
-  constexpr int kHalo = BLUR ? 2 : ALIGNED ? 0 : 1, kCols = 64 - 2 * kHalo;      // lanes that only feed their neighbours on each side / lanes that store
+  // YUV with the 4:2:0 sink: 60 storing lanes (1 .. 60; lane 61 feeds, 62 and 63 idle), so that a strip starts at a multiple of four quads and every wave owns whole
+  // luma octets / chroma quads -- see sink_row
+  constexpr int kHalo = BLUR ? 2 : ALIGNED ? 0 : 1, kCols = (YUV && SINK == 2) ? 60 : 64 - 2 * kHalo;      // lanes that only feed their neighbours on each side / lanes that store
   __shared__ PbSinkLds<SINK> s_sink;
   if constexpr (SINK) {           // the sink's tables: the whole workgroup, before a wave without work leaves (the only workgroup barrier of this form; no letterbox bars in it)
 #pragma unroll
     for (int i = 0; i < 6; i++) {
-      const uint2 e = Y.tab[threadIdx.x + 256 * i];
+      const uint2 e = SK.tab[threadIdx.x + 256 * i];
       pb_u2 w; w.x = e.x; w.y = e.y;
       s_sink.t[threadIdx.x + 256 * i] = w;
     }
@@ -524,12 +542,12 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
   if constexpr (SINK == 2) {      // boundaries at odd rows: row 0 | whole row pairs | row dh - 1
     // band b owns the inner row pairs [b P / bands, (b + 1) P / bands): heights that differ by one pair ALTERNATE along the frame, so that the runs of neighbouring
     // bands the XCDs take (PbHalfArgs.bgroup) weigh the same (taller bands first, as PbHalfArgs.rem deals them, gave four XCDs 6-row bands and four 4-row ones)
-    const int p_lo = (int)((uint32_t)(band * Y.pairs) / (uint32_t)A.bands), p_hi = (int)((uint32_t)((band + 1) * Y.pairs) / (uint32_t)A.bands);
+    const int p_lo = (int)((uint32_t)(band * SK.pairs) / (uint32_t)A.bands), p_hi = (int)((uint32_t)((band + 1) * SK.pairs) / (uint32_t)A.bands);
     y0_ = band ? 1 + 2 * p_lo : 0;
     rows_ = (band == A.bands - 1 ? A.dh : 1 + 2 * p_hi) - y0_;
   }
   const int y0 = y0_, rows = rows_;
-  const bool out_lane = lane >= kHalo && lane < 64 - kHalo && k <= kmax;
+  const bool out_lane = lane >= kHalo && lane < kHalo + kCols && k <= kmax;
   const bool edge_strip = strip == 0 || (strip + 1) * kCols + kHalo >= kmax;        // wave-uniform: some lanes of this strip lie outside the frame
   // BLUR: a band whose scaled rows (its own and the two above / below) keep clear of the frame's first and last row walks in straight-line code (further down).  There
   // every source row index lies in [1, sh - 2], and the lanes outside the frame read the ONE pixel their neighbour wants from them where it lies -- the lane left of
@@ -551,7 +569,7 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
   const __amdgpu_buffer_rsrc_t r_dst = srd(T.dst[track], (uint32_t)out_rows * (uint32_t)A.orow);
   const __amdgpu_buffer_rsrc_t r_l2 = srd(CHAIN == 1 ? (const void *)T.l2[track] : (const void *)T.src[track], CHAIN == 1 ? (uint32_t)out_rows * (uint32_t)A.irow2 : 16u);
   __amdgpu_buffer_rsrc_t r_su = r_dst, r_sv = r_dst;
-  if constexpr (SINK == 2) { r_su = srd(Y.u[track], (uint32_t)(A.dh >> 1) * (uint32_t)Y.urow); r_sv = srd(Y.v[track], (uint32_t)(A.dh >> 1) * (uint32_t)Y.vrow); }
+  if constexpr (SINK == 2) { r_su = srd(SK.u[track], (uint32_t)(A.dh >> 1) * (uint32_t)SK.urow); r_sv = srd(SK.v[track], (uint32_t)(A.dh >> 1) * (uint32_t)SK.vrow); }
   const uint32_t lane_off = fastp ? (k < 0 ? 4u : k > kmax ? 16u * (uint32_t)(kmax + 1) + 12u : 16u * (uint32_t)(k + 1)) : 16u * (uint32_t)kc;
   const int row_adj = __builtin_amdgcn_readfirstlane(fastp ? -16 : 0);      // fastp: the lane offsets are written against 16 bytes before the row
   auto load_row = [&](int sy) -> pb_u4 {
@@ -625,7 +643,7 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
       const pb_u2 a0 = tu[p0 & 0xFF], b0 = tu[256 + ((p0 >> 8) & 0xFF)], c0 = tu[512 + ((p0 >> 16) & 0xFF)];
       const pb_u2 a1 = tv[p1 & 0xFF], b1 = tv[256 + ((p1 >> 8) & 0xFF)], c1 = tv[512 + ((p1 >> 16) & 0xFF)];
       // (int) sum >> 16 IS the reference's short; upper clamp then lower = the median, the bounds being ordered
-      const int min_y = Y.unclamped ? 0 : 16, max_y = Y.unclamped ? 255 : 235, min_uv = min_y, max_uv = Y.unclamped ? 255 : 240;
+      const int min_y = SK.unclamped ? 0 : 16, max_y = SK.unclamped ? 255 : 235, min_uv = min_y, max_uv = SK.unclamped ? 255 : 240;
       const int ya = (int)(a0.x + b0.x + c0.x) >> 16, yb = (int)(a1.x + b1.x + c1.x) >> 16;
       const int ur = (int)(a0.y + b0.y + c0.y) >> 16, vr = (int)(a1.y + b1.y + c1.y) >> 16;
       const uint32_t y0c = (uint32_t)min(max(ya, min_y), max_y), y1c = (uint32_t)min(max(yb, min_y), max_y);
@@ -633,22 +651,25 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
       if constexpr (SINK == 1) {
         // rgb2yuyv lost its `else`: only the lower chroma clamp, then the byte cast (src/colourspace.c:2183-2191)
         const int ul = max(ur, min_uv), vl = max(vr, min_uv);
-        const uint32_t uu = (uint32_t)(Y.fmt == 3 ? ul : min(ul, max_uv)) & 0xFFu, vv = (uint32_t)(Y.fmt == 3 ? vl : min(vl, max_uv)) & 0xFFu;
-        const uint32_t w = Y.fmt == 3 ? (y0c | (uu << 8) | (y1c << 16) | (vv << 24)) : (uu | (y0c << 8) | (vv << 16) | (y1c << 24));
+        const uint32_t uu = (uint32_t)(SK.fmt == 3 ? ul : min(ul, max_uv)) & 0xFFu, vv = (uint32_t)(SK.fmt == 3 ? vl : min(vl, max_uv)) & 0xFFu;
+        const uint32_t w = SK.fmt == 3 ? (y0c | (uu << 8) | (y1c << 16) | (vv << 24)) : (uu | (y0c << 8) | (vv << 16) | (y1c << 24));
         const uint32_t off = out_lane ? 4u * (uint32_t)k : 0xFFFFFFF0u;
         __builtin_amdgcn_raw_buffer_store_b32(w, r_dst, (int)off, __builtin_amdgcn_readfirstlane(y * A.orow), 2);
       } else {
         // quad permutes: [1 1 3 3] -- the even lanes take their right neighbour's value; [2 3 2 3] -- lane 0 of a quad takes lane 2's
-        const bool lead = out_lane && !(k & 3), full = k + 3 <= kmax;      // strips start at multiples of 64 quads: k & 3 == lane & 3
+        const bool lead = out_lane && !(k & 3), full = k + 3 <= kmax;      // strips start at multiples of 64 (YUV: 60) quads: a quad of k is a run of four lanes
         const uint32_t yy = y0c | (y1c << 8);
-        const uint32_t t = yy | ((uint32_t)__builtin_amdgcn_mov_dpp((int)yy, 0xF5, 0xF, 0xF, true) << 16);
+        // behind the 4:2:0 source (strips of 60 quads from lane 1 on) k & 3 == (lane - 1) & 3: the lead lane takes its right neighbour over wave_shl:1 and the lane two
+        // to its right over row_shl:2 (a lead lane is lane 1, 5, 9 or 13 of its row of 16, so lane + 2 lies in the same row); lanes <= 63 of this wave only
+        constexpr int kNext = YUV ? 0x130 : 0xF5, kNext2 = YUV ? 0x102 : 0xEE;
+        const uint32_t t = yy | ((uint32_t)__builtin_amdgcn_mov_dpp((int)yy, kNext, 0xF, 0xF, true) << 16);
         pb_u2 o;
-        o.x = t; o.y = (uint32_t)__builtin_amdgcn_mov_dpp((int)t, 0xEE, 0xF, 0xF, true);
+        o.x = t; o.y = (uint32_t)__builtin_amdgcn_mov_dpp((int)t, kNext2, 0xF, 0xF, true);
         const int yo = __builtin_amdgcn_readfirstlane(y * A.orow);
         __builtin_amdgcn_raw_buffer_store_b64(o, r_dst, (int)(lead && full ? 2u * (uint32_t)k : 0xFFFFFFF0u), yo, 2);
         if (edge_strip) __builtin_amdgcn_raw_buffer_store_b32(t, r_dst, (int)(lead && !full ? 2u * (uint32_t)k : 0xFFFFFFF0u), yo, 2);      // dw % 8 == 4: the frame's last two pairs
         if (y != 0) {                                                  // row 0's chroma is never kept
-          const int cl = !Y.unclamped;
+          const int cl = !SK.unclamped;
           int cu = min(max(ur, min_uv), max_uv), cv = min(max(vr, min_uv), max_uv);
           const bool last = y == A.dh - 1;
           if (!last && (y & 1) == (d > 0 ? 1 : 0)) { sk_cu = cu; sk_cv = cv; }      // the pair's first row on this walk
@@ -658,9 +679,9 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
               else { cu = cavg_arith(cl, cu, sk_cu); cv = cavg_arith(cl, cv, sk_cv); }
             }
             const uint32_t uv = (uint32_t)cu | ((uint32_t)cv << 16);
-            const uint32_t q = uv | ((uint32_t)__builtin_amdgcn_mov_dpp((int)uv, 0xF5, 0xF, 0xF, true) << 8);        // u(k) u(k + 1) v(k) v(k + 1)
-            const uint32_t q2 = (uint32_t)__builtin_amdgcn_mov_dpp((int)q, 0xEE, 0xF, 0xF, true);
-            const int kr = (y - 1) >> 1, uo = __builtin_amdgcn_readfirstlane(kr * Y.urow), vo = __builtin_amdgcn_readfirstlane(kr * Y.vrow);
+            const uint32_t q = uv | ((uint32_t)__builtin_amdgcn_mov_dpp((int)uv, kNext, 0xF, 0xF, true) << 8);        // u(k) u(k + 1) v(k) v(k + 1)
+            const uint32_t q2 = (uint32_t)__builtin_amdgcn_mov_dpp((int)q, kNext2, 0xF, 0xF, true);
+            const int kr = (y - 1) >> 1, uo = __builtin_amdgcn_readfirstlane(kr * SK.urow), vo = __builtin_amdgcn_readfirstlane(kr * SK.vrow);
             const uint32_t co = lead && full ? (uint32_t)k : 0xFFFFFFF0u;
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_amdgcn_perm(q2, q, 0x05040100u), r_su, (int)co, uo, 2);
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_amdgcn_perm(q2, q, 0x07060302u), r_sv, (int)co, vo, 2);
@@ -681,7 +702,7 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
     __shared__ pb_u2 s_rg[256], s_gb[256];
     // The source rows of output row y are 2y - 1 .. 2y + 2: K2's row pairs (2p - 1, 2p) for p = y and y + 1 (pair 0 is row 0 twice, pair dh the trailing row H - 1
     // twice -- the scaler's clamp).  A lane's quad kc covers chroma columns 2kc, 2kc + 1; every chroma row it reads is ONE 4-byte window, columns 2kc - 1 .. 2kc + 2.
-    const __amdgpu_buffer_rsrc_t r_u = srd(Y.u[track], Y.usize), r_v = srd(Y.v[track], Y.vsize);
+    const __amdgpu_buffer_rsrc_t r_u = srd(YS.u[track], YS.usize), r_v = srd(YS.v[track], YS.vsize);
     const int dh = A.dh;
     const uint32_t c_off = 2u * (uint32_t)kc - (kc ? 1u : 0u);      // kc == 0: the window starts at column 0 and column -1 is filled in afterwards
     struct Raw { uint32_t ya, yb, u0, v0, u1, v1, e0, e1; };
@@ -704,24 +725,24 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
       p = __builtin_amdgcn_readfirstlane(p);
       if (p > 0 && p < dh) {
         w.ya = yrow(2 * p - 1); w.yb = yrow(2 * p);
-        w.u0 = win(r_u, p - 1, Y.us, Y.usize); w.v0 = win(r_v, p - 1, Y.vs, Y.vsize); w.u1 = win(r_u, p, Y.us, Y.usize); w.v1 = win(r_v, p, Y.vs, Y.vsize);
-        w.e0 = __builtin_amdgcn_raw_buffer_load_b8(r_v, 0, __builtin_amdgcn_readfirstlane(p * Y.vs), 0);      // V(r + 1, 0): the reference's frozen "last V"
+        w.u0 = win(r_u, p - 1, YS.us, YS.usize); w.v0 = win(r_v, p - 1, YS.vs, YS.vsize); w.u1 = win(r_u, p, YS.us, YS.usize); w.v1 = win(r_v, p, YS.vs, YS.vsize);
+        w.e0 = __builtin_amdgcn_raw_buffer_load_b8(r_v, 0, __builtin_amdgcn_readfirstlane(p * YS.vs), 0);      // V(r + 1, 0): the reference's frozen "last V"
       } else if (p == 0) {
-        w.ya = yrow(0); w.u0 = win(r_u, 0, Y.us, Y.usize); w.v0 = win(r_v, 0, Y.vs, Y.vsize);
+        w.ya = yrow(0); w.u0 = win(r_u, 0, YS.us, YS.usize); w.v0 = win(r_v, 0, YS.vs, YS.vsize);
       } else {
         const int r = dh - 1;
-        w.ya = yrow(A.sh - 1); w.u1 = win(r_u, r, Y.us, Y.usize); w.v1 = win(r_v, r, Y.vs, Y.vsize);
-        if (!Y.fix_edges) {       // the 1-thread reference's last row: the left pixel's luma from row 0, its chroma walk from chroma row 0 seeded with row r's column 0
-          w.yb = yrow(0); w.u0 = win(r_u, 0, Y.us, Y.usize); w.v0 = win(r_v, 0, Y.vs, Y.vsize);
-          w.e0 = __builtin_amdgcn_raw_buffer_load_b8(r_u, 0, __builtin_amdgcn_readfirstlane(r * Y.us), 0);
-          w.e1 = __builtin_amdgcn_raw_buffer_load_b8(r_v, 0, __builtin_amdgcn_readfirstlane(r * Y.vs), 0);
+        w.ya = yrow(A.sh - 1); w.u1 = win(r_u, r, YS.us, YS.usize); w.v1 = win(r_v, r, YS.vs, YS.vsize);
+        if (!YS.fix_edges) {       // the 1-thread reference's last row: the left pixel's luma from row 0, its chroma walk from chroma row 0 seeded with row r's column 0
+          w.yb = yrow(0); w.u0 = win(r_u, 0, YS.us, YS.usize); w.v0 = win(r_v, 0, YS.vs, YS.vsize);
+          w.e0 = __builtin_amdgcn_raw_buffer_load_b8(r_u, 0, __builtin_amdgcn_readfirstlane(r * YS.us), 0);
+          w.e1 = __builtin_amdgcn_raw_buffer_load_b8(r_v, 0, __builtin_amdgcn_readfirstlane(r * YS.vs), 0);
         }
       }
       return w;
     };
     auto at = [](uint32_t w, int j) -> uint32_t { return (w >> (8 * (j + 1))) & 0xFFu; };      // chroma column 2kc + j, j = -1 .. 2
     auto lu = [](uint32_t w, int i) -> uint32_t { return (w >> (8 * i)) & 0xFFu; };           // luma column 4kc + i
-    auto bl = [&](uint32_t s1, uint32_t s2) -> uint32_t { return Y.lowq ? s1 >> 1 : yuv_third(s1, s2); };
+    auto bl = [&](uint32_t s1, uint32_t s2) -> uint32_t { return YS.lowq ? s1 >> 1 : yuv_third(s1, s2); };
     auto rclamp = [&](uint32_t w) -> uint32_t { return kc == kmax ? (w & 0x00FFFFFFu) | ((w << 8) & 0xFF000000u) : w; };      // column hw := hw - 1
     auto px = [&](uint32_t y, uint32_t iu, uint32_t iv, uint32_t *c) {
       const pb_u2 rg = s_rg[iv], gb = s_gb[iu];
@@ -766,7 +787,7 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
           const uint32_t u1 = rclamp(w.u1), v1 = rclamp(w.v1);
 #pragma unroll
           for (int j = 0; j < 2; j++) {
-            if (Y.fix_edges) px(lu(w.ya, 2 * j), (at(u1, j) + at(u1, j - 1)) >> 1, (at(v1, j) + at(v1, j - 1)) >> 1, t[2 * j]);
+            if (YS.fix_edges) px(lu(w.ya, 2 * j), (at(u1, j) + at(u1, j - 1)) >> 1, (at(v1, j) + at(v1, j - 1)) >> 1, t[2 * j]);
             else {
               const bool c0 = !kc && !j, c2 = kc != 0;                 // chroma column 0 / >= 2
               const uint32_t tu = c0 ? w.e0 : at(w.u0, j), tv = c0 ? w.e1 : at(w.v0, j);
@@ -808,12 +829,12 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
     l2.x = 0; l2.y = 0; nl2 = l2;
     if (CHAIN == 1) l2 = load_l2(d > 0 ? y0 : y0 + rows - 1);
     {       // this wave's copy of the tables, requested while the first rows are in flight (as the LUT and the blend's scalers; no workgroup barrier)
-      const int clo = Y.clamped ? 16 : 0, chi = Y.clamped ? 240 : 255;
+      const int clo = YS.clamped ? 16 : 0, chi = YS.clamped ? 240 : 255;
       uint32_t ty[4], ra[4], rb[4], ga[4], gb[4];
 #pragma unroll
       for (int i = 0; i < 4; i++) {
         const int e = lane + 64 * i, ec = e < clo ? clo : e > chi ? chi : e;
-        ty[i] = (uint32_t)Y.tables[e]; ra[i] = (uint32_t)Y.tables[256 + ec]; rb[i] = (uint32_t)Y.tables[768 + ec]; ga[i] = (uint32_t)Y.tables[512 + ec]; gb[i] = (uint32_t)Y.tables[1024 + ec];
+        ty[i] = (uint32_t)YS.tables[e]; ra[i] = (uint32_t)YS.tables[256 + ec]; rb[i] = (uint32_t)YS.tables[768 + ec]; ga[i] = (uint32_t)YS.tables[512 + ec]; gb[i] = (uint32_t)YS.tables[1024 + ec];
       }
       reinterpret_cast<uint32_t *>(s_lut)[lane] = lut.w[lane];
 #pragma unroll
@@ -847,7 +868,9 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
         else { v[i] = carry[i] + hr[i]; carry[i] = hs[i]; }
       }
       constexpr int sh_ = HYPER ? 8 : 2;
-      store_row(yy, finish(v[0] >> sh_, v[1] >> sh_, v[2] >> sh_, 0xFF000000u, cl2.x), finish(v[4] >> sh_, v[5] >> sh_, v[6] >> sh_, 0xFF000000u, cl2.y));
+      const uint32_t f0 = finish(v[0] >> sh_, v[1] >> sh_, v[2] >> sh_, 0xFF000000u, cl2.x), f1 = finish(v[4] >> sh_, v[5] >> sh_, v[6] >> sh_, 0xFF000000u, cl2.y);
+      if constexpr (SINK) sink_row(yy, f0, f1);
+      else store_row(yy, f0, f1);
     };
     int r = 0;
     for (; r + 1 < rows; r += 2) {
@@ -2037,14 +2060,14 @@ static void pb_half_bands(PbHalfArgs *a, int bands) {
   a->bands = bands; a->th = a->dh / bands; a->rem = a->dh - a->th * bands;
 }
 
-static void pb_half_geometry(PbHalfArgs *a, int ntracks, int blur = 0, int opaque = 0, int yuv = 0) {
+static void pb_half_geometry(PbHalfArgs *a, int ntracks, int blur = 0, int opaque = 0, int yuv = 0, int strip_cols = 0) {      // strip_cols: output columns per strip, when the form has its own
   // strips of 64 storing lanes on 128-byte lines (k_pb_half<.., ALIGNED>; the two outer taps of a strip from one extra 4-byte load in lanes 0 and 63, which ride into
   // the lane exchange for free).  Round 3 measured them 3 % lighter on traffic and 13 % heavier on arithmetic: a draw.  With round 4's arithmetic (buffer addressing,
   // five-operation reciprocal, no register moves, the edge taps through DPP's kept destination) they win clearly: 16 tracks 166.5 -> 155.0 us, 8 tracks 85.7 -> 81.1,
   // one frame equal (profiles/r04/al_ab1.txt, interleaved).  LGPU_PBH_ALIGNED=0 keeps the feeder-lane strips.
   a->aligned = (blur || yuv) ? 0 : 1;           // (the 4:2:0 source: the all-opaque arithmetic exists for the strips with feeder lanes)
   if (!blur && !yuv && tune(TUNE_PBH_ALIGNED) >= 0) a->aligned = tune(TUNE_PBH_ALIGNED) ? 1 : 0;
-  a->strips = (int)cdiv((unsigned)a->dw, blur ? 120 : a->aligned ? 128 : 124);
+  a->strips = (int)cdiv((unsigned)a->dw, strip_cols ? strip_cols : blur ? 120 : a->aligned ? 128 : 124);
   a->cgroups = (a->strips + 3) / 4;
   a->ntracks = ntracks;
   // Band height.  Short bands win (profiles/r03/pbh_sweep*.txt, r04/al_ab1.txt: 4-6 rows within 1 %, 8 rows 5 % behind, 12 rows further).  One frame: 6 rows.  A launch of
@@ -2768,7 +2791,7 @@ extern "C" int lgpu_chain_to_yuv(const lgpu_chain_params *pr, const lgpu_chain_s
   if ((interp != 2 && interp != 3) || pr->sw != 2 * pr->dw || pr->sh != 2 * pr->dh || (pr->dw & 3) || (planar && (pr->dh & 1)) || (sb & 15) || (lb & 7) || (pb & 15) ||
       (sk->orow[0] & 7) || (planar && ((sk->orow[1] | sk->orow[2]) & 3))) {
     set_error("lgpu_chain_to_yuv: one launch serves the exact 2:1 reduction (HYPER / BILINEAR, dw %% 4 == 0, dh even for 4:2:0, 16-byte aligned source rows and sink planes, "
-              "8-byte aligned layer-2 rows, luma / packed rowstride %% 8 == 0, chroma rowstrides %% 4 == 0)");
+              "8-byte aligned layer-2 rows, luma / packed rowstride %% 8 == 0, chroma rowstrides %% 4 == 0) of an RGBA source; a YUV420P source: lgpu_chain_yuv420p_to_yuv");
     return LGPU_E_UNSUPPORTED;
   }
   const long long lim = 1ll << 31;
@@ -2832,5 +2855,128 @@ extern "C" int lgpu_chain_to_yuv(const lgpu_chain_params *pr, const lgpu_chain_s
 #undef PBS_SWAP
 #undef PBS_LAUNCH
   LGPU_CHECK_LAUNCH();
+  return LGPU_OK;
+}
+
+// lgpu_chain_yuv420p_to_yuv: both ends at once -- K2's conversion in registers -> the exact 2:1 scaler (all-opaque arithmetic) [-> chroma blend with layer 2] [-> gamma
+// LUT] -> K4's conversion in the store.  Neither the 4K nor the 1080p RGBA frame is ever written.  Every check of lgpu_chain_yuv420p and of lgpu_chain_to_yuv on their
+// own arguments is made here before anything is enqueued.
+static_assert(sizeof(PbHalfArgs) + sizeof(PbTracks) + sizeof(Lut8) + sizeof(PbYuvSink) <= 4096, "HIP documents 4 KB of arguments for a __global__ function");
+static_assert(sizeof(PbHalfArgs) + sizeof(PbTracks) + sizeof(Lut8) + sizeof(PbYuvSrc) <= 4096 && sizeof(PbHalfArgs) + sizeof(PbTracks) + sizeof(Lut8) + sizeof(PbSinkDst) <= 4096,
+              "HIP documents 4 KB of arguments for a __global__ function");
+extern "C" int lgpu_chain_yuv420p_to_yuv(const lgpu_chain_params *pr, const lgpu_yuv_source *ys, const lgpu_chain_sink *sk, const lgpu_chain_yuv_sink_track *tracks,
+                                         int ntracks, const uint8_t *amounts, void *stream) {
+  int rc = ensure_init();
+  if (rc) return rc;
+  LGPU_REQUIRE(pr && ys && sk && tracks && ntracks > 0 && ntracks <= LGPU_CHAIN_MAX_TRACKS, "params, source, sink and 1..64 tracks required");
+  LGPU_REQUIRE(pr->interp & LGPU_INTERP_PIXBUF, "lgpu_chain_yuv420p_to_yuv serves the gdk-pixbuf arithmetic (LGPU_INTERP_PIXBUF)");
+  const bool noblend = (pr->interp & LGPU_INTERP_NOBLEND) != 0;
+  LGPU_REQUIRE(amounts || noblend, "null amounts");
+  // the source's own (lgpu_chain_yuv420p)
+  LGPU_REQUIRE(pr->sw >= 2 && !(pr->sw & 1) && pr->sh >= 1 && pr->dw > 0 && pr->dh > 0, "empty geometry or an odd 4:2:0 width");
+  LGPU_REQUIRE(ys->out_order == 0 || ys->out_order == 1, "out_order is 0 (RGBA) or 1 (BGRA)");
+  LGPU_REQUIRE(ys->which_tables >= 0 && ys->which_tables <= 3, "source which_tables is 0..3");
+  LGPU_REQUIRE(ys->pb_quality >= 1 && ys->pb_quality <= 3, "pb_quality is 1 (LOW), 2 (MED) or 3 (HIGH)");
+  LGPU_REQUIRE(!(ys->flags & ~LGPU_YUV_FIX_EDGES), "unknown flags");
+  const int hw = pr->sw >> 1, hh = (pr->sh + 1) >> 1, lys = ys->istrides[0], us = ys->istrides[1], vs = ys->istrides[2];
+  LGPU_REQUIRE(lys >= pr->sw && us >= hw && vs >= hw, "plane rowstride smaller than a row");
+  LGPU_REQUIRE(ys->u_size >= (long)(hh - 1) * us + hw && ys->v_size >= (long)(hh - 1) * vs + hw, "chroma plane smaller than its (sw / 2) x (sh / 2) samples");
+  // the sink's own (lgpu_chain_to_yuv)
+  LGPU_REQUIRE(sk->out_fmt >= 2 && sk->out_fmt <= 5, "out_fmt must be 2 (UYVY), 3 (YUYV), 4 (4:2:0 planar) or 5 (4:2:2 planar)");
+  LGPU_REQUIRE(sk->in_order == 0 || sk->in_order == 1, "in_order is 0 (RGBA) or 1 (BGRA)");
+  LGPU_REQUIRE(sk->which_tables >= 0 && sk->which_tables <= 3, "sink which_tables is 0..3");
+  LGPU_REQUIRE(sk->out_fmt >= 4 || !(sk->which_tables & 2), "only the 4:2:0 / 4:2:2 conversions take a BT.709 subspace (as lgpu_rgb_to_yuv)");
+  LGPU_REQUIRE(!(pr->dw & 1), "an odd destination width");
+  LGPU_REQUIRE(pr->sw < 32768 && pr->sh < 32768, "frame sides must stay below 32768 (16.16 positions)");
+  const int chain_order = (ys->out_order ^ (pr->swap_rb ? 1 : 0)) & 1;
+  LGPU_REQUIRE(sk->in_order == chain_order, "sink->in_order must state the byte order of the chain's result: src->out_order ^ params->swap_rb");
+  const bool planar = sk->out_fmt >= 4;
+  const int nplanes = planar ? 3 : 1, cwid = pr->dw >> 1;
+  LGPU_REQUIRE(noblend || pr->irow2 >= pr->dw * 4, "rowstride smaller than a row");
+  LGPU_REQUIRE(sk->orow[0] >= (planar ? pr->dw : pr->dw * 2) && (!planar || (sk->orow[1] >= cwid && sk->orow[2] >= cwid)), "sink rowstride smaller than a row");
+  LGPU_REQUIRE(noblend || !(pr->irow2 & 3), "rowstrides must be multiples of 4");
+  uintptr_t lb = noblend ? 0 : (uintptr_t)pr->irow2, pb = 0;
+  for (int i = 0; i < ntracks; i++) {
+    const lgpu_chain_yuv_sink_track &t = tracks[i];
+    LGPU_REQUIRE(t.y_d && t.u_d && t.v_d && (noblend || t.layer2_d), "null track pointer");
+    LGPU_REQUIRE(noblend || !((uintptr_t)t.layer2_d & 3), "layer 2 must be 4-byte aligned");
+    for (int k = 0; k < nplanes; k++) {
+      LGPU_REQUIRE(t.dst_d[k], "null destination plane");
+      LGPU_REQUIRE((const uint8_t *)t.dst_d[k] != t.y_d && (const uint8_t *)t.dst_d[k] != t.u_d && (const uint8_t *)t.dst_d[k] != t.v_d, "the chain cannot run in place");
+      pb |= (uintptr_t)t.dst_d[k];
+    }
+    lb |= (uintptr_t)(noblend ? nullptr : t.layer2_d);
+  }
+  // the one-launch form; anything else is refused, never run some other way
+  const int interp = pr->interp & 0xFF;
+  if (pr->do_blur) { set_error("lgpu_chain_yuv420p_to_yuv: the gaussian is not offered here (lgpu_yuv420p_to_rgb_batch + lgpu_chain + lgpu_rgb_to_yuv_batch)"); return LGPU_E_UNSUPPORTED; }
+  if (sk->out_fmt == 5) { set_error("lgpu_chain_yuv420p_to_yuv: YUV422P is not served (lgpu_chain_yuv420p + lgpu_rgb_to_yuv_batch)"); return LGPU_E_UNSUPPORTED; }
+  if ((interp != 2 && interp != 3) || pr->sw != 2 * pr->dw || pr->sh != 2 * pr->dh || (pr->dw & 3) || (planar && (pr->dh & 1)) || (lb & 7) || (pb & 15) ||
+      (sk->orow[0] & 7) || (planar && ((sk->orow[1] | sk->orow[2]) & 3))) {
+    set_error("lgpu_chain_yuv420p_to_yuv: one launch serves the exact 2:1 reduction (HYPER / BILINEAR, dw %% 4 == 0, dh even for 4:2:0, 16-byte aligned sink planes, "
+              "8-byte aligned layer-2 rows, luma / packed rowstride %% 8 == 0, chroma rowstrides %% 4 == 0); run lgpu_chain_yuv420p + lgpu_rgb_to_yuv_batch otherwise");
+    return LGPU_E_UNSUPPORTED;
+  }
+  const long long lim = 1ll << 31;
+  if ((long long)pr->sh * lys >= lim || ys->u_size >= lim || ys->v_size >= lim || (long long)pr->dh * sk->orow[0] >= lim || (!noblend && (long long)pr->dh * pr->irow2 >= lim)) {
+    set_error("lgpu_chain_yuv420p_to_yuv: planes of 2 GiB or more (lgpu_chain_yuv420p + lgpu_rgb_to_yuv_batch)");
+    return LGPU_E_UNSUPPORTED;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  PbPin pin;
+  if ((rc = pb_table(interp, pr->sw, pr->sh, pr->dw, pr->dh, st, &pin))) return rc;
+  PbHalfArgs a;
+  if (!pb_half_ok(pin.t, interp, pr->sw, pr->sh, pr->dw, pr->dh, 0, lb, &a.hyper, &a.ashift)) {
+    set_error("lgpu_chain_yuv420p_to_yuv: the scaler's table is not the exact 2:1 outer product (lgpu_chain_yuv420p + lgpu_rgb_to_yuv_batch)");
+    return LGPU_E_UNSUPPORTED;
+  }
+  PbYuvSink Y;
+  if ((rc = pb_opaque_check())) return rc;
+  if (planar && (rc = cavg_forms_checked())) return rc;
+  if ((rc = get_sink_tables(sk->which_tables, sk->in_order, &Y.s.tab))) return rc;
+  if ((rc = get_kscale(&a.kscale))) return rc;
+  a.sw = pr->sw; a.sh = pr->sh; a.irow = lys; a.dw = pr->dw; a.dh = pr->dh; a.orow = sk->orow[0];
+  a.swap_rb = chain_order; a.blend = 1; a.irow2 = noblend ? sk->orow[0] : pr->irow2; a.use_lut = pr->use_lut ? 1 : 0;
+  a.bf = 0; a.bf_d = nullptr; a.bf_tracks = 1; a.nt_out = 1;
+  a.cw = a.ch = a.ox = a.oy = 0; a.bar_blocks = 0; a.bar_first = 0;
+  Y.y.tables = device_tables()->yuv2rgb[ys->which_tables & 3];
+  Y.y.us = us; Y.y.vs = vs; Y.y.usize = (uint32_t)ys->u_size; Y.y.vsize = (uint32_t)ys->v_size;
+  Y.y.clamped = !(ys->which_tables & 1); Y.y.lowq = ys->pb_quality == 1; Y.y.fix_edges = (ys->flags & LGPU_YUV_FIX_EDGES) ? 1 : 0;
+  Y.s.urow = planar ? sk->orow[1] : 0; Y.s.vrow = planar ? sk->orow[2] : 0; Y.s.fmt = sk->out_fmt; Y.s.unclamped = sk->which_tables & 1;
+  const Lut8 l = pack_lut(pr->use_lut ? pr->lut8 : nullptr);
+  // kPbTranscodeTracks tracks per launch (the kernel arguments, PbYuvSink's comment): a longer tick goes as two launches on the stream
+  for (int t0 = 0; t0 < ntracks; t0 += kPbTranscodeTracks) {
+    const int n = std::min(kPbTranscodeTracks, ntracks - t0);
+    a.row_major = -1; a.bgroup = 0;
+    // the 4:2:0 sink walks strips of 60 storing lanes (whole quads of k per wave, k_pb_half's comment); the packed sinks keep the source form's 62
+    pb_half_geometry(&a, n, 0, 0, 1, planar ? 120 : 0);
+    Y.s.pairs = 0;
+    if (planar) {      // band boundaries at odd rows, as lgpu_chain_to_yuv deals them
+      const int pairs = (a.dh - 2) / 2;
+      pb_half_bands(&a, std::min(a.bands, std::max(1, pairs)));
+      Y.s.pairs = pairs;
+    }
+    a.row_major = ((long long)a.cgroups * a.bands * n >= (long long)device_cus() * 8 + 1) ? 2 : 1;
+    a.bgroup = (a.bands % 8 == 0) ? a.bands / 8 : 1;
+    a.main_blocks = (int)pb_half_grid(a);
+    PbTracks T;
+    for (int i = 0; i < n; i++) {
+      const lgpu_chain_yuv_sink_track &t = tracks[t0 + i];
+      T.src[i] = t.y_d; T.l2[i] = noblend ? t.y_d : t.layer2_d; T.dst[i] = t.dst_d[0]; T.bf[i] = amounts ? amounts[t0 + i] : 0;
+      Y.y.u[i] = t.u_d; Y.y.v[i] = t.v_d;
+      Y.s.u[i] = planar ? t.dst_d[1] : nullptr; Y.s.v[i] = planar ? t.dst_d[2] : nullptr;
+    }
+    const dim3 grid((unsigned)a.main_blocks);
+    // no dynamic LDS, as lgpu_chain_yuv420p: the registers hold this form to five waves per SIMD or fewer (docs/KERNELS.md)
+#define PBT_LAUNCH(CH, HY, SW, SK) hipLaunchKernelGGL((k_pb_half<CH, HY, 0, 0, SW, 1, 1, SK>), grid, dim3(256), 0, st, a, T, l, Y)
+#define PBT_SWAP(CH, HY, SK) do { if (a.swap_rb) PBT_LAUNCH(CH, HY, 1, SK); else PBT_LAUNCH(CH, HY, 0, SK); } while (0)
+#define PBT_HYPER(CH, SK) do { if (a.hyper) PBT_SWAP(CH, 1, SK); else PBT_SWAP(CH, 0, SK); } while (0)
+    if (planar) { if (noblend) PBT_HYPER(2, 2); else PBT_HYPER(1, 2); }
+    else { if (noblend) PBT_HYPER(2, 1); else PBT_HYPER(1, 1); }
+#undef PBT_HYPER
+#undef PBT_SWAP
+#undef PBT_LAUNCH
+    LGPU_CHECK_LAUNCH();
+  }
   return LGPU_OK;
 }

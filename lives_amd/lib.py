@@ -51,6 +51,11 @@ class ChainSinkTrack(ctypes.Structure):
     _fields_ = [("src_d", vp), ("layer2_d", vp), ("dst_d", vp * 3)]
 
 
+class ChainYuvSinkTrack(ctypes.Structure):
+    """lgpu_chain_yuv_sink_track"""
+    _fields_ = [("y_d", vp), ("u_d", vp), ("v_d", vp), ("layer2_d", vp), ("dst_d", vp * 3)]
+
+
 class YuvSource(ctypes.Structure):
     """lgpu_yuv_source"""
     _fields_ = [("istrides", ci * 3), ("u_size", cl), ("v_size", cl), ("out_order", ci), ("which_tables", ci), ("pb_quality", ci), ("flags", ci)]
@@ -162,6 +167,7 @@ PROTOTYPES = {
     "lgpu_chain_amounts": [vp, vp, vp, ci, vp, vp],
     "lgpu_chain_yuv420p": [vp, vp, vp, vp, ci, vp, vp],
     "lgpu_chain_to_yuv": [vp, vp, vp, ci, vp, vp],
+    "lgpu_chain_yuv420p_to_yuv": [vp, vp, vp, vp, ci, vp, vp],
     "lgpu_pixbuf_scale_check": [ci, ci, ci, ci, ci, ci, vp],
     "lgpu_pixbuf_scale_batch": [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp],
     "lgpu_fx_batch": [ctypes.POINTER(FxParams), ctypes.POINTER(FxFrame), ci, vp],

@@ -466,6 +466,29 @@ def chain_to_yuv(params, sink, tracks, amounts, check=True):
     return lib.call("lgpu_chain_to_yuv", *args)
 
 
+def chain_yuv_sink_tracks(ys, us, vs, layer2s, dst_planes):
+    """lgpu_chain_yuv_sink_track[]: the planes of each track's 4:2:0 source (u / v swapped for YVU420P), layer 2 (None: LGPU_INTERP_NOBLEND) and the sink's planes
+    (one tensor for UYVY / YUYV; Y, U, V for YUV420P -- the chroma planes swapped for YVU420P)"""
+    n = len(ys)
+    arr = (lib.ChainYuvSinkTrack * n)()
+    for i in range(n):
+        arr[i].y_d, arr[i].u_d, arr[i].v_d = ys[i].data_ptr(), us[i].data_ptr(), vs[i].data_ptr()
+        arr[i].layer2_d = layer2s[i].data_ptr() if layer2s is not None else None
+        for k, t in enumerate(dst_planes[i]):
+            arr[i].dst_d[k] = t.data_ptr()
+    return arr
+
+
+def chain_yuv420p_to_yuv(params, src, sink, tracks, amounts, check=True):
+    """lgpu_chain_yuv420p_to_yuv: the chain of lgpu_chain_amounts from 4:2:0 frames to a YUV sink, one launch and no RGBA frame at either end.  check=False returns
+    the library's code instead of raising (tests of the refusals)"""
+    am = (ctypes.c_uint8 * max(1, len(tracks)))(*[int(a) & 0xFF for a in amounts]) if amounts is not None else None      # None: with LGPU_INTERP_NOBLEND (0x400) in params.interp
+    args = (ctypes.byref(params), ctypes.byref(src), ctypes.byref(sink), tracks, len(tracks), am, stream_ptr())
+    if not check:
+        return lib.load().lgpu_chain_yuv420p_to_yuv(*args)
+    return lib.call("lgpu_chain_yuv420p_to_yuv", *args)
+
+
 def stream_probe(params, tracks, reps):
     """lgpu_debug_stream_probe: the chain's algorithmic bytes as a bare stream on the same frames, ms for `reps` launches (destinations left dirty)"""
     ms = ctypes.c_float()
