@@ -97,6 +97,33 @@ int lgpu_gamma_lut16(double file_gamma, int gamma_from, int gamma_to, double scr
    (0 = RS_ALIGN_DEF 32, -1 = compact).  Returns the number of planes, fills rowstrides[4]. */
 int lgpu_calc_rowstrides(int width, int palette, int alignment, int rowstrides[4]);
 
+/* ---- buffer alignment -------------------------------------------------------------------------------
+   What every entry point asks of the addresses and rowstrides it is given, and what it does below that.  "any": every address and rowstride is
+   served; an aligned frame only selects a faster kernel with the same result (docs/KERNELS.md, "Forms by alignment class").  "4": base address
+   and rowstride multiples of 4, LGPU_E_BADARG otherwise, before anything is launched.  tests/test_address_alignment.py holds every line.
+     lgpu_swizzle(_batch), lgpu_gamma_apply(_batch), lgpu_byte_luts, lgpu_mirror(_batch), lgpu_resize, lgpu_gauss5,
+     lgpu_alpha_premult_yuva, lgpu_transition, lgpu_slide_over, lgpu_dissolve, lgpu_triple_split, lgpu_composite, lgpu_colorkey(_batch),
+     lgpu_blend_multi, lgpu_deinterlace, lgpu_edge, lgpu_softlight, lgpu_yuv_switch_clamping, lgpu_yuv_repack, lgpu_yuv411_to_rgb,
+     lgpu_rgb_to_yuv411, lgpu_rgbdelay_process, lgpu_fill_pattern       any
+     lgpu_alpha_premult(_batch)                                         4
+     lgpu_blend_chroma, lgpu_blend_luma                                 4 with psize 4; any with psize 3
+     lgpu_letterbox(_at, _batch), lgpu_letterbox_bars                   4 with psize 4 (both frames); any with psize 1 and 3
+     lgpu_rgb_to_yuv(_batch, _lut16)                                    UYVY / YUYV destination: 4; everything else any
+     lgpu_yuv_to_rgb(_batch)                                            UYVY / YUYV source: 4; everything else any
+     lgpu_yuv420p_to_rgb(_batch, _lut16)                                destination 4 with opsize 4; Y, U, V and a 3-byte destination any
+     lgpu_pixbuf_scale(_batch)                                          4 with channels 4; any with channels 3
+     lgpu_blurzoom_process                                              4
+     lgpu_gauss5_colorkey, LGPU_FX_GAUSS5_COLORKEY                      4 (psize 3) / 16 (psize 4) on all three frames and rowstrides: LGPU_E_UNSUPPORTED
+                                                                        otherwise (the caller runs lgpu_gauss5 + lgpu_colorkey)
+     lgpu_fx_batch, other ops                                           as the single-frame entry point of the op, over all frames of the batch
+     lgpu_chain(_canvas, _amounts, _check, _step)                       4 on every track's source, layer 2 and destination and on the three rowstrides; frames
+                                                                        below the fused kernels' 16 (source) / 8 (destination, layer 2) run stage by stage
+     lgpu_chain_yuv420p                                                 destination and layer 2: 4 (Y, U, V planes: any).  The one-launch form wants the
+                                                                        destination and layer 2 rows 8-aligned: LGPU_E_UNSUPPORTED below that
+     lgpu_chain_to_yuv, lgpu_chain_yuv420p_to_yuv                       RGBA source and layer 2: 4.  LGPU_E_UNSUPPORTED unless the source rows and sink planes
+                                                                        are 16-aligned, layer-2 rows 8-aligned, chroma rowstrides multiples of 4
+   A batch is dispatched on its least aligned frame: one misaligned slot puts every frame of the launch on the fallback kernel. */
+
 /* ---- K1: packed RGB <-> RGB swizzles ---------------------------------------------------------------
    replaces convert_swap3_frame ... convert_swapprepost_frame (src/colourspace.c:9259-10577) as picked
    by the selector tree of convert_layer_palette_full (:12370-12556). */
