@@ -260,18 +260,18 @@ __device__ __forceinline__ uint32_t pb_mad7(uint32_t a, uint32_t c) {
   asm("v_mad_u32_u24 %0, %1, 7, %2" : "=v"(d) : "v"(a), "v"(c));
   return d;
 }
-template <int HYPER, int ALIGNED, int NCH>
-__device__ __forceinline__ void pb_half_hsum(const uint32_t A[4], const uint32_t B[4], const uint32_t xe[4], uint32_t h[8]);
-// one source row of a lane: 4 pixels -> the two H columns of its 4 channels (h[c] = column 2k, h[4 + c] = column 2k + 1)
-// e (ALIGNED strips only, otherwise 0): lane 0 holds pixel P[4k-1] there, lane 63 pixel P[4k+4] (clamped into the row), every other lane 0 -- the two taps the
-// wave shifts cannot deliver.  SWAP: channel 0 is fed from byte 2 and channel 2 from byte 0 (the R <-> B conversion of the chain costs nothing: the three colours
-// are treated alike until they are stored).
+template <int HYPER, int NCH>
+__device__ __forceinline__ void pb_half_hsum(const uint32_t A[4], const uint32_t B[4], uint32_t h[8]);
+// one source row of a lane: 4 pixels -> the two H columns of its 4 channels (h[c] = column 2k, h[4 + c] = column 2k + 1).  HYPER: on strips with feeder lanes
+// (the lanes at a strip's ends only feed their neighbours; the HYPER strips of 64 quads take pb_half_hrow_raw below).  SWAP: channel 0 is fed from byte 2 and
+// channel 2 from byte 0 (the R <-> B conversion of the chain costs nothing: the three colours are treated alike until they are stored).  ALIGNED enters no arithmetic
+// here (BILINEAR has no outer taps to exchange): it only guards the OPAQUE form.
 // OPAQUE (the caller states that every source pixel has alpha 255 -- decoded video, a frame that has just been given its alpha channel): alpha * colour is 255 * colour
 // for every tap, the 255 and the library's reciprocal cancel EXACTLY (trunc(255 T * fl(1 / 65280)) == T >> 8 for every T the 256 weight units can make of bytes, and
 // the bilinear twin with 1020 and >> 2: checked for all of them when the kernel's tables are built, pb_opaque_check), so the colours go through as plain bytes: one
 // v_perm per channel pair instead of two SDWA multiplies, three channels instead of four, a shift instead of the reciprocal and three double-precision products.
 template <int HYPER, int ALIGNED = 0, int SWAP = 0, int OPAQUE = 0>
-__device__ __forceinline__ void pb_half_hrow(pb_u4 q, uint32_t h[8], uint32_t e = 0u, uint32_t em = 0u) {
+__device__ __forceinline__ void pb_half_hrow(pb_u4 q, uint32_t h[8]) {
   static_assert(!(OPAQUE && ALIGNED), "the all-opaque form exists for the strips with feeder lanes (the gaussian chain)");
   uint32_t A[4], B[4];
   if (OPAQUE) {
@@ -286,34 +286,19 @@ __device__ __forceinline__ void pb_half_hrow(pb_u4 q, uint32_t h[8], uint32_t e 
   A[2] = pb_premul_pair<SWAP ? 0 : 2>(q.x, q.y); B[2] = pb_premul_pair<SWAP ? 0 : 2>(q.z, q.w);
   A[3] = __builtin_amdgcn_perm(q.y, q.x, 0x0C070C03u); B[3] = __builtin_amdgcn_perm(q.w, q.z, 0x0C070C03u);       // the alpha pairs
   }
-  // ALIGNED: the one pixel beyond the strip, premultiplied and already in the half of the dword where the wave shift would have delivered it -- em = 65536 in
-  // lane 0 (P[4k-1] belongs in the high half of the left neighbour's pair), 1 in lane 63 (P[4k+4] in the low half of the right neighbour's), 0 elsewhere; it then
-  // rides into the lane exchange as the value the shift leaves in lanes that have no source lane (DPP without bound_ctrl keeps the destination): 5 operations per row
-  uint32_t xe[4] = {0u, 0u, 0u, 0u};
-  if (HYPER && ALIGNED) {
-    const uint32_t am = __umul24(e >> 24, em);                           // alpha * {65536, 1, 0} <= 0xFF0000: a 24-bit operand
-    if (SWAP) {
-      asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(xe[0]) : "v"(am), "v"(e));
-      asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(xe[2]) : "v"(am), "v"(e));
-    } else {
-      asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(xe[0]) : "v"(am), "v"(e));
-      asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(xe[2]) : "v"(am), "v"(e));
-    }
-    asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(xe[1]) : "v"(am), "v"(e));
-    xe[3] = am;
-  }
-  pb_half_hsum<HYPER, ALIGNED, OPAQUE ? 3 : 4>(A, B, xe, h);
+  pb_half_hsum<HYPER, OPAQUE ? 3 : 4>(A, B, h);
 }
 
-// the horizontal taps of one source row on channel pairs already apart: A[c] = (pixel 4k, pixel 4k+1), B[c] = (4k+2, 4k+3) of channel c as 16-bit halves
-template <int HYPER, int ALIGNED, int NCH>
-__device__ __forceinline__ void pb_half_hsum(const uint32_t A[4], const uint32_t B[4], const uint32_t xe[4], uint32_t h[8]) {
+// the horizontal taps of one source row on channel pairs already apart: A[c] = (pixel 4k, pixel 4k+1), B[c] = (4k+2, 4k+3) of channel c as 16-bit halves.
+// HYPER: the outer taps come from the adjacent lanes' pairs, two DPP moves per channel (strips with feeder lanes: the lanes without a source lane get 0 and store nothing)
+template <int HYPER, int NCH>
+__device__ __forceinline__ void pb_half_hsum(const uint32_t A[4], const uint32_t B[4], uint32_t h[8]) {
 #pragma unroll
   for (int c = 0; c < NCH; c++) {
     if (HYPER) {
-      // wave_shr:1 -- the left lane's (P[4k-2], P[4k-1]);  wave_shl:1 -- the right lane's (P[4k+4], P[4k+5]);  lanes 0 / 63 keep xe (0 in strips with feeder lanes)
-      const uint32_t bl = ALIGNED ? (uint32_t)__builtin_amdgcn_update_dpp((int)xe[c], (int)B[c], 0x138, 0xF, 0xF, false) : (uint32_t)__builtin_amdgcn_mov_dpp((int)B[c], 0x138, 0xF, 0xF, true);
-      const uint32_t ar = ALIGNED ? (uint32_t)__builtin_amdgcn_update_dpp((int)xe[c], (int)A[c], 0x130, 0xF, 0xF, false) : (uint32_t)__builtin_amdgcn_mov_dpp((int)A[c], 0x130, 0xF, 0xF, true);
+      // wave_shr:1 -- the left lane's (P[4k-2], P[4k-1]);  wave_shl:1 -- the right lane's (P[4k+4], P[4k+5])
+      const uint32_t bl = (uint32_t)__builtin_amdgcn_mov_dpp((int)B[c], 0x138, 0xF, 0xF, true);
+      const uint32_t ar = (uint32_t)__builtin_amdgcn_mov_dpp((int)A[c], 0x130, 0xF, 0xF, true);
       h[c] = pb_dot2(A[c], 0x00070007u, pb_add_hi_lo(bl, B[c]));          // P[4k-1] + 7 P[4k] + 7 P[4k+1] + P[4k+2]
       h[4 + c] = pb_dot2(B[c], 0x00070007u, pb_add_hi_lo(A[c], ar));      // P[4k+1] + 7 P[4k+2] + 7 P[4k+3] + P[4k+4]
     } else {
@@ -321,6 +306,58 @@ __device__ __forceinline__ void pb_half_hsum(const uint32_t A[4], const uint32_t
       h[4 + c] = pb_dot2(B[c], 0x00010001u, 0u);
     }
   }
+}
+
+// alpha * byte C of ONE raw pixel as a whole dword (< 2^16)
+template <int C>
+__device__ __forceinline__ uint32_t pb_premul_one(uint32_t p) {
+  uint32_t d;
+  if (C == 0) asm("v_mul_u32_u24_sdwa %0, %1, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:BYTE_0" : "=v"(d) : "v"(p));
+  else if (C == 1) asm("v_mul_u32_u24_sdwa %0, %1, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:BYTE_1" : "=v"(d) : "v"(p));
+  else asm("v_mul_u32_u24_sdwa %0, %1, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:BYTE_2" : "=v"(d) : "v"(p));
+  return d;
+}
+__device__ __forceinline__ uint32_t pb_add_dw_lo(uint32_t x, uint32_t y) {      // x + y.lo16
+  uint32_t d;
+  asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0" : "=v"(d) : "v"(x), "v"(y));
+  return d;
+}
+__device__ __forceinline__ uint32_t pb_add_hi_dw(uint32_t x, uint32_t y) {      // x.hi16 + y
+  uint32_t d;
+  asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:DWORD" : "=v"(d) : "v"(x), "v"(y));
+  return d;
+}
+__device__ __forceinline__ uint32_t pb_add_b3_lo(uint32_t p, uint32_t y) {      // (alpha byte of raw pixel p) + y.lo16
+  uint32_t d;
+  asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:WORD_0" : "=v"(d) : "v"(p), "v"(y));
+  return d;
+}
+__device__ __forceinline__ uint32_t pb_add_hi_b3(uint32_t x, uint32_t p) {      // x.hi16 + (alpha byte of raw pixel p)
+  uint32_t d;
+  asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:BYTE_3" : "=v"(d) : "v"(x), "v"(p));
+  return d;
+}
+// The HYPER, ALIGNED row step (strips of 64 quads, translucent pixels): the same H_c as pb_half_hrow + pb_half_hsum give, with the lane exchange done on RAW pixels.
+// A lane needs exactly two foreign pixels per source row, nl = P[4k-1] and nr = P[4k+4]: the caller fetches them as whole RGBA dwords (two DPP moves per row instead
+// of eight on premultiplied channel pairs; the strip's edge pixel rides in as the value DPP keeps in the lane without a source lane).  Here they are premultiplied --
+// one SDWA multiply per colour, alpha byte x colour byte -> dword -- and added to the pair half they meet; the alpha itself is a byte select of that add.
+template <int SWAP>
+__device__ __forceinline__ void pb_half_hrow_raw(const pb_u4 &q, uint32_t nl, uint32_t nr, uint32_t h[8]) {
+  uint32_t A[4], B[4];
+  A[0] = pb_premul_pair<SWAP ? 2 : 0>(q.x, q.y); B[0] = pb_premul_pair<SWAP ? 2 : 0>(q.z, q.w);
+  A[1] = pb_premul_pair<1>(q.x, q.y); B[1] = pb_premul_pair<1>(q.z, q.w);
+  A[2] = pb_premul_pair<SWAP ? 0 : 2>(q.x, q.y); B[2] = pb_premul_pair<SWAP ? 0 : 2>(q.z, q.w);
+  A[3] = __builtin_amdgcn_perm(q.y, q.x, 0x0C070C03u); B[3] = __builtin_amdgcn_perm(q.w, q.z, 0x0C070C03u);       // the alpha pairs
+  const uint32_t l0 = pb_premul_one<SWAP ? 2 : 0>(nl), l1 = pb_premul_one<1>(nl), l2 = pb_premul_one<SWAP ? 0 : 2>(nl);
+  const uint32_t r0 = pb_premul_one<SWAP ? 2 : 0>(nr), r1 = pb_premul_one<1>(nr), r2 = pb_premul_one<SWAP ? 0 : 2>(nr);
+  h[0] = pb_dot2(A[0], 0x00070007u, pb_add_dw_lo(l0, B[0]));          // P[4k-1] + 7 P[4k] + 7 P[4k+1] + P[4k+2]
+  h[1] = pb_dot2(A[1], 0x00070007u, pb_add_dw_lo(l1, B[1]));
+  h[2] = pb_dot2(A[2], 0x00070007u, pb_add_dw_lo(l2, B[2]));
+  h[3] = pb_dot2(A[3], 0x00070007u, pb_add_b3_lo(nl, B[3]));
+  h[4] = pb_dot2(B[0], 0x00070007u, pb_add_hi_dw(A[0], r0));          // P[4k+1] + 7 P[4k+2] + 7 P[4k+3] + P[4k+4]
+  h[5] = pb_dot2(B[1], 0x00070007u, pb_add_hi_dw(A[1], r1));
+  h[6] = pb_dot2(B[2], 0x00070007u, pb_add_hi_dw(A[2], r2));
+  h[7] = pb_dot2(B[3], 0x00070007u, pb_add_hi_b3(A[3], nr));
 }
 
 // the all-opaque forms replace the library's (uint8_t)((double)V_c * (1.0 / (double)V_alpha)) by a shift: V_c = 255 T, V_alpha = 255 * 256 (HYPER: T = the 256 weight
@@ -581,13 +618,14 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
   const bool e_lane = HYPER && ALIGNED && (lane == 0 || lane == 63);
   const int e_x = lane == 0 ? 4 * k - 1 : 4 * k + 4;
   const uint32_t e_off = 4u * (uint32_t)(e_x < 0 ? 0 : e_x > A.sw - 1 ? A.sw - 1 : e_x);
+  // every lane issues the load, the 62 inner ones with an offset beyond the descriptor's range: the raw-buffer range check (offset >= size - row offset) that drops the
+  // stores of st_off answers such a load without a memory request.  What those lanes get is never used -- both DPP moves of hrow_raw overwrite it in every lane that has
+  // a source lane -- so there is no exec-mask branch and no initialisation per source row
+  const uint32_t e_off_x = e_lane ? e_off : 0xFFFFFFF0u;
   auto load_e = [&](int sy) -> uint32_t {
-    uint32_t e = 0u;
-    if (e_lane) {
-      sy = __builtin_amdgcn_readfirstlane(sy < 0 ? 0 : sy > A.sh - 1 ? A.sh - 1 : sy);
-      e = __builtin_amdgcn_raw_buffer_load_b32(r_src, (int)e_off, sy * A.irow, 0);
-    }
-    return e;
+    if constexpr (!(HYPER && ALIGNED)) return 0u;
+    sy = __builtin_amdgcn_readfirstlane(sy < 0 ? 0 : sy > A.sh - 1 ? A.sh - 1 : sy);
+    return __builtin_amdgcn_raw_buffer_load_b32(r_src, (int)e_off_x, sy * A.irow, 0);
   };
   // lanes outside the frame (edge strips only, a wave-uniform test) repeat the border pixel; applied when a row is consumed, so that no load is waited for early
   auto fix = [&](pb_u4 q) -> pb_u4 {
@@ -597,6 +635,18 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
       if (k > kmax) { q.x = q.w; q.y = q.w; q.z = q.w; }       // right of the frame: the last pixel repeated
     }
     return q;
+  };
+  // HYPER, ALIGNED: one source row from the loaded quad as it lies in its registers.  The two foreign pixels arrive raw: the left lane's fourth pixel (wave_shr:1) and
+  // the right lane's first (wave_shl:1); the lane without a source lane keeps e, its strip-edge pixel (DPP without bound_ctrl keeps the destination).  At the frame's
+  // right end (edge strips, a wave-uniform branch) the last quad's lane takes its own last pixel -- the library's clamp -- so the row registers are never rewritten.
+  auto hrow_raw = [&](const pb_u4 &q, uint32_t e, uint32_t h[8]) __attribute__((always_inline)) {
+    const uint32_t nl = (uint32_t)__builtin_amdgcn_update_dpp((int)e, (int)q.w, 0x138, 0xF, 0xF, false);
+    uint32_t nr = (uint32_t)__builtin_amdgcn_update_dpp((int)e, (int)q.x, 0x130, 0xF, 0xF, false);
+    if (edge_strip) {
+      asm volatile("" ::: "memory");                            // keeps this a (wave-uniform) branch, as in fix()
+      if (k == kmax) nr = q.w;
+    }
+    pb_half_hrow_raw<SWAP>(q, nl, nr, h);
   };
   const uint32_t l2_off = 8u * (uint32_t)kc + 4u * (uint32_t)A.ox;
   auto load_l2 = [&](int y) -> pb_u2 {
@@ -751,7 +801,6 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
       c[0] = SWAP ? b : r; c[1] = g; c[2] = SWAP ? r : b;
     };
     // pair p -> the H columns of its first consumed row (hf) and its second (hs_): top first walking down, bottom first walking up
-    const uint32_t xe0[4] = {0u, 0u, 0u, 0u};
     // The chroma walk below is yuv.hip's yuv420_cell() (and k_yuv420p_to_rgb_s's fast cell) on a 4-byte window: row 0, the row pair with its (2a + b) / 3 blend,
     // the left pixel's U rebuilt from the first row, the frozen V(r + 1, 0), the read one past the last pair's end, the 1-thread trailing row.  A change to one of
     // those quirks there must be made here too; tests/test_chain_yuv.py holds both against the oracle's K2 bit for bit.
@@ -819,8 +868,8 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
           }
         }
       }
-      if (d > 0) { pb_half_hsum<HYPER, 0, 3>(At, Bt, xe0, hf); pb_half_hsum<HYPER, 0, 3>(Ab, Bb, xe0, hs_); }
-      else { pb_half_hsum<HYPER, 0, 3>(Ab, Bb, xe0, hf); pb_half_hsum<HYPER, 0, 3>(At, Bt, xe0, hs_); }
+      if (d > 0) { pb_half_hsum<HYPER, 3>(At, Bt, hf); pb_half_hsum<HYPER, 3>(Ab, Bb, hs_); }
+      else { pb_half_hsum<HYPER, 3>(Ab, Bb, hf); pb_half_hsum<HYPER, 3>(At, Bt, hs_); }
     };
 
     const int p0 = d > 0 ? ylo : yhi + 1;                     // the pair of output row ystart's first two source rows; step r adds pair p0 + d (r + 1)
@@ -898,16 +947,21 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
   }
-  const uint32_t e_m = lane == 0 ? 65536u : lane == 63 ? 1u : 0u;
-  pb_half_hrow<HYPER, ALIGNED, SWAP, OPAQUE>(fix(q0), hr, e0, e_m);
-  pb_half_hrow<HYPER, ALIGNED, SWAP, OPAQUE>(fix(q1), hs, e1, e_m);
+  if constexpr (HYPER && ALIGNED) { hrow_raw(q0, e0, hr); hrow_raw(q1, e1, hs); }
+  else {
+  pb_half_hrow<HYPER, ALIGNED, SWAP, OPAQUE>(fix(q0), hr);
+  pb_half_hrow<HYPER, ALIGNED, SWAP, OPAQUE>(fix(q1), hs);
+  }
 #pragma unroll
   for (int i = 0; i < 8; i++) if (!OPAQUE || (i & 3) != 3) carry[i] = (HYPER && OPAQUE) ? pb_mad7(hs[i], hr[i]) : HYPER ? __umul24(hs[i], 7u) + hr[i] : hs[i];
 
   // one scaled row from its last two source rows (the first two are in `carry`): colours apart in cc, alpha in place (<< 24) in al
   auto scale_row = [&](const pb_u4 &ra, const pb_u4 &rb, uint32_t xa, uint32_t xb, uint32_t cc[2][3], uint32_t al[2]) __attribute__((always_inline)) {
-    pb_half_hrow<HYPER, ALIGNED, SWAP, OPAQUE>(fix(ra), hr, xa, e_m);
-    pb_half_hrow<HYPER, ALIGNED, SWAP, OPAQUE>(fix(rb), hs, xb, e_m);
+    if constexpr (HYPER && ALIGNED) { hrow_raw(ra, xa, hr); hrow_raw(rb, xb, hs); }
+    else {
+    pb_half_hrow<HYPER, ALIGNED, SWAP, OPAQUE>(fix(ra), hr);
+    pb_half_hrow<HYPER, ALIGNED, SWAP, OPAQUE>(fix(rb), hs);
+    }
     uint32_t v[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) {
@@ -936,9 +990,11 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
       const int yy = d > 0 ? ystart + r : ystart - r;
       if (r + 1 < rows) {       // the next scaled row's two new source rows and the layer-2 pixels of the next output row: in flight during this row's arithmetic
         xa = load_row(S0 + d * (2 * r + 4)); xb = load_row(S0 + d * (2 * r + 5));
-        xea = load_e(S0 + d * (2 * r + 4)); xeb = load_e(S0 + d * (2 * r + 5));
         if (CHAIN == 1) xl2 = load_l2(yy + d);
       }
+      // the strip's edge pixels (HYPER strips of 64 quads; 0 otherwise) are requested on the band's last row too -- 4 bytes in two lanes, the row index clamped into
+      // the frame, never used: each is then redefined on every trip, so the lane exchange may overwrite it where it lies instead of working on a copy
+      xea = load_e(S0 + d * (2 * r + 4)); xeb = load_e(S0 + d * (2 * r + 5));
       uint32_t cc[2][3], al[2];
       scale_row(ca, cb, cea, ceb, cc, al);
       if constexpr (SINK) sink_row(yy, finish(cc[0][0], cc[0][1], cc[0][2], al[0], cl2.x), finish(cc[1][0], cc[1][1], cc[1][2], al[1], cl2.y));
@@ -991,9 +1047,9 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
     // layer-2 pixels behind the store: a step then waits for the loads it has just issued and for its own store -- profiles/r05/blur_investigation.md.)
     uint32_t cc[2][3], al[2];
     auto scale_refill = [&](int s, bool more) __attribute__((always_inline)) {
-      pb_half_hrow<HYPER, ALIGNED, SWAP, OPAQUE>(qa, hr, 0u, e_m);
+      pb_half_hrow<HYPER, ALIGNED, SWAP, OPAQUE>(qa, hr);
       if (more) qa = load_row(S0 + d * (2 * s + 4));
-      pb_half_hrow<HYPER, ALIGNED, SWAP, OPAQUE>(qb, hs, 0u, e_m);
+      pb_half_hrow<HYPER, ALIGNED, SWAP, OPAQUE>(qb, hs);
       if (more) qb = load_row(S0 + d * (2 * s + 5));
       uint32_t v[8];
 #pragma unroll
@@ -2061,10 +2117,11 @@ static void pb_half_bands(PbHalfArgs *a, int bands) {
 }
 
 static void pb_half_geometry(PbHalfArgs *a, int ntracks, int blur = 0, int opaque = 0, int yuv = 0, int strip_cols = 0) {      // strip_cols: output columns per strip, when the form has its own
-  // strips of 64 storing lanes on 128-byte lines (k_pb_half<.., ALIGNED>; the two outer taps of a strip from one extra 4-byte load in lanes 0 and 63, which ride into
-  // the lane exchange for free).  Round 3 measured them 3 % lighter on traffic and 13 % heavier on arithmetic: a draw.  With round 4's arithmetic (buffer addressing,
-  // five-operation reciprocal, no register moves, the edge taps through DPP's kept destination) they win clearly: 16 tracks 166.5 -> 155.0 us, 8 tracks 85.7 -> 81.1,
-  // one frame equal (profiles/r04/al_ab1.txt, interleaved).  LGPU_PBH_ALIGNED=0 keeps the feeder-lane strips.
+  // strips of 64 storing lanes on 128-byte lines (k_pb_half<.., ALIGNED>; the two outer taps of a strip from one extra 4-byte load per source row, which lanes 0 and 63
+  // keep as the raw pixel the lane exchange leaves in a lane without a source lane -- hrow_raw in the kernel).  Round 3 measured them 3 % lighter on traffic and 13 %
+  // heavier on arithmetic: a draw.  With round 4's arithmetic (buffer addressing, five-operation reciprocal) they win clearly: 16 tracks 166.5 -> 155.0 us, 8 tracks
+  // 85.7 -> 81.1, one frame equal (profiles/r04/al_ab1.txt, interleaved; measured on the exchange of premultiplied pairs that the kernel had then).  The exchange of raw
+  // pixels and its instruction budget: profiles/r10/.  LGPU_PBH_ALIGNED=0 keeps the feeder-lane strips.
   a->aligned = (blur || yuv) ? 0 : 1;           // (the 4:2:0 source: the all-opaque arithmetic exists for the strips with feeder lanes)
   if (!blur && !yuv && tune(TUNE_PBH_ALIGNED) >= 0) a->aligned = tune(TUNE_PBH_ALIGNED) ? 1 : 0;
   a->strips = (int)cdiv((unsigned)a->dw, strip_cols ? strip_cols : blur ? 120 : a->aligned ? 128 : 124);
