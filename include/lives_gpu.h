@@ -501,6 +501,29 @@ typedef struct { const uint8_t *y_d, *u_d, *v_d; const uint8_t *layer2_d; uint8_
 int lgpu_chain_yuv420p_to_yuv(const lgpu_chain_params *params, const lgpu_yuv_source *src, const lgpu_chain_sink *sink, const lgpu_chain_yuv_sink_track *tracks,
                               int ntracks, const uint8_t *amounts, void *stream);
 
+/* the UNSCALED tick from decoded planar 4:2:0 frames as ONE launch -- the decoder's frame already has the project's size: the K2 conversion (lgpu_yuv420p_to_rgb,
+   opsize 4, src->out_order, every quirk kept, no LUT in it) -> [R <-> B when params->swap_rb] [-> letterbox into `canvas`, opaque black bars, written by the same
+   launch] [-> chroma blend] [-> gamma LUT]: the bytes of lgpu_yuv420p_to_rgb followed by lgpu_chain_amounts with sw == dw, sh == dh, and the converted RGBA frame is
+   never written.  Structs and conventions of lgpu_chain_yuv420p (LGPU_INTERP_PIXBUF required; LGPU_INTERP_NOBLEND: no layer 2, amounts may be NULL; the interpolation
+   number itself is not read: nothing is scaled).  Any even sw >= 2 and any sh >= 1 (odd heights as K2 takes them), any canvas offs_x, destination and layer 2 on any
+   4-byte boundary (8-byte stores where the address allows, 4-byte ones elsewhere).  LGPU_E_BADARG: what lgpu_chain_yuv420p calls a bad argument (null planes, 0 or 65
+   tracks, an odd sw, numbers out of range, unknown flags, strides or chroma planes too small, no PIXBUF, null amounts with a blend, a destination that is one of the
+   track's source planes).  LGPU_E_UNSUPPORTED: sw != dw or sh != dh (the exact 2:1 reduction is lgpu_chain_yuv420p), do_blur, planes of 2 GiB or more.  Nothing is
+   enqueued or written in either case. */
+int lgpu_chain_flat_yuv420p(const lgpu_chain_params *params, const lgpu_yuv_source *src, const lgpu_canvas *canvas, const lgpu_chain_yuv_track *tracks, int ntracks,
+                            const uint8_t *amounts, void *stream);
+/* the same tick ending at a YUV consumer: those bytes (no canvas) followed by lgpu_rgb_to_yuv(.., sink->in_order, 1, .., sink->out_fmt, 0, sink->which_tables), every
+   K4 quirk kept (YUYV without its upper chroma clamp; the 4:2:0 chroma walk cavg(row 2k + 2, row 2k + 1), the last chroma row from row dh - 1 alone); neither RGBA
+   frame is written.  Structs and conventions of lgpu_chain_yuv420p_to_yuv: out_fmt 2 UYVY / 3 YUYV / 4 YUV420P, sink->in_order == src->out_order ^ params->swap_rb,
+   YVU on either end by passing the planes swapped.  LGPU_E_BADARG: what lgpu_chain_yuv420p_to_yuv calls a bad argument.  LGPU_E_UNSUPPORTED: sw != dw or sh != dh
+   (the exact 2:1 reduction is lgpu_chain_yuv420p_to_yuv), do_blur, out_fmt 5, an odd dh with out_fmt 4, a packed sink whose plane or rowstride is not a multiple of
+   4 (a macropixel is one 4-byte store), a 4:2:0 luma plane or rowstride that is odd (a luma pair is one 2-byte store; chroma planes and strides: any), planes of
+   2 GiB or more.  Nothing is enqueued or written in either case.  UYVY / YUYV: up to 64 tracks in one launch; YUV420P: 32 per launch, 33..64 as two on `stream`
+   (seven pointers per track in the kernel's arguments).  The first call with a new (sink->which_tables, sink->in_order) pair builds a device table with a blocking
+   allocation and copy outside `stream`, as in lgpu_chain_to_yuv. */
+int lgpu_chain_flat_yuv420p_to_yuv(const lgpu_chain_params *params, const lgpu_yuv_source *src, const lgpu_chain_sink *sink, const lgpu_chain_yuv_sink_track *tracks,
+                                   int ntracks, const uint8_t *amounts, void *stream);
+
 /* ---- timing helper: HIP events on `stream` around `reps` launches of the last-configured chain; used by
    bench.py to measure the kernel's average launch duration on the stream it is launched on. */
 int lgpu_chain_timed(const lgpu_chain_params *params, const lgpu_chain_track *tracks, int ntracks,

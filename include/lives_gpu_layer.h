@@ -164,6 +164,12 @@ int lives_gpu_layer_set_opaque(lives_gpu_layer_t *layer, int on);
    alone as that batch (tests/test_deferred_sink.py).  What a stage can refuse is checked when it is recorded;
    device failures at run time surface at the flush / sync that runs the program.  lives_gpu_set_deferred(0) launches every call by itself (returns the old value). */
 int lives_gpu_set_deferred(int on);
+/* opt-in (off by default; returns the old value): a flush runs a group of YUV420P / YVU420P programs that KEEP their size -- the decoder's frame already has the
+   project's size, letterboxed or not -- with a swap, letterbox, blend or gamma table behind the conversion as ONE lgpu_chain_flat_yuv420p launch instead of the
+   batched conversion followed by lgpu_chain_amounts, and such a group (no canvas) that ends in a UYVY / YUYV / YUV420P / YVU420P sink as ONE
+   lgpu_chain_flat_yuv420p_to_yuv launch instead of three; no RGBA frame is written.  Same bytes either way (tests/test_deferred_flat.py); shapes the one-launch
+   forms refuse, and LGPU_SEAM_STAGED, keep today's launches.  A process-wide setting like lives_gpu_set_deferred. */
+int lives_gpu_set_flat_yuv(int on);
 int lives_gpu_layers_flush(lives_gpu_layer_t *const *layers, int nlayers);
 /* counters since load: [0] stages recorded, [1] fused chain launches made for pending programs, [2] programs (tracks) those carried, [3] programs run stage by stage */
 void lives_gpu_deferred_stats(unsigned long long out[4]);
@@ -172,8 +178,9 @@ void lives_gpu_deferred_stats(unsigned long long out[4]);
    shape the one-launch form does not take), [8] sink conversions recorded (LZ_SINK), [9] sink launches -- a lgpu_chain_to_yuv launch (also counted in [1]) or one
    lgpu_rgb_to_yuv_batch / lgpu_rgb_to_yuv -- and [10] the tracks they carried, [11] how many of [9] were fused launches, [12] launches that ran from YUV planes to
    YUV planes (lgpu_chain_yuv420p_to_yuv: a group of programs that start at a YUV420P / YVU420P conversion, have the exact 2:1 scale, no canvas and end in the sink;
-   each is also counted in [1], [5], [9] and [11] with its tracks in [2], [6] and [10], and makes no pre-launch [7]); at most n entries are written (callers that pass
-   n = 12 see what they saw before) */
+   each is also counted in [1], [5], [9] and [11] with its tracks in [2], [6] and [10], and makes no pre-launch [7]), [13] launches of the unscaled one-launch forms
+   (lives_gpu_set_flat_yuv(1): lgpu_chain_flat_yuv420p, also counted in [1]; lgpu_chain_flat_yuv420p_to_yuv, also counted in [1], [9] and [11]; no pre-launch [7]) and
+   [14] the tracks they carried; at most n entries are written (callers that pass n = 12 or 13 see what they saw before) */
 void lives_gpu_deferred_stats_n(unsigned long long *out, int n);
 /* (for livesgpu_fx.so) record an in-place "chroma blend" of the pending plane dst_host with the resident plane layer2_host; 1 = recorded, 0 = run the kernel */
 int lives_gpu_deferred_blend_chroma(const void *dst_host, int orow, int width, int height, int palette, const void *layer2_host, int irow2, int bf);

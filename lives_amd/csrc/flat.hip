@@ -1,0 +1,377 @@
+// flat.hip -- the UNSCALED tick from decoded planar YUV 4:2:0 frames in one launch (lgpu_chain_flat_yuv420p, lgpu_chain_flat_yuv420p_to_yuv):
+// K2's conversion (yuv.hip, every quirk kept) -> [R <-> B] [-> letterbox onto opaque black] [-> chroma blend with layer 2] [-> gamma LUT] -> RGBA, or -> K4's
+// conversion (palette.hip, every quirk kept) to UYVY / YUYV / YUV420P.  No RGBA frame is read or written in between: 1.5 + 4 + 4 bytes per pixel to RGBA with a
+// blend instead of 17.5 over two launches, 1.5 + 4 + 1.5 to YUV420P instead of 23 over three.
+//
+// No scaler, no LDS window, no cross-lane exchange.  A lane owns one (unit, chroma column k) cell of K2's walk -- unit 0 = row 0, unit p >= 1 = rows (2p - 1, 2p),
+// then (even heights) the trailing row -- that is two pixels of one row or a 2 x 2 quad.  K4's 4:2:0 chroma walk pairs the rows the same way: chroma row r is
+// cavg(row 2r + 2, row 2r + 1) with U of a pair's first pixel and V of its second, and the last chroma row is row dh - 1's alone (palette.hip, k_rgb_to_yuv FMT 4).
+// So unit p feeds chroma row p - 1 from the quad it already holds, unit 0 gives luma only, and the trailing-row unit of an even height gives the last chroma row.
+// THIS IS THE THIRD PLACE the 4:2:0 quirk walk is written down (yuv.hip yuv420_cell / k_yuv420p_to_rgb_s, pixbuf.hip k_pb_half<.., YUV>): a quirk changed
+// there must change here too.
+//
+// Tables: K2's as in k_yuv420p_to_rgb_s (RGB_Y, {R_Cr, G_Cr}[v], {G_Cb, B_Cb}[u] with the chroma clamp folded into the index: 5 KB), the LUT (256 B) and, with a
+// sink, the {Y, U} / {Y, V} tables of get_sink_tables (12 KB), all staged in LDS once per workgroup; a workgroup then walks a run of consecutive units.
+#include "lgpu_common.h"
+#include <algorithm>
+#include <string.h>
+
+namespace lgpu { int cavg_forms_checked(); }      // palette.hip
+int get_sink_tables(int which_tables, int in_order, const uint2 **out);      // pixbuf.hip
+
+namespace lgpu {
+
+constexpr int kFlatPlanarTracks = 32;     // tracks per launch with the 4:2:0 sink (seven pointers per track: 64 would not fit HIP's 4 KB of kernel arguments)
+constexpr int kFlatWgTarget = 2048;       // workgroups a launch aims at: each walks nunits * gx * ntracks / 2048 units (at least one) on one staging of the tables
+
+struct FlatArgs {
+  const int32_t *tables;         // device [5][256] RGB_Y R_Cr G_Cb G_Cr B_Cb
+  const uint2 *stab;             // sink: device [2][3][256] (get_sink_tables)
+  uint32_t usize, vsize;         // chroma plane bytes; K2's read one past the last row's end is clamped to the last byte
+  int ys, us, vs;
+  int w, h;                      // the frame
+  int orow, irow2;               // destination (RGBA / packed / luma) and layer-2 rowstrides
+  int urow, vrow;                // 4:2:0 sink: chroma rowstrides
+  int cw, ch, ox, oy;            // canvas (cw == 0: none)
+  int clamped, lowq, fix_edges, use_lut;
+  int fmt, unclamped;            // sink: 2 UYVY, 3 YUYV, 4 YUV420P
+  int gy_units, per;             // blockIdx.y < gy_units: the workgroup walks units [y * per, (y + 1) * per); the others write the canvas's bars
+};
+template <int NT, int NDST> struct FlatTracksT {
+  const uint8_t *y[NT], *u[NT], *v[NT], *l2[NT];
+  uint8_t *dst[NDST][NT];
+  uint8_t bf[NT];
+};
+template <int SINK> struct FlatTr { typedef FlatTracksT<LGPU_CHAIN_MAX_TRACKS, 1> type; };
+template <> struct FlatTr<2> { typedef FlatTracksT<kFlatPlanarTracks, 3> type; };
+template <int SINK> struct FlatSinkLds { uint2 t[6 * 256]; };
+template <> struct FlatSinkLds<0> {};
+static_assert(sizeof(FlatArgs) + sizeof(FlatTr<0>::type) + sizeof(Lut8) <= 4096 && sizeof(FlatArgs) + sizeof(FlatTr<2>::type) + sizeof(Lut8) <= 4096,
+              "HIP documents 4 KB of arguments for a __global__ function");
+
+// an address or pitch as a multiple of n (a power of two).  Every alignment decision of this file goes through it, in the kernel and in the entry points;
+// tests/test_chain_flat.py walks each class they tell apart (test_chain_flat_addresses, test_chain_flat_refusals)
+__host__ __device__ static inline bool multiple_of(uintptr_t v, unsigned n) { return v % n == 0; }
+
+// SINK: 0 RGBA, 1 packed 4:2:2 (UYVY / YUYV), 2 planar 4:2:0.  SWAP: the finished pixel is BGRA (src->out_order ^ params->swap_rb)
+template <int BLEND, int SWAP, int SINK>
+__global__ __launch_bounds__(256) void k_flat_yuv420(const FlatArgs A, const typename FlatTr<SINK>::type T, const Lut8 lut) {
+  __shared__ uint32_t s_ty[256];
+  __shared__ uint2 s_rg[256], s_gb[256];
+  __shared__ __attribute__((aligned(16))) uint8_t s_lut[256];
+  __shared__ FlatSinkLds<SINK> s_sink;
+  const int tid = threadIdx.x, z = blockIdx.z;
+  const uint32_t bf = BLEND ? (uint32_t)T.bf[z] : 0u, nbf = 255u - bf;
+  stage_lut(s_lut, lut);
+  if constexpr (SINK == 0) {
+    if ((int)blockIdx.y >= A.gy_units) {
+      // letterbox bars (letterbox_layer's black canvas under the rest of the chain): opaque black [-> chroma blend with layer 2] [-> LUT]
+      __syncthreads();
+      const int bb = ((int)blockIdx.y - A.gy_units) * (int)gridDim.x + (int)blockIdx.x, nbb = ((int)gridDim.y - A.gy_units) * (int)gridDim.x;
+      const int top = A.oy * A.cw, bottom = (A.ch - A.oy - A.h) * A.cw, sw_ = A.cw - A.w, total = top + bottom + A.h * sw_;
+      for (long p = (long)bb * 256 + tid; p < total; p += (long)nbb * 256) {
+        int q = (int)p, x, y;
+        if (q < top) { y = q / A.cw; x = q - y * A.cw; }
+        else if (q < top + bottom) { q -= top; y = q / A.cw; x = q - y * A.cw; y += A.oy + A.h; }
+        else { q -= top + bottom; y = q / sw_; x = q - y * sw_; y += A.oy; if (x >= A.ox) x += A.w; }
+        uint32_t c = 0xFF000000u;
+        if (BLEND) c = pb_chroma_rgba(c, reinterpret_cast<const uint32_t *>(T.l2[z] + (size_t)y * A.irow2)[x], bf, nbf);
+        if (A.use_lut) c = lut3_rgba(s_lut, c);
+        reinterpret_cast<uint32_t *>(T.dst[0][z] + (size_t)y * A.orow)[x] = c;
+      }
+      return;
+    }
+  }
+  {
+    // K2's tables, paired: the entry of an UNCLAMPED blended chroma value e is tables[clamp(e)] (CLAMP16_240 is 16 below 16 and 240 from 0xF0 up on 0..255)
+    const int clo = A.clamped ? 16 : 0, chi = A.clamped ? 240 : 255;
+    const int ec = tid < clo ? clo : tid > chi ? chi : tid;
+    s_ty[tid] = (uint32_t)A.tables[tid];
+    s_rg[tid] = make_uint2((uint32_t)A.tables[256 + ec], (uint32_t)A.tables[768 + ec]);
+    s_gb[tid] = make_uint2((uint32_t)A.tables[512 + ec], (uint32_t)A.tables[1024 + ec]);
+    if constexpr (SINK != 0) {
+#pragma unroll
+      for (int i = 0; i < 6; i++) s_sink.t[tid + 256 * i] = A.stab[tid + 256 * i];
+    }
+  }
+  __syncthreads();
+  const int hw = A.w >> 1, H = A.h;
+  const int k = (int)blockIdx.x * 256 + tid;
+  if (k >= hw) return;
+  const int npairs = (H - 1) / 2;                            // full row pairs starting at row 1
+  const int nunits = 1 + npairs + (((H - 1) & 1) ? 1 : 0);
+  const uint8_t *py = T.y[z], *pu = T.u[z], *pv = T.v[z];
+  auto PU = [&](int r, int kk) -> uint32_t { long i = (long)r * A.us + kk; return pu[i < (long)A.usize ? i : (long)A.usize - 1]; };
+  auto PV = [&](int r, int kk) -> uint32_t { long i = (long)r * A.vs + kk; return pv[i < (long)A.vsize ? i : (long)A.vsize - 1]; };
+  auto ld32 = [](const uint8_t *p) -> uint32_t { uint32_t w; __builtin_memcpy(&w, p, 4); return w; };
+  auto ld16 = [](const uint8_t *p) -> uint32_t { uint16_t w; __builtin_memcpy(&w, p, 2); return w; };
+  // xyuv2rgb on the paired tables; the chroma index is the blended value itself
+  auto px = [&](uint32_t yv, uint32_t iu, uint32_t iv) -> uint32_t {
+    const uint32_t yy = s_ty[yv];
+    const uint2 rg = s_rg[iv], gb = s_gb[iu];
+    uint32_t r, g, b;
+    yuv_rgb(yy, rg.x, rg.y, gb.x, gb.y, r, g, b);
+    return SWAP ? (b | (g << 8) | (r << 16) | 0xFF000000u) : (r | (g << 8) | (b << 16) | 0xFF000000u);
+  };
+  // K2's vblend: (2a + b) / 3 and (a + 2b) / 3 on doubled sums, or the halves with pb_quality LOW
+  auto vtop = [&](uint32_t s1, uint32_t s2) -> uint32_t { return A.lowq ? s1 >> 1 : yuv_third(s1, s2); };
+  auto vbot = [&](uint32_t s1, uint32_t s2) -> uint32_t { return A.lowq ? s2 >> 1 : yuv_third(s2, s1); };
+  // the rest of the chain on the two pixels of frame row i, then the store; cu / cv: the clamped U of the first pixel and V of the second (4:2:0 sink)
+  auto emit = [&](int i, uint32_t p0, uint32_t p1, int &cu, int &cv) __attribute__((always_inline)) {
+    if (BLEND) {
+      const uint8_t *l = T.l2[z] + (size_t)(i + A.oy) * A.irow2 + 4 * (size_t)(2 * k + A.ox);
+      uint32_t q0, q1;
+      if (multiple_of(reinterpret_cast<uintptr_t>(l), 8)) { const uint2 q = *reinterpret_cast<const uint2 *>(l); q0 = q.x; q1 = q.y; }
+      else { q0 = reinterpret_cast<const uint32_t *>(l)[0]; q1 = reinterpret_cast<const uint32_t *>(l)[1]; }
+      p0 = pb_chroma_rgba(p0, q0, bf, nbf); p1 = pb_chroma_rgba(p1, q1, bf, nbf);
+    }
+    if (A.use_lut) { p0 = lut3_rgba(s_lut, p0); p1 = lut3_rgba(s_lut, p1); }
+    if constexpr (SINK == 0) {
+      uint8_t *d = T.dst[0][z] + (size_t)(i + A.oy) * A.orow + 4 * (size_t)(2 * k + A.ox);
+      if (multiple_of(reinterpret_cast<uintptr_t>(d), 8)) *reinterpret_cast<uint2 *>(d) = make_uint2(p0, p1);
+      else { reinterpret_cast<uint32_t *>(d)[0] = p0; reinterpret_cast<uint32_t *>(d)[1] = p1; }
+    } else {
+      // K4 (k_pb_half's sink_row): the nine table sums >> 16 as a short, upper clamp then lower
+      const uint2 *tu = s_sink.t, *tv = s_sink.t + 768;
+      const uint2 a0 = tu[p0 & 0xFF], b0 = tu[256 + ((p0 >> 8) & 0xFF)], c0 = tu[512 + ((p0 >> 16) & 0xFF)];
+      const uint2 a1 = tv[p1 & 0xFF], b1 = tv[256 + ((p1 >> 8) & 0xFF)], c1 = tv[512 + ((p1 >> 16) & 0xFF)];
+      const int min_y = A.unclamped ? 0 : 16, max_y = A.unclamped ? 255 : 235, min_uv = min_y, max_uv = A.unclamped ? 255 : 240;
+      const int ya = (int)(a0.x + b0.x + c0.x) >> 16, yb = (int)(a1.x + b1.x + c1.x) >> 16;
+      const int ur = (int)(a0.y + b0.y + c0.y) >> 16, vr = (int)(a1.y + b1.y + c1.y) >> 16;
+      const uint32_t y0c = (uint32_t)min(max(ya, min_y), max_y), y1c = (uint32_t)min(max(yb, min_y), max_y);
+      if constexpr (SINK == 1) {
+        // rgb2yuyv lost its `else`: only the lower chroma clamp, then the byte cast (src/colourspace.c:2183-2191)
+        const int ul = max(ur, min_uv), vl = max(vr, min_uv);
+        const uint32_t uu = (uint32_t)(A.fmt == 3 ? ul : min(ul, max_uv)) & 0xFFu, vv = (uint32_t)(A.fmt == 3 ? vl : min(vl, max_uv)) & 0xFFu;
+        const uint32_t w = A.fmt == 3 ? (y0c | (uu << 8) | (y1c << 16) | (vv << 24)) : (uu | (y0c << 8) | (vv << 16) | (y1c << 24));
+        reinterpret_cast<uint32_t *>(T.dst[0][z] + (size_t)i * A.orow)[k] = w;
+      } else {
+        reinterpret_cast<uint16_t *>(T.dst[0][z] + (size_t)i * A.orow)[k] = (uint16_t)(y0c | (y1c << 8));
+        cu = min(max(ur, min_uv), max_uv); cv = min(max(vr, min_uv), max_uv);
+      }
+    }
+  };
+  const int u_lo = (int)blockIdx.y * A.per, u_hi = min(nunits, u_lo + A.per);
+  for (int unit = u_lo; unit < u_hi; unit++) {
+    int cu0 = 0, cv0 = 0, cu1 = 0, cv1 = 0;
+    if (unit == 0) {
+      // row 0 (:3399-3443)
+      const int kp = k ? k - 1 : 0, kn = (k + 1 < hw) ? k + 1 : hw - 1;
+      const uint32_t yy = ld16(py + 2 * k), uk = PU(0, k), vk = PV(0, k);
+      const uint32_t p0 = px(yy & 0xFF, (uk + PU(0, kp)) >> 1, (vk + PV(0, kp)) >> 1);
+      const uint32_t p1 = px(yy >> 8, (uk + PU(0, kn)) >> 1, (vk + PV(0, kn)) >> 1);
+      emit(0, p0, p1, cu0, cv0);       // row 0's chroma is never kept
+    } else if (unit <= npairs) {
+      // rows (i, i + 1), chroma rows r and r + 1 (:3445-3554)
+      const int i = 2 * unit - 1, r = unit - 1;
+      const uint32_t ya = ld16(py + (size_t)i * A.ys + 2 * k), yb = ld16(py + (size_t)(i + 1) * A.ys + 2 * k);
+      uint32_t u_l, u_c, u_n, u1_c, u1_n, v_c, v_n, v1_l, v1_c, v1_n, v1_0;
+      const long ou = (long)(r + 1) * A.us, ov = (long)(r + 1) * A.vs;
+      if (k >= 1 && ou + k + 3 <= (long)A.usize && ov + k + 3 <= (long)A.vsize) {
+        // interior: one 4-byte window (columns k - 1 .. k + 2, the last unused) per chroma row
+        const uint32_t wu0 = ld32(pu + (ou - A.us + k - 1)), wu1 = ld32(pu + (ou + k - 1)), wv0 = ld32(pv + (ov - A.vs + k - 1)), wv1 = ld32(pv + (ov + k - 1));
+        v1_0 = pv[ov];
+        u_l = wu0 & 0xFF; u_c = (wu0 >> 8) & 0xFF; u_n = (wu0 >> 16) & 0xFF; u1_c = (wu1 >> 8) & 0xFF; u1_n = (wu1 >> 16) & 0xFF;
+        v_c = (wv0 >> 8) & 0xFF; v_n = (wv0 >> 16) & 0xFF; v1_l = wv1 & 0xFF; v1_c = (wv1 >> 8) & 0xFF; v1_n = (wv1 >> 16) & 0xFF;
+      } else {
+        u_c = PU(r, k); v_c = PV(r, k); v1_c = PV(r + 1, k);
+        u_l = k ? PU(r, k - 1) : u_c;
+        v1_l = k ? PV(r + 1, k - 1) : v_c;
+        v1_0 = PV(r + 1, 0);
+        u_n = PU(r, k + 1); u1_c = PU(r + 1, k); u1_n = PU(r + 1, k + 1);
+        v_n = PV(r, k + 1); v1_n = PV(r + 1, k + 1);
+      }
+      // left pixel: the second row's U sum rebuilt from the first row (:3461); V of row r with the previous V of row r + 1, "last V" frozen at column 0 (:3544)
+      const uint32_t su = u_c + u_l, s1v = v_c + v1_l, s2v = v1_c + v1_0;
+      const uint32_t a0 = px(ya & 0xFF, vtop(su, su), vtop(s1v, s2v)), b0 = px(yb & 0xFF, vbot(su, su), vbot(s1v, s2v));
+      // right pixel
+      const uint32_t s1u = u_c + u_n, s2u = u1_c + u1_n, s1w = v_c + v_n, s2w = v1_c + v1_n;
+      const uint32_t a1 = px(ya >> 8, vtop(s1u, s2u), vtop(s1w, s2w)), b1 = px(yb >> 8, vbot(s1u, s2u), vbot(s1w, s2w));
+      emit(i, a0, a1, cu0, cv0);
+      emit(i + 1, b0, b1, cu1, cv1);
+      if constexpr (SINK == 2) {      // chroma row r = cavg(row 2r + 2, row 2r + 1): the argument order of the reference
+        const int cl = !A.unclamped;
+        T.dst[1][z][(size_t)r * A.urow + k] = (uint8_t)cavg_arith(cl, cu1, cu0);
+        T.dst[2][z][(size_t)r * A.vrow + k] = (uint8_t)cavg_arith(cl, cv1, cv0);
+      }
+    } else {
+      // trailing row H - 1 (:3556-3592)
+      const int i = H - 1, r = i >> 1;
+      const int kp = k ? k - 1 : 0, kn = (k + 1 < hw) ? k + 1 : hw - 1;
+      const uint32_t yy = ld16(py + (size_t)i * A.ys + 2 * k), uk = PU(r, k), vk = PV(r, k);
+      uint32_t p0;
+      if (A.fix_edges) p0 = px(yy & 0xFF, (uk + PU(r, kp)) >> 1, (vk + PV(r, kp)) >> 1);
+      else {
+        // 1-thread reference: luma from row 0; this / last walk = {row r col 0, row r col 0, row 0 col 1, row 0 col 2, ...}
+        const uint32_t tu = k ? PU(0, k) : PU(r, 0), tv = k ? PV(0, k) : PV(r, 0);
+        const uint32_t lu = (k >= 2) ? PU(0, k - 1) : PU(r, 0), lv = (k >= 2) ? PV(0, k - 1) : PV(r, 0);
+        p0 = px(py[2 * k], (tu + lu) >> 1, (tv + lv) >> 1);
+      }
+      const uint32_t p1 = px(yy >> 8, (uk + PU(r, kn)) >> 1, (vk + PV(r, kn)) >> 1);
+      emit(i, p0, p1, cu0, cv0);
+      if constexpr (SINK == 2) {      // the last chroma row is row dh - 1's alone
+        T.dst[1][z][(size_t)r * A.urow + k] = (uint8_t)cu0;
+        T.dst[2][z][(size_t)r * A.vrow + k] = (uint8_t)cv0;
+      }
+    }
+  }
+}
+
+}  // namespace lgpu
+
+using namespace lgpu;
+
+// both entry points: tracks in the sink form's layout (the RGBA form's destination is dst_d[0]); cv or sk is null
+static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv_source *ys, const lgpu_canvas *cv, const lgpu_chain_sink *sk,
+                     const lgpu_chain_yuv_sink_track *tracks, int ntracks, const uint8_t *amounts, void *stream) {
+#define FLAT_REQUIRE(cond, msg) do { if (!(cond)) { set_error("%s: %s", fn, msg); return LGPU_E_BADARG; } } while (0)
+#define FLAT_REFUSE(msg) do { set_error("%s: %s", fn, msg); return LGPU_E_UNSUPPORTED; } while (0)
+  const bool noblend = (pr->interp & LGPU_INTERP_NOBLEND) != 0;
+  FLAT_REQUIRE(pr->interp & LGPU_INTERP_PIXBUF, "the gdk-pixbuf arithmetic only (LGPU_INTERP_PIXBUF)");
+  FLAT_REQUIRE(amounts || noblend, "null amounts");
+  // the source's own (lgpu_chain_yuv420p)
+  FLAT_REQUIRE(pr->sw >= 2 && !(pr->sw & 1) && pr->sh >= 1 && pr->dw > 0 && pr->dh > 0, "empty geometry or an odd 4:2:0 width");
+  FLAT_REQUIRE(ys->out_order == 0 || ys->out_order == 1, "out_order is 0 (RGBA) or 1 (BGRA)");
+  FLAT_REQUIRE(ys->which_tables >= 0 && ys->which_tables <= 3, "source which_tables is 0..3");
+  FLAT_REQUIRE(ys->pb_quality >= 1 && ys->pb_quality <= 3, "pb_quality is 1 (LOW), 2 (MED) or 3 (HIGH)");
+  FLAT_REQUIRE(!(ys->flags & ~LGPU_YUV_FIX_EDGES), "unknown flags");
+  const int hw = pr->sw >> 1, hh = (pr->sh + 1) >> 1, lys = ys->istrides[0], us = ys->istrides[1], vs = ys->istrides[2];
+  FLAT_REQUIRE(lys >= pr->sw && us >= hw && vs >= hw, "plane rowstride smaller than a row");
+  FLAT_REQUIRE(ys->u_size >= (long)(hh - 1) * us + hw && ys->v_size >= (long)(hh - 1) * vs + hw, "chroma plane smaller than its (sw / 2) x (sh / 2) samples");
+  const int chain_order = (ys->out_order ^ (pr->swap_rb ? 1 : 0)) & 1;
+  const bool planar = sk && sk->out_fmt >= 4;
+  const int nplanes = planar ? 3 : 1;
+  int cw = pr->dw, ch = pr->dh;
+  if (sk) {
+    // the sink's own (lgpu_chain_to_yuv)
+    FLAT_REQUIRE(sk->out_fmt >= 2 && sk->out_fmt <= 5, "out_fmt must be 2 (UYVY), 3 (YUYV), 4 (4:2:0 planar) or 5 (4:2:2 planar)");
+    FLAT_REQUIRE(sk->in_order == 0 || sk->in_order == 1, "in_order is 0 (RGBA) or 1 (BGRA)");
+    FLAT_REQUIRE(sk->which_tables >= 0 && sk->which_tables <= 3, "sink which_tables is 0..3");
+    FLAT_REQUIRE(sk->out_fmt >= 4 || !(sk->which_tables & 2), "only the 4:2:0 / 4:2:2 conversions take a BT.709 subspace (as lgpu_rgb_to_yuv)");
+    FLAT_REQUIRE(!(pr->dw & 1), "an odd destination width");
+    FLAT_REQUIRE(pr->sw < 32768 && pr->sh < 32768, "frame sides must stay below 32768");
+    FLAT_REQUIRE(sk->in_order == chain_order, "sink->in_order must state the byte order of the chain's result: src->out_order ^ params->swap_rb");
+    const int cwid = pr->dw >> 1;
+    FLAT_REQUIRE(noblend || pr->irow2 >= pr->dw * 4, "rowstride smaller than a row");
+    FLAT_REQUIRE(sk->orow[0] >= (planar ? pr->dw : pr->dw * 2) && (!planar || (sk->orow[1] >= cwid && sk->orow[2] >= cwid)), "sink rowstride smaller than a row");
+    FLAT_REQUIRE(noblend || !(pr->irow2 & 3), "rowstrides must be multiples of 4");
+  } else {
+    if (cv) {
+      FLAT_REQUIRE(cv->nwidth >= pr->dw && cv->nheight >= pr->dh && cv->offs_x >= 0 && cv->offs_y >= 0 && cv->offs_x + pr->dw <= cv->nwidth &&
+                   cv->offs_y + pr->dh <= cv->nheight, "the frame must lie inside the canvas");
+      cw = cv->nwidth; ch = cv->nheight;
+    }
+    FLAT_REQUIRE(pr->orow >= cw * 4 && (noblend || pr->irow2 >= cw * 4), "rowstride smaller than a row");
+    FLAT_REQUIRE(((pr->orow | (noblend ? 0 : pr->irow2)) & 3) == 0, "rowstrides must be multiples of 4");
+  }
+  uintptr_t pb = 0;
+  for (int i = 0; i < ntracks; i++) {
+    const lgpu_chain_yuv_sink_track &t = tracks[i];
+    FLAT_REQUIRE(t.y_d && t.u_d && t.v_d && (noblend || t.layer2_d), "null track pointer");
+    FLAT_REQUIRE(noblend || multiple_of((uintptr_t)t.layer2_d, 4), "layer 2 must be 4-byte aligned");
+    for (int k = 0; k < nplanes; k++) {
+      FLAT_REQUIRE(t.dst_d[k], "null destination plane");
+      FLAT_REQUIRE((const uint8_t *)t.dst_d[k] != t.y_d && (const uint8_t *)t.dst_d[k] != t.u_d && (const uint8_t *)t.dst_d[k] != t.v_d, "the chain cannot run in place");
+    }
+    FLAT_REQUIRE(sk || multiple_of((uintptr_t)t.dst_d[0], 4), "the destination must be 4-byte aligned");
+    pb |= (uintptr_t)t.dst_d[0];
+  }
+  // the one-launch form; anything else is refused, never run some other way
+  if (pr->sw != pr->dw || pr->sh != pr->dh)
+    FLAT_REFUSE(sk ? "frames that keep their size only (sw == dw, sh == dh); the exact 2:1 reduction is lgpu_chain_yuv420p_to_yuv"
+                   : "frames that keep their size only (sw == dw, sh == dh); the exact 2:1 reduction is lgpu_chain_yuv420p");
+  if (pr->do_blur) FLAT_REFUSE("the gaussian is not offered with a 4:2:0 source");
+  if (sk) {
+    if (sk->out_fmt == 5) FLAT_REFUSE("YUV422P is not served (lgpu_chain_flat_yuv420p + lgpu_rgb_to_yuv_batch)");
+    if (planar && (pr->dh & 1)) FLAT_REFUSE("the 4:2:0 sink needs an even height");
+    // a lane stores one macropixel (4 bytes) or one luma pair (2 bytes) per row; chroma samples are single bytes
+    if (!multiple_of(pb | (uintptr_t)sk->orow[0], planar ? 2 : 4))
+      FLAT_REFUSE("packed sinks are stored as 4-byte macropixels (plane and rowstride % 4 == 0), the 4:2:0 luma plane as 2-byte pairs (plane and rowstride % 2 == 0)");
+  }
+  const long long lim = 1ll << 31;
+  const int drow = sk ? sk->orow[0] : pr->orow;
+  if ((long long)pr->sh * lys >= lim || ys->u_size >= lim || ys->v_size >= lim || (long long)ch * drow >= lim || (!noblend && (long long)ch * pr->irow2 >= lim) ||
+      (planar && ((long long)(pr->dh >> 1) * sk->orow[1] >= lim || (long long)(pr->dh >> 1) * sk->orow[2] >= lim)))
+    FLAT_REFUSE("planes of 2 GiB or more");
+  int rc;
+  FlatArgs a;
+  memset(&a, 0, sizeof a);
+  if (planar && (rc = cavg_forms_checked())) return rc;
+  if (sk && (rc = get_sink_tables(sk->which_tables, sk->in_order, &a.stab))) return rc;
+  a.tables = device_tables()->yuv2rgb[ys->which_tables & 3];
+  a.usize = (uint32_t)ys->u_size; a.vsize = (uint32_t)ys->v_size; a.ys = lys; a.us = us; a.vs = vs; a.w = pr->sw; a.h = pr->sh;
+  a.orow = drow; a.irow2 = noblend ? 0 : pr->irow2;
+  a.urow = planar ? sk->orow[1] : 0; a.vrow = planar ? sk->orow[2] : 0;
+  if (cv) { a.cw = cv->nwidth; a.ch = cv->nheight; a.ox = cv->offs_x; a.oy = cv->offs_y; }
+  a.clamped = !(ys->which_tables & 1); a.lowq = ys->pb_quality == 1; a.fix_edges = (ys->flags & LGPU_YUV_FIX_EDGES) ? 1 : 0; a.use_lut = pr->use_lut ? 1 : 0;
+  a.fmt = sk ? sk->out_fmt : 0; a.unclamped = sk ? (sk->which_tables & 1) : 0;
+  const Lut8 l = pack_lut(pr->use_lut ? pr->lut8 : nullptr);
+  const int nunits = pr->sh / 2 + 1;
+  const unsigned gx = cdiv((unsigned)hw, 256u);
+  const long long bar_px = cv ? (long long)cw * ch - (long long)pr->sw * pr->sh : 0;
+  const int per_launch = planar ? kFlatPlanarTracks : LGPU_CHAIN_MAX_TRACKS;
+  hipStream_t st = (hipStream_t)stream;
+  for (int t0 = 0; t0 < ntracks; t0 += per_launch) {
+    const int n = std::min(per_launch, ntracks - t0);
+    // about kFlatWgTarget workgroups per launch, each walking a run of consecutive units on one staging of the tables
+    const int cap = std::max(1, (int)(kFlatWgTarget / ((long long)gx * n)));
+    int gy = std::min(nunits, cap);
+    a.per = (nunits + gy - 1) / gy;
+    gy = (nunits + a.per - 1) / a.per;
+    a.gy_units = gy;
+    const unsigned bar_gy = bar_px > 0 ? (unsigned)std::min<long long>(64, (bar_px + 1024ll * gx - 1) / (1024ll * gx)) : 0u;
+    const dim3 grid(gx, (unsigned)gy + bar_gy, (unsigned)n);
+    if (planar) {
+      FlatTr<2>::type T;
+      for (int i = 0; i < n; i++) {
+        const lgpu_chain_yuv_sink_track &t = tracks[t0 + i];
+        T.y[i] = t.y_d; T.u[i] = t.u_d; T.v[i] = t.v_d; T.l2[i] = noblend ? nullptr : t.layer2_d; T.bf[i] = amounts ? amounts[t0 + i] : 0;
+        for (int k = 0; k < 3; k++) T.dst[k][i] = t.dst_d[k];
+      }
+      if (noblend) { if (chain_order) hipLaunchKernelGGL((k_flat_yuv420<0, 1, 2>), grid, dim3(256), 0, st, a, T, l); else hipLaunchKernelGGL((k_flat_yuv420<0, 0, 2>), grid, dim3(256), 0, st, a, T, l); }
+      else { if (chain_order) hipLaunchKernelGGL((k_flat_yuv420<1, 1, 2>), grid, dim3(256), 0, st, a, T, l); else hipLaunchKernelGGL((k_flat_yuv420<1, 0, 2>), grid, dim3(256), 0, st, a, T, l); }
+    } else {
+      FlatTr<0>::type T;
+      for (int i = 0; i < n; i++) {
+        const lgpu_chain_yuv_sink_track &t = tracks[t0 + i];
+        T.y[i] = t.y_d; T.u[i] = t.u_d; T.v[i] = t.v_d; T.l2[i] = noblend ? nullptr : t.layer2_d; T.bf[i] = amounts ? amounts[t0 + i] : 0;
+        T.dst[0][i] = t.dst_d[0];
+      }
+#define FLAT_LAUNCH(SK) do {                                                                                                                             \
+        if (noblend) { if (chain_order) hipLaunchKernelGGL((k_flat_yuv420<0, 1, SK>), grid, dim3(256), 0, st, a, T, l); else hipLaunchKernelGGL((k_flat_yuv420<0, 0, SK>), grid, dim3(256), 0, st, a, T, l); } \
+        else { if (chain_order) hipLaunchKernelGGL((k_flat_yuv420<1, 1, SK>), grid, dim3(256), 0, st, a, T, l); else hipLaunchKernelGGL((k_flat_yuv420<1, 0, SK>), grid, dim3(256), 0, st, a, T, l); }     \
+      } while (0)
+      if (sk) FLAT_LAUNCH(1); else FLAT_LAUNCH(0);
+#undef FLAT_LAUNCH
+    }
+    LGPU_CHECK_LAUNCH();
+  }
+  return LGPU_OK;
+#undef FLAT_REQUIRE
+#undef FLAT_REFUSE
+}
+
+// lgpu_chain_flat_yuv420p: lgpu_yuv420p_to_rgb (opsize 4, src->out_order, no LUT) + lgpu_chain_amounts with sw == dw, sh == dh, as ONE launch (the canvas's bars
+// included); every argument is checked before anything is enqueued
+extern "C" int lgpu_chain_flat_yuv420p(const lgpu_chain_params *pr, const lgpu_yuv_source *ys, const lgpu_canvas *cv, const lgpu_chain_yuv_track *tracks, int ntracks,
+                                       const uint8_t *amounts, void *stream) {
+  int rc = ensure_init();
+  if (rc) return rc;
+  LGPU_REQUIRE(pr && ys && tracks && ntracks > 0 && ntracks <= LGPU_CHAIN_MAX_TRACKS, "params, source and 1..64 tracks required");
+  lgpu_chain_yuv_sink_track tr[LGPU_CHAIN_MAX_TRACKS];
+  for (int i = 0; i < ntracks; i++) {
+    tr[i].y_d = tracks[i].y_d; tr[i].u_d = tracks[i].u_d; tr[i].v_d = tracks[i].v_d; tr[i].layer2_d = tracks[i].layer2_d;
+    tr[i].dst_d[0] = tracks[i].dst_d; tr[i].dst_d[1] = tr[i].dst_d[2] = nullptr;
+  }
+  return flat_impl("lgpu_chain_flat_yuv420p", pr, ys, cv, nullptr, tr, ntracks, amounts, stream);
+}
+
+// lgpu_chain_flat_yuv420p_to_yuv: the same without a canvas, ending in lgpu_rgb_to_yuv(.., sink->in_order, 1, .., sink->out_fmt, 0, sink->which_tables); neither RGBA
+// frame is written.  Up to 64 tracks as one launch to UYVY / YUYV; to YUV420P 32 per launch (seven pointers per track in the kernel's arguments)
+extern "C" int lgpu_chain_flat_yuv420p_to_yuv(const lgpu_chain_params *pr, const lgpu_yuv_source *ys, const lgpu_chain_sink *sk, const lgpu_chain_yuv_sink_track *tracks,
+                                              int ntracks, const uint8_t *amounts, void *stream) {
+  int rc = ensure_init();
+  if (rc) return rc;
+  LGPU_REQUIRE(pr && ys && sk && tracks && ntracks > 0 && ntracks <= LGPU_CHAIN_MAX_TRACKS, "params, source, sink and 1..64 tracks required");
+  return flat_impl("lgpu_chain_flat_yuv420p_to_yuv", pr, ys, nullptr, sk, tracks, ntracks, amounts, stream);
+}

@@ -617,6 +617,8 @@ std::atomic<unsigned long long> g_lz_recorded{0}, g_lz_chain_launches{0}, g_lz_c
 std::atomic<unsigned long long> g_lz_yuv_recorded{0}, g_lz_yuv_launches{0}, g_lz_yuv_tracks{0}, g_lz_yuv_pre{0};        // lives_gpu_deferred_stats_n [4..7]
 std::atomic<unsigned long long> g_lz_sink_recorded{0}, g_lz_sink_launches{0}, g_lz_sink_tracks{0}, g_lz_sink_fused{0};    // lives_gpu_deferred_stats_n [8..11]
 std::atomic<unsigned long long> g_lz_transcode{0};                                                                          // lives_gpu_deferred_stats_n [12]
+std::atomic<unsigned long long> g_lz_flat_launches{0}, g_lz_flat_tracks{0};                                                     // lives_gpu_deferred_stats_n [13..14]
+std::atomic<int> g_flat_yuv{0};     // lives_gpu_set_flat_yuv: unscaled YUV groups take the one-launch forms of flat.hip (off until the default is flipped with the tests' expectations)
 std::mutex g_lazy_mu;               // one program (group) runs at a time; never taken with a table lock held
 bool lazy_pal(int pal) { return pal == WEED_PALETTE_RGBA32 || pal == WEED_PALETTE_BGRA32; }
 
@@ -731,6 +733,22 @@ int lazy_run_rgba(Lazy *const *zs, int n, uint8_t *const *outp) {
       if (crc == LGPU_OK) { done = true; g_lz_chain_launches++; g_lz_chain_tracks += (unsigned long long)n; g_lz_yuv_launches++; g_lz_yuv_tracks += (unsigned long long)n; }
       else if (crc != LGPU_E_BADARG && crc != LGPU_E_UNSUPPORTED) rc = crc;
     }
+    // lives_gpu_set_flat_yuv(1): a group that keeps its size (letterboxed or not) with anything behind the conversion takes lgpu_chain_flat_yuv420p, ONE launch and no
+    // converted frame; a conversion that is all there is stays with K2's own kernel below (the same bytes either way, and that kernel is the faster converter)
+    if (!rc && !done && !staged && !z0->scale && g_flat_yuv.load() && n <= LGPU_CHAIN_MAX_TRACKS && (z0->swap || z0->canvas || z0->blend || z0->lut)) {
+      lgpu_yuv_source ys;
+      memset(&ys, 0, sizeof ys);
+      ys.istrides[0] = strides[0]; ys.istrides[1] = strides[1]; ys.istrides[2] = strides[2]; ys.u_size = z0->usz; ys.v_size = z0->vsz;
+      ys.out_order = z0->order; ys.which_tables = z0->which; ys.pb_quality = z0->quality; ys.flags = 0;
+      std::vector<lgpu_chain_yuv_track> yt((size_t)n);
+      for (int i = 0; i < n; i++) {
+        yt[(size_t)i].y_d = (const uint8_t *)zs[i]->src.d; yt[(size_t)i].u_d = (const uint8_t *)zs[i]->yu.d; yt[(size_t)i].v_d = (const uint8_t *)zs[i]->yv.d;
+        yt[(size_t)i].layer2_d = (const uint8_t *)zs[i]->l2.d; yt[(size_t)i].dst_d = outp[i];
+      }
+      const int crc = lgpu_chain_flat_yuv420p(&pr, &ys, z0->canvas ? &cv : nullptr, yt.data(), n, z0->blend ? amounts.data() : nullptr, S());
+      if (crc == LGPU_OK) { done = true; g_lz_chain_launches++; g_lz_chain_tracks += (unsigned long long)n; g_lz_flat_launches++; g_lz_flat_tracks += (unsigned long long)n; }
+      else if (crc != LGPU_E_BADARG && crc != LGPU_E_UNSUPPORTED) rc = crc;          // a refused shape takes today's two launches below
+    }
     if (!rc && !done) {
       // two launches: the group's conversions in one batch (SEAM_STAGED: one call per track), then the RGBA program -- or straight into the planes when the
       // conversion is all there is
@@ -834,6 +852,7 @@ int lazy_run_group(Lazy *const *zs, const void *const *hs, int n) {
 // UYVY, rounds within 2 us of each other): whatever fits lgpu_chain_to_yuv's one-launch form takes it -- ONE launch, no RGBA frame; every other shape runs its RGBA
 // stages as the chain group into scratch frames, followed by ONE lgpu_rgb_to_yuv_batch per 16 tracks; a program of the sink stage alone is that batch on the
 // resident frames.  SEAM_STAGED: stage by stage and one conversion per track, for tests.
+#define FLAT_SINK_FORMATS(fmt) ((fmt) == 2 || (fmt) == 3 || (fmt) == 4)
 int lazy_run_sink(Lazy *const *zs, int n, Dev (*souts)[3]) {
   const Lazy *z0 = zs[0];
   const bool staged = lgpu_tuning_get("SEAM_STAGED") > 0;
@@ -884,6 +903,44 @@ int lazy_run_sink(Lazy *const *zs, int n, Dev (*souts)[3]) {
       return LGPU_OK;
     }
     if (crc != LGPU_E_BADARG && crc != LGPU_E_UNSUPPORTED) return crc;            // a shape outside the one-launch form takes today's launches below
+  }
+  // lives_gpu_set_flat_yuv(1): an UNSCALED group from YUV planes to a YUV sink as ONE lgpu_chain_flat_yuv420p_to_yuv launch, for the sink formats FLAT_SINK_FORMATS
+  // names: those for which tools/bench_flat_chain.py shows the launch ahead of today's three (lgpu_yuv420p_to_rgb_batch, lgpu_chain_amounts, lgpu_rgb_to_yuv_batch) by
+  // more than the round-to-round spread of the latter.  profiles/r11/flat_chain.md (16 x 1080p, blend + LUT, five interleaved rounds): to UYVY 157.2 us against 274.2
+  // (spread 0.4 us), YUYV with it (the same instantiation); to YUV420P 159.7 us against 271.7 (spread 0.7 us) -- all taken.  (RGBA, lazy_run_rgba: 158.0 against 227.3.)
+  const bool flat_sink = FLAT_SINK_FORMATS(z0->sfmt);
+  if (flat_sink && g_flat_yuv.load() && !staged && z0->yuv && !z0->scale && !z0->canvas && z0->sww == z0->w && z0->shh == z0->h && n <= LGPU_CHAIN_MAX_TRACKS) {
+    for (int i = 0; i < n; i++) { await(zs[i]->src, false); await(zs[i]->yu, false); await(zs[i]->yv, false); if (zs[i]->blend) await(zs[i]->l2, false); }
+    lgpu_chain_params pr;
+    memset(&pr, 0, sizeof pr);
+    pr.sw = z0->sw; pr.sh = z0->sh; pr.irow = z0->ystr[0]; pr.dw = z0->sw; pr.dh = z0->sh; pr.irow2 = z0->blend ? z0->l2rs : 0; pr.orow = 0;
+    pr.swap_rb = z0->swap ? 1 : 0; pr.interp = LGPU_INTERP_PIXBUF | (z0->blend ? 0 : LGPU_INTERP_NOBLEND); pr.use_lut = z0->lut ? 1 : 0;
+    if (z0->lut) memcpy(pr.lut8, z0->lut8, 256);
+    lgpu_yuv_source ys;
+    memset(&ys, 0, sizeof ys);
+    ys.istrides[0] = z0->ystr[0]; ys.istrides[1] = z0->ystr[1]; ys.istrides[2] = z0->ystr[2]; ys.u_size = z0->usz; ys.v_size = z0->vsz;
+    ys.out_order = z0->order; ys.which_tables = z0->which; ys.pb_quality = z0->quality; ys.flags = 0;
+    lgpu_chain_sink sk;
+    memset(&sk, 0, sizeof sk);
+    sk.out_fmt = z0->sfmt; sk.which_tables = z0->swhich; sk.in_order = z0->sorder;
+    for (int p = 0; p < z0->snp; p++) sk.orow[p] = z0->sors[p];
+    std::vector<lgpu_chain_yuv_sink_track> tr((size_t)n);
+    std::vector<uint8_t> amounts((size_t)n);
+    for (int i = 0; i < n; i++) {
+      memset(&tr[(size_t)i], 0, sizeof tr[0]);
+      tr[(size_t)i].y_d = (const uint8_t *)zs[i]->src.d; tr[(size_t)i].u_d = (const uint8_t *)zs[i]->yu.d; tr[(size_t)i].v_d = (const uint8_t *)zs[i]->yv.d;
+      tr[(size_t)i].layer2_d = (const uint8_t *)zs[i]->l2.d;
+      for (int p = 0; p < z0->snp; p++) tr[(size_t)i].dst_d[p] = (uint8_t *)souts[i][p].d;
+      amounts[(size_t)i] = (uint8_t)zs[i]->bf;
+    }
+    const int crc = lgpu_chain_flat_yuv420p_to_yuv(&pr, &ys, &sk, tr.data(), n, z0->blend ? amounts.data() : nullptr, S());
+    if (crc == LGPU_OK) {
+      const unsigned long long nl = z0->sfmt == 4 ? (unsigned long long)((n + 31) / 32) : 1ull;      // the call's launches: 32 tracks each to YUV420P
+      g_lz_chain_launches += nl; g_lz_chain_tracks += (unsigned long long)n; g_lz_sink_launches += nl; g_lz_sink_tracks += (unsigned long long)n; g_lz_sink_fused += nl;
+      g_lz_flat_launches += nl; g_lz_flat_tracks += (unsigned long long)n;
+      return LGPU_OK;
+    }
+    if (crc != LGPU_E_BADARG && crc != LGPU_E_UNSUPPORTED) return crc;            // a refused shape takes today's launches below
   }
   if (!staged && z0->scale && !z0->canvas && !z0->yuv && z0->sww == z0->w && z0->shh == z0->h && n <= LGPU_CHAIN_MAX_TRACKS) {
     for (int i = 0; i < n; i++) { await(zs[i]->src, false); if (zs[i]->blend) await(zs[i]->l2, false); }
@@ -2248,6 +2305,8 @@ int lives_gpu_layer_set_opaque(lives_gpu_layer_t *layer, int on) {
 }
 // deferred execution (see "deferred execution on pinned layers" above): on (default) / off; returns the previous setting
 int lives_gpu_set_deferred(int on) { return g_deferred.exchange(on ? 1 : 0); }
+// unscaled YUV groups as one launch (flat.hip): off (default) / on; returns the previous setting
+int lives_gpu_set_flat_yuv(int on) { return g_flat_yuv.exchange(on ? 1 : 0); }
 // counters since the library was loaded: [0] stages recorded, [1] fused chain launches made for pending programs, [2] tracks (programs) those launches carried,
 // [3] programs run stage by stage (shapes the fused kernel does not take)
 void lives_gpu_deferred_stats(unsigned long long out[4]) {
@@ -2257,15 +2316,16 @@ void lives_gpu_deferred_stats(unsigned long long out[4]) {
 // the same counters, then [4] YUV420P / YVU420P conversions recorded, [5] one-launch YUV chain launches (lgpu_chain_yuv420p) and [6] the tracks they carried,
 // [7] conversion pre-launches of the two-launch path (lgpu_yuv420p_to_rgb_batch), [8] sink conversions recorded (LZ_SINK), [9] sink launches (a fused
 // lgpu_chain_to_yuv launch, also counted in [1], or one lgpu_rgb_to_yuv_batch / lgpu_rgb_to_yuv) and [10] the tracks they carried, [11] those of [9] that were fused lgpu_chain_to_yuv launches (the others converted an
-// RGBA frame), [12] launches that ran from YUV planes to YUV planes (lgpu_chain_yuv420p_to_yuv; each is also counted in [1], [5], [9] and [11]); at most n entries
-// are written
+// RGBA frame), [12] launches that ran from YUV planes to YUV planes (lgpu_chain_yuv420p_to_yuv; each is also counted in [1], [5], [9] and [11]), [13] launches of the
+// unscaled one-launch forms (lives_gpu_set_flat_yuv: lgpu_chain_flat_yuv420p, counted in [1] too, and lgpu_chain_flat_yuv420p_to_yuv, counted in [1], [9] and [11] too) and
+// [14] the tracks they carried; at most n entries are written
 void lives_gpu_deferred_stats_n(unsigned long long *out, int n) {
   if (!out || n <= 0) return;
-  const unsigned long long v[13] = {g_lz_recorded.load(), g_lz_chain_launches.load(), g_lz_chain_tracks.load(), g_lz_staged.load(),
+  const unsigned long long v[15] = {g_lz_recorded.load(), g_lz_chain_launches.load(), g_lz_chain_tracks.load(), g_lz_staged.load(),
                                     g_lz_yuv_recorded.load(), g_lz_yuv_launches.load(), g_lz_yuv_tracks.load(), g_lz_yuv_pre.load(),
                                     g_lz_sink_recorded.load(), g_lz_sink_launches.load(), g_lz_sink_tracks.load(), g_lz_sink_fused.load(),
-                                    g_lz_transcode.load()};
-  for (int i = 0; i < n && i < 13; i++) out[i] = v[i];
+                                    g_lz_transcode.load(), g_lz_flat_launches.load(), g_lz_flat_tracks.load()};
+  for (int i = 0; i < n && i < 15; i++) out[i] = v[i];
 }
 // Run the pending programs of these layers now, on the calling thread's stream: programs of equal shape (the tracks of one plan step) share ONE launch of the
 // fused chain kernel.  The layers stay pinned, nothing is downloaded, the host does not wait.  What a host calls once per tick when the plan steps of its tracks

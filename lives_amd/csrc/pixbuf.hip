@@ -1313,24 +1313,7 @@ __global__ __launch_bounds__(256) void k_pb_double(const PbHalfArgs A, const PbF
   }
 }
 
-// chroma blend of simple_blend.c:117-146 on an RGBA pair (the staged path's form): opaque layer-2 pixels through the integer table expression, translucent ones
-// through the reference's float scaling of both sources first; dst alpha = the track's alpha
-__device__ __forceinline__ uint32_t pb_chroma_rgba(uint32_t p1, uint32_t p2, uint32_t bf, uint32_t nbf) {
-  const uint32_t al = p2 >> 24;
-  uint32_t s1 = p1, s2 = p2;
-  if (al != 255) {
-    const float alpha = (float)((double)(float)al / 255.), inv = (float)(1. - (double)alpha);
-    s1 = 0; s2 = 0;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      s2 |= ((uint32_t)(int)__fmul_rn((float)((p2 >> (8 * c)) & 0xFF), alpha) & 0xFF) << (8 * c);
-      s1 |= ((uint32_t)(int)__fmul_rn((float)((p1 >> (8 * c)) & 0xFF), inv) & 0xFF) << (8 * c);
-    }
-  }
-  const uint32_t lo = ((__umul24(s2 & 0x00FF00FFu, bf) + __umul24(s1 & 0x00FF00FFu, nbf)) >> 8) & 0x00FF00FFu;
-  const uint32_t hi = ((__umul24((s2 >> 8) & 0xFFu, bf) + __umul24((s1 >> 8) & 0xFFu, nbf))) & 0x0000FF00u;
-  return lo | hi | (p1 & 0xFF000000u);
-}
+// (pb_chroma_rgba, the chroma blend of simple_blend.c:117-146 on an RGBA pair, lives in lgpu_common.h: flat.hip's unscaled chain blends with it too)
 
 // The chain's last stages inside a scaler's store (lgpu_chain off the exact 2:1 case, no gaussian, no canvas): the destination pixel goes [R <-> B] -> chroma blend with
 // layer 2 -> gamma LUT before it is written -- no scratch frame, no second launch.  Kernels take it as their last argument: PbNoEpi (nothing) or PbEpi.
@@ -2782,7 +2765,7 @@ extern "C" int lgpu_chain_yuv420p(const lgpu_chain_params *pr, const lgpu_yuv_so
 // is blue -- one device table per (device, which_tables, in_order).  Like the file's other lazily built tables (get_kscale, pb_table) the FIRST use of a pair does a
 // blocking hipMalloc + hipMemcpy outside `stream` (a stream capture must have met the pair before it begins), and the eight 12 KB tables live until the process ends.
 namespace lgpu { int cavg_forms_checked(); }      // palette.hip: cavg_arith against the table form, all 65,536 pairs, once per device
-static int get_sink_tables(int which_tables, int in_order, const uint2 **out) {
+int get_sink_tables(int which_tables, int in_order, const uint2 **out) {      // (not static: flat.hip's sinks take the same tables)
   static std::mutex mu;
   static std::map<std::tuple<int, int, int>, uint2 *> tabs;
   int dev = 0;

@@ -84,7 +84,8 @@ struct YuvCtx {
   }
 };
 
-// (the same walk runs in registers in pixbuf.hip's k_pb_half<.., YUV>, the 2:1 chain from a 4:2:0 source: a quirk changed here must change there too)
+// (the same walk runs in registers in pixbuf.hip's k_pb_half<.., YUV>, the 2:1 chain from a 4:2:0 source, and in flat.hip's k_flat_yuv420, the unscaled chain: a quirk
+// changed here must change in both)
 // one (unit, chroma column k) cell of the 4:2:0 walk: 2 pixels of row 0, a 2 x 2 quad of a row pair, or 2 pixels of the trailing row
 // units: 0 = row 0; p >= 1 = rows (2p-1, 2p) while 2p <= H-1; then (even H) the trailing row H-1
 __device__ __forceinline__ void yuv420_cell(const YuvArgs &a, const YuvCtx &c, int unit, int k, int hw, int npairs) {

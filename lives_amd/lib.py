@@ -168,6 +168,8 @@ PROTOTYPES = {
     "lgpu_chain_yuv420p": [vp, vp, vp, vp, ci, vp, vp],
     "lgpu_chain_to_yuv": [vp, vp, vp, ci, vp, vp],
     "lgpu_chain_yuv420p_to_yuv": [vp, vp, vp, vp, ci, vp, vp],
+    "lgpu_chain_flat_yuv420p": [vp, vp, vp, vp, ci, vp, vp],
+    "lgpu_chain_flat_yuv420p_to_yuv": [vp, vp, vp, vp, ci, vp, vp],
     "lgpu_pixbuf_scale_check": [ci, ci, ci, ci, ci, ci, vp],
     "lgpu_pixbuf_scale_batch": [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp],
     "lgpu_fx_batch": [ctypes.POINTER(FxParams), ctypes.POINTER(FxFrame), ci, vp],

@@ -489,6 +489,27 @@ def chain_yuv420p_to_yuv(params, src, sink, tracks, amounts, check=True):
     return lib.call("lgpu_chain_yuv420p_to_yuv", *args)
 
 
+def chain_flat_yuv420p(params, src, tracks, amounts, canvas=None, check=True):
+    """lgpu_chain_flat_yuv420p: lgpu_yuv420p_to_rgb + lgpu_chain_amounts on frames that keep their size (sw == dw, sh == dh), one launch and no converted frame;
+    arguments as chain_yuv420p.  check=False returns the library's code instead of raising (tests of the refusals)"""
+    am = (ctypes.c_uint8 * max(1, len(tracks)))(*[int(a) & 0xFF for a in amounts]) if amounts is not None else None      # None: with LGPU_INTERP_NOBLEND (0x400) in params.interp
+    cv = lib.Canvas(*canvas) if canvas is not None else None
+    args = (ctypes.byref(params), ctypes.byref(src), ctypes.byref(cv) if cv is not None else None, tracks, len(tracks), am, stream_ptr())
+    if not check:
+        return lib.load().lgpu_chain_flat_yuv420p(*args)
+    return lib.call("lgpu_chain_flat_yuv420p", *args)
+
+
+def chain_flat_yuv420p_to_yuv(params, src, sink, tracks, amounts, check=True):
+    """lgpu_chain_flat_yuv420p_to_yuv: the same frames to a YUV sink (UYVY / YUYV / YUV420P), one launch and no RGBA frame at either end; arguments as
+    chain_yuv420p_to_yuv.  check=False returns the library's code instead of raising (tests of the refusals)"""
+    am = (ctypes.c_uint8 * max(1, len(tracks)))(*[int(a) & 0xFF for a in amounts]) if amounts is not None else None      # None: with LGPU_INTERP_NOBLEND (0x400) in params.interp
+    args = (ctypes.byref(params), ctypes.byref(src), ctypes.byref(sink), tracks, len(tracks), am, stream_ptr())
+    if not check:
+        return lib.load().lgpu_chain_flat_yuv420p_to_yuv(*args)
+    return lib.call("lgpu_chain_flat_yuv420p_to_yuv", *args)
+
+
 def stream_probe(params, tracks, reps):
     """lgpu_debug_stream_probe: the chain's algorithmic bytes as a bare stream on the same frames, ms for `reps` launches (destinations left dirty)"""
     ms = ctypes.c_float()
