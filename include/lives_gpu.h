@@ -523,6 +523,27 @@ int lgpu_chain_flat_yuv420p(const lgpu_chain_params *params, const lgpu_yuv_sour
    allocation and copy outside `stream`, as in lgpu_chain_to_yuv. */
 int lgpu_chain_flat_yuv420p_to_yuv(const lgpu_chain_params *params, const lgpu_yuv_source *src, const lgpu_chain_sink *sink, const lgpu_chain_yuv_sink_track *tracks,
                                    int ntracks, const uint8_t *amounts, void *stream);
+/* the same tick with a decoded 4:2:0 frame as LAYER 2 as well -- a transition between two clips of the project's size: both K2 conversions ride in the loads of
+   ONE launch and no RGBA frame is read or written anywhere.  The bytes are those of lgpu_yuv420p_to_rgb on each track's layer-2 planes (opsize 4, src2->out_order,
+   src2->which_tables, src2->pb_quality, src2->flags, no LUT) into a tight sw x sh RGBA frame, followed by lgpu_chain_flat_yuv420p (sink == NULL: RGBA into dst_d[0],
+   rowstride params->orow) or lgpu_chain_flat_yuv420p_to_yuv with that frame as layer 2: every K2 quirk on both layers, each under its own lgpu_yuv_source (plane
+   rowstrides, chroma plane sizes and their clamped read past the end, table set, pb_quality, LGPU_YUV_FIX_EDGES), every K4 quirk behind them.  Both layers are
+   sw x sh; params->irow2 is not read.  YVU420P on either layer or on the sink: pass the planes swapped.  Layer 2's planes may be the track's own source planes.
+   src2->out_order states the byte order the blend works in: src->out_order ^ params->swap_rb (the rule of sink->in_order).  LGPU_E_BADARG: what
+   lgpu_chain_flat_yuv420p[_to_yuv] call a bad argument, for either source; a null layer-2 plane; src2 strides or chroma sizes too small; another src2->out_order; a
+   destination plane that is one of the track's six source planes; LGPU_INTERP_NOBLEND (nothing to mix: lgpu_chain_flat_yuv420p); null amounts; 0 or 65 tracks.
+   LGPU_E_UNSUPPORTED: what the two flat entry points refuse (sw != dw or sh != dh, do_blur, out_fmt 5, an odd dh with out_fmt 4, the sink's store-alignment classes,
+   planes of 2 GiB or more -- layer 2's count).  No canvas (the signature takes none: layer 2 would be canvas-sized and K2 pairs rows on the frame's grid).  Nothing is
+   enqueued or written in either case.  Every format goes LGPU_CHAIN_MIX_TRACKS per launch, 33..64 tracks as two launches on `stream` (nine pointers per track in
+   the kernel's arguments).  With a sink, the first call with a new (sink->which_tables, sink->in_order) pair builds a device table outside `stream`, as in
+   lgpu_chain_to_yuv. */
+#define LGPU_CHAIN_MIX_TRACKS 32   /* tracks per launch of lgpu_chain_flat_yuv420p_mix */
+typedef struct { const uint8_t *y_d, *u_d, *v_d;      /* layer 1 */
+                 const uint8_t *y2_d, *u2_d, *v2_d;   /* layer 2 */
+                 uint8_t *dst_d[3]; } lgpu_chain_yuv_mix_track;
+int lgpu_chain_flat_yuv420p_mix(const lgpu_chain_params *params, const lgpu_yuv_source *src, const lgpu_yuv_source *src2,
+                                const lgpu_chain_sink *sink /* NULL: RGBA into dst_d[0], rowstride params->orow */,
+                                const lgpu_chain_yuv_mix_track *tracks, int ntracks, const uint8_t *amounts, void *stream);
 
 /* ---- timing helper: HIP events on `stream` around `reps` launches of the last-configured chain; used by
    bench.py to measure the kernel's average launch duration on the stream it is launched on. */

@@ -12,6 +12,9 @@
 //
 // Tables: K2's as in k_yuv420p_to_rgb_s (RGB_Y, {R_Cr, G_Cr}[v], {G_Cb, B_Cb}[u] with the chroma clamp folded into the index: 5 KB), the LUT (256 B) and, with a
 // sink, the {Y, U} / {Y, V} tables of get_sink_tables (12 KB), all staged in LDS once per workgroup; a workgroup then walks a run of consecutive units.
+//
+// lgpu_chain_flat_yuv420p_mix (the L2YUV policy): layer 2 is a decoded 4:2:0 frame of the same size.  The lane that owns a cell of layer 1 owns the same cell of layer
+// 2 and converts it with the same walk (flat_cell) under layer 2's own description; 1.5 + 1.5 + 4 bytes per pixel to RGBA and no RGBA frame anywhere.
 #include "lgpu_common.h"
 #include <algorithm>
 #include <string.h>
@@ -42,28 +45,128 @@ template <int NT, int NDST> struct FlatTracksT {
   uint8_t *dst[NDST][NT];
   uint8_t bf[NT];
 };
-template <int SINK> struct FlatTr { typedef FlatTracksT<LGPU_CHAIN_MAX_TRACKS, 1> type; };
-template <> struct FlatTr<2> { typedef FlatTracksT<kFlatPlanarTracks, 3> type; };
+// L2YUV: layer 2 is a decoded 4:2:0 frame too (lgpu_chain_flat_yuv420p_mix).  Its description travels with the tracks, so FlatArgs and the argument layout of the
+// L2YUV = 0 instantiations stay what they were
+template <int NT, int NDST> struct FlatMixTracksT {
+  const uint8_t *y[NT], *u[NT], *v[NT], *y2[NT], *u2[NT], *v2[NT];
+  uint8_t *dst[NDST][NT];
+  uint8_t bf[NT];
+  const int32_t *tables2;        // layer 2's device [5][256]; null: src2 names layer 1's tables and the one staged copy serves both
+  uint32_t usize2, vsize2;
+  int ys2, us2, vs2;
+  int clamped2, lowq2, fix_edges2;
+};
+template <int SINK, int L2YUV = 0> struct FlatTr { typedef FlatTracksT<LGPU_CHAIN_MAX_TRACKS, 1> type; };
+template <> struct FlatTr<2, 0> { typedef FlatTracksT<kFlatPlanarTracks, 3> type; };
+template <int SINK> struct FlatTr<SINK, 1> { typedef FlatMixTracksT<LGPU_CHAIN_MIX_TRACKS, SINK == 2 ? 3 : 1> type; };
 template <int SINK> struct FlatSinkLds { uint2 t[6 * 256]; };
 template <> struct FlatSinkLds<0> {};
-static_assert(sizeof(FlatArgs) + sizeof(FlatTr<0>::type) + sizeof(Lut8) <= 4096 && sizeof(FlatArgs) + sizeof(FlatTr<2>::type) + sizeof(Lut8) <= 4096,
+template <int L2YUV> struct FlatL2Lds { uint32_t ty[256]; uint2 rg[256], gb[256]; };      // layer 2's own K2 tables (5 KB), staged when its which_tables differs
+template <> struct FlatL2Lds<0> {};
+static_assert(sizeof(FlatArgs) + sizeof(FlatTr<0>::type) + sizeof(Lut8) <= 4096 && sizeof(FlatArgs) + sizeof(FlatTr<2>::type) + sizeof(Lut8) <= 4096 &&
+              sizeof(FlatArgs) + sizeof(FlatTr<0, 1>::type) + sizeof(Lut8) <= 4096 && sizeof(FlatArgs) + sizeof(FlatTr<2, 1>::type) + sizeof(Lut8) <= 4096,
               "HIP documents 4 KB of arguments for a __global__ function");
 
 // an address or pitch as a multiple of n (a power of two).  Every alignment decision of this file goes through it, in the kernel and in the entry points;
 // tests/test_chain_flat.py walks each class they tell apart (test_chain_flat_addresses, test_chain_flat_refusals)
 __host__ __device__ static inline bool multiple_of(uintptr_t v, unsigned n) { return v % n == 0; }
 
-// SINK: 0 RGBA, 1 packed 4:2:2 (UYVY / YUYV), 2 planar 4:2:0.  SWAP: the finished pixel is BGRA (src->out_order ^ params->swap_rb)
-template <int BLEND, int SWAP, int SINK>
-__global__ __launch_bounds__(256) void k_flat_yuv420(const FlatArgs A, const typename FlatTr<SINK>::type T, const Lut8 lut) {
+// one layer's planes as K2 reads them, and the staged K2 tables they are converted with
+struct FlatPlanes {
+  const uint8_t *y, *u, *v;
+  uint32_t usize, vsize;         // chroma plane bytes; K2's read one past the last row's end is clamped to the last byte of THIS layer's plane
+  int ys, us, vs;
+  int lowq, fix_edges;
+};
+struct FlatK2Lds { const uint32_t *ty; const uint2 *rg, *gb; };
+template <int KIND> struct FlatCell { static constexpr int value = KIND; };      // 0: row 0, 1: a row pair, 2: the trailing row
+
+// K2's walk for cell (unit, k) of one layer: its two pixels of one row or its 2 x 2 quad go to out(FlatCell<KIND>, first row, chroma row, p0, p1, second row's p0, p1).  Both layers
+// of the L2YUV form come through here, each with its own planes and tables
+template <int SWAP, class Out>
+__device__ __forceinline__ void flat_cell(const FlatPlanes &P, const FlatK2Lds &L, int unit, int k, int hw, int H, int npairs, Out &&out) {
+  const uint8_t *py = P.y, *pu = P.u, *pv = P.v;
+  auto PU = [&](int r, int kk) -> uint32_t { long i = (long)r * P.us + kk; return pu[i < (long)P.usize ? i : (long)P.usize - 1]; };
+  auto PV = [&](int r, int kk) -> uint32_t { long i = (long)r * P.vs + kk; return pv[i < (long)P.vsize ? i : (long)P.vsize - 1]; };
+  auto ld32 = [](const uint8_t *p) -> uint32_t { uint32_t w; __builtin_memcpy(&w, p, 4); return w; };
+  auto ld16 = [](const uint8_t *p) -> uint32_t { uint16_t w; __builtin_memcpy(&w, p, 2); return w; };
+  // xyuv2rgb on the paired tables; the chroma index is the blended value itself
+  auto px = [&](uint32_t yv, uint32_t iu, uint32_t iv) -> uint32_t {
+    const uint32_t yy = L.ty[yv];
+    const uint2 rg = L.rg[iv], gb = L.gb[iu];
+    uint32_t r, g, b;
+    yuv_rgb(yy, rg.x, rg.y, gb.x, gb.y, r, g, b);
+    return SWAP ? (b | (g << 8) | (r << 16) | 0xFF000000u) : (r | (g << 8) | (b << 16) | 0xFF000000u);
+  };
+  // K2's vblend: (2a + b) / 3 and (a + 2b) / 3 on doubled sums, or the halves with pb_quality LOW
+  auto vtop = [&](uint32_t s1, uint32_t s2) -> uint32_t { return P.lowq ? s1 >> 1 : yuv_third(s1, s2); };
+  auto vbot = [&](uint32_t s1, uint32_t s2) -> uint32_t { return P.lowq ? s2 >> 1 : yuv_third(s2, s1); };
+  if (unit == 0) {
+    // row 0 (:3399-3443)
+    const int kp = k ? k - 1 : 0, kn = (k + 1 < hw) ? k + 1 : hw - 1;
+    const uint32_t yy = ld16(py + 2 * k), uk = PU(0, k), vk = PV(0, k);
+    const uint32_t p0 = px(yy & 0xFF, (uk + PU(0, kp)) >> 1, (vk + PV(0, kp)) >> 1);
+    const uint32_t p1 = px(yy >> 8, (uk + PU(0, kn)) >> 1, (vk + PV(0, kn)) >> 1);
+    out(FlatCell<0>(), 0, 0, p0, p1, 0u, 0u);
+  } else if (unit <= npairs) {
+    // rows (i, i + 1), chroma rows r and r + 1 (:3445-3554)
+    const int i = 2 * unit - 1, r = unit - 1;
+    const uint32_t ya = ld16(py + (size_t)i * P.ys + 2 * k), yb = ld16(py + (size_t)(i + 1) * P.ys + 2 * k);
+    uint32_t u_l, u_c, u_n, u1_c, u1_n, v_c, v_n, v1_l, v1_c, v1_n, v1_0;
+    const long ou = (long)(r + 1) * P.us, ov = (long)(r + 1) * P.vs;
+    if (k >= 1 && ou + k + 3 <= (long)P.usize && ov + k + 3 <= (long)P.vsize) {
+      // interior: one 4-byte window (columns k - 1 .. k + 2, the last unused) per chroma row
+      const uint32_t wu0 = ld32(pu + (ou - P.us + k - 1)), wu1 = ld32(pu + (ou + k - 1)), wv0 = ld32(pv + (ov - P.vs + k - 1)), wv1 = ld32(pv + (ov + k - 1));
+      v1_0 = pv[ov];
+      u_l = wu0 & 0xFF; u_c = (wu0 >> 8) & 0xFF; u_n = (wu0 >> 16) & 0xFF; u1_c = (wu1 >> 8) & 0xFF; u1_n = (wu1 >> 16) & 0xFF;
+      v_c = (wv0 >> 8) & 0xFF; v_n = (wv0 >> 16) & 0xFF; v1_l = wv1 & 0xFF; v1_c = (wv1 >> 8) & 0xFF; v1_n = (wv1 >> 16) & 0xFF;
+    } else {
+      u_c = PU(r, k); v_c = PV(r, k); v1_c = PV(r + 1, k);
+      u_l = k ? PU(r, k - 1) : u_c;
+      v1_l = k ? PV(r + 1, k - 1) : v_c;
+      v1_0 = PV(r + 1, 0);
+      u_n = PU(r, k + 1); u1_c = PU(r + 1, k); u1_n = PU(r + 1, k + 1);
+      v_n = PV(r, k + 1); v1_n = PV(r + 1, k + 1);
+    }
+    // left pixel: the second row's U sum rebuilt from the first row (:3461); V of row r with the previous V of row r + 1, "last V" frozen at column 0 (:3544)
+    const uint32_t su = u_c + u_l, s1v = v_c + v1_l, s2v = v1_c + v1_0;
+    const uint32_t a0 = px(ya & 0xFF, vtop(su, su), vtop(s1v, s2v)), b0 = px(yb & 0xFF, vbot(su, su), vbot(s1v, s2v));
+    // right pixel
+    const uint32_t s1u = u_c + u_n, s2u = u1_c + u1_n, s1w = v_c + v_n, s2w = v1_c + v1_n;
+    const uint32_t a1 = px(ya >> 8, vtop(s1u, s2u), vtop(s1w, s2w)), b1 = px(yb >> 8, vbot(s1u, s2u), vbot(s1w, s2w));
+    out(FlatCell<1>(), i, r, a0, a1, b0, b1);
+  } else {
+    // trailing row H - 1 (:3556-3592)
+    const int i = H - 1, r = i >> 1;
+    const int kp = k ? k - 1 : 0, kn = (k + 1 < hw) ? k + 1 : hw - 1;
+    const uint32_t yy = ld16(py + (size_t)i * P.ys + 2 * k), uk = PU(r, k), vk = PV(r, k);
+    uint32_t p0;
+    if (P.fix_edges) p0 = px(yy & 0xFF, (uk + PU(r, kp)) >> 1, (vk + PV(r, kp)) >> 1);
+    else {
+      // 1-thread reference: luma from row 0; this / last walk = {row r col 0, row r col 0, row 0 col 1, row 0 col 2, ...}
+      const uint32_t tu = k ? PU(0, k) : PU(r, 0), tv = k ? PV(0, k) : PV(r, 0);
+      const uint32_t lu = (k >= 2) ? PU(0, k - 1) : PU(r, 0), lv = (k >= 2) ? PV(0, k - 1) : PV(r, 0);
+      p0 = px(py[2 * k], (tu + lu) >> 1, (tv + lv) >> 1);
+    }
+    const uint32_t p1 = px(yy >> 8, (uk + PU(r, kn)) >> 1, (vk + PV(r, kn)) >> 1);
+    out(FlatCell<2>(), i, r, p0, p1, 0u, 0u);
+  }
+}
+
+// SINK: 0 RGBA, 1 packed 4:2:2 (UYVY / YUYV), 2 planar 4:2:0.  SWAP: the finished pixel is BGRA (src->out_order ^ params->swap_rb).  L2YUV: layer 2 is a 4:2:0 frame
+// of the same size (BLEND is 1, no canvas): the lane converts ITS cell of layer 2 first, with the same walk, keeps the two or four finished pixels and only then
+// walks layer 1, so the temporaries of the two walks are never live together.  Layer 2's alpha is 255 by construction: the blend is the opaque one
+template <int BLEND, int SWAP, int SINK, int L2YUV = 0>
+__global__ __launch_bounds__(256) void k_flat_yuv420(const FlatArgs A, const typename FlatTr<SINK, L2YUV>::type T, const Lut8 lut) {
   __shared__ uint32_t s_ty[256];
   __shared__ uint2 s_rg[256], s_gb[256];
   __shared__ __attribute__((aligned(16))) uint8_t s_lut[256];
   __shared__ FlatSinkLds<SINK> s_sink;
+  __shared__ FlatL2Lds<L2YUV> s_l2;
   const int tid = threadIdx.x, z = blockIdx.z;
   const uint32_t bf = BLEND ? (uint32_t)T.bf[z] : 0u, nbf = 255u - bf;
   stage_lut(s_lut, lut);
-  if constexpr (SINK == 0) {
+  if constexpr (SINK == 0 && !L2YUV) {
     if ((int)blockIdx.y >= A.gy_units) {
       // letterbox bars (letterbox_layer's black canvas under the rest of the chain): opaque black [-> chroma blend with layer 2] [-> LUT]
       __syncthreads();
@@ -93,6 +196,15 @@ __global__ __launch_bounds__(256) void k_flat_yuv420(const FlatArgs A, const typ
 #pragma unroll
       for (int i = 0; i < 6; i++) s_sink.t[tid + 256 * i] = A.stab[tid + 256 * i];
     }
+    if constexpr (L2YUV) {
+      if (T.tables2) {        // layer 2's own tables, its own chroma clamp in the index
+        const int clo2 = T.clamped2 ? 16 : 0, chi2 = T.clamped2 ? 240 : 255;
+        const int e2 = tid < clo2 ? clo2 : tid > chi2 ? chi2 : tid;
+        s_l2.ty[tid] = (uint32_t)T.tables2[tid];
+        s_l2.rg[tid] = make_uint2((uint32_t)T.tables2[256 + e2], (uint32_t)T.tables2[768 + e2]);
+        s_l2.gb[tid] = make_uint2((uint32_t)T.tables2[512 + e2], (uint32_t)T.tables2[1024 + e2]);
+      }
+    }
   }
   __syncthreads();
   const int hw = A.w >> 1, H = A.h;
@@ -100,27 +212,15 @@ __global__ __launch_bounds__(256) void k_flat_yuv420(const FlatArgs A, const typ
   if (k >= hw) return;
   const int npairs = (H - 1) / 2;                            // full row pairs starting at row 1
   const int nunits = 1 + npairs + (((H - 1) & 1) ? 1 : 0);
-  const uint8_t *py = T.y[z], *pu = T.u[z], *pv = T.v[z];
-  auto PU = [&](int r, int kk) -> uint32_t { long i = (long)r * A.us + kk; return pu[i < (long)A.usize ? i : (long)A.usize - 1]; };
-  auto PV = [&](int r, int kk) -> uint32_t { long i = (long)r * A.vs + kk; return pv[i < (long)A.vsize ? i : (long)A.vsize - 1]; };
-  auto ld32 = [](const uint8_t *p) -> uint32_t { uint32_t w; __builtin_memcpy(&w, p, 4); return w; };
-  auto ld16 = [](const uint8_t *p) -> uint32_t { uint16_t w; __builtin_memcpy(&w, p, 2); return w; };
-  // xyuv2rgb on the paired tables; the chroma index is the blended value itself
-  auto px = [&](uint32_t yv, uint32_t iu, uint32_t iv) -> uint32_t {
-    const uint32_t yy = s_ty[yv];
-    const uint2 rg = s_rg[iv], gb = s_gb[iu];
-    uint32_t r, g, b;
-    yuv_rgb(yy, rg.x, rg.y, gb.x, gb.y, r, g, b);
-    return SWAP ? (b | (g << 8) | (r << 16) | 0xFF000000u) : (r | (g << 8) | (b << 16) | 0xFF000000u);
-  };
-  // K2's vblend: (2a + b) / 3 and (a + 2b) / 3 on doubled sums, or the halves with pb_quality LOW
-  auto vtop = [&](uint32_t s1, uint32_t s2) -> uint32_t { return A.lowq ? s1 >> 1 : yuv_third(s1, s2); };
-  auto vbot = [&](uint32_t s1, uint32_t s2) -> uint32_t { return A.lowq ? s2 >> 1 : yuv_third(s2, s1); };
-  // the rest of the chain on the two pixels of frame row i, then the store; cu / cv: the clamped U of the first pixel and V of the second (4:2:0 sink)
-  auto emit = [&](int i, uint32_t p0, uint32_t p1, int &cu, int &cv) __attribute__((always_inline)) {
-    if (BLEND) {
+  const FlatPlanes P1 = {T.y[z], T.u[z], T.v[z], A.usize, A.vsize, A.ys, A.us, A.vs, A.lowq, A.fix_edges};
+  const FlatK2Lds L1 = {s_ty, s_rg, s_gb};
+  // the rest of the chain on the two pixels of frame row i, then the store; q0 / q1: layer 2's two pixels (L2YUV; read from the RGBA frame otherwise); cu / cv: the
+  // clamped U of the first pixel and V of the second (4:2:0 sink)
+  auto emit = [&](int i, uint32_t p0, uint32_t p1, uint32_t q0, uint32_t q1, int &cu, int &cv) __attribute__((always_inline)) {
+    if constexpr (L2YUV) {
+      p0 = pb_chroma_opaque(p0, q0, bf, nbf); p1 = pb_chroma_opaque(p1, q1, bf, nbf);
+    } else if (BLEND) {
       const uint8_t *l = T.l2[z] + (size_t)(i + A.oy) * A.irow2 + 4 * (size_t)(2 * k + A.ox);
-      uint32_t q0, q1;
       if (multiple_of(reinterpret_cast<uintptr_t>(l), 8)) { const uint2 q = *reinterpret_cast<const uint2 *>(l); q0 = q.x; q1 = q.y; }
       else { q0 = reinterpret_cast<const uint32_t *>(l)[0]; q1 = reinterpret_cast<const uint32_t *>(l)[1]; }
       p0 = pb_chroma_rgba(p0, q0, bf, nbf); p1 = pb_chroma_rgba(p1, q1, bf, nbf);
@@ -154,66 +254,31 @@ __global__ __launch_bounds__(256) void k_flat_yuv420(const FlatArgs A, const typ
   const int u_lo = (int)blockIdx.y * A.per, u_hi = min(nunits, u_lo + A.per);
   for (int unit = u_lo; unit < u_hi; unit++) {
     int cu0 = 0, cv0 = 0, cu1 = 0, cv1 = 0;
-    if (unit == 0) {
-      // row 0 (:3399-3443)
-      const int kp = k ? k - 1 : 0, kn = (k + 1 < hw) ? k + 1 : hw - 1;
-      const uint32_t yy = ld16(py + 2 * k), uk = PU(0, k), vk = PV(0, k);
-      const uint32_t p0 = px(yy & 0xFF, (uk + PU(0, kp)) >> 1, (vk + PV(0, kp)) >> 1);
-      const uint32_t p1 = px(yy >> 8, (uk + PU(0, kn)) >> 1, (vk + PV(0, kn)) >> 1);
-      emit(0, p0, p1, cu0, cv0);       // row 0's chroma is never kept
-    } else if (unit <= npairs) {
-      // rows (i, i + 1), chroma rows r and r + 1 (:3445-3554)
-      const int i = 2 * unit - 1, r = unit - 1;
-      const uint32_t ya = ld16(py + (size_t)i * A.ys + 2 * k), yb = ld16(py + (size_t)(i + 1) * A.ys + 2 * k);
-      uint32_t u_l, u_c, u_n, u1_c, u1_n, v_c, v_n, v1_l, v1_c, v1_n, v1_0;
-      const long ou = (long)(r + 1) * A.us, ov = (long)(r + 1) * A.vs;
-      if (k >= 1 && ou + k + 3 <= (long)A.usize && ov + k + 3 <= (long)A.vsize) {
-        // interior: one 4-byte window (columns k - 1 .. k + 2, the last unused) per chroma row
-        const uint32_t wu0 = ld32(pu + (ou - A.us + k - 1)), wu1 = ld32(pu + (ou + k - 1)), wv0 = ld32(pv + (ov - A.vs + k - 1)), wv1 = ld32(pv + (ov + k - 1));
-        v1_0 = pv[ov];
-        u_l = wu0 & 0xFF; u_c = (wu0 >> 8) & 0xFF; u_n = (wu0 >> 16) & 0xFF; u1_c = (wu1 >> 8) & 0xFF; u1_n = (wu1 >> 16) & 0xFF;
-        v_c = (wv0 >> 8) & 0xFF; v_n = (wv0 >> 16) & 0xFF; v1_l = wv1 & 0xFF; v1_c = (wv1 >> 8) & 0xFF; v1_n = (wv1 >> 16) & 0xFF;
-      } else {
-        u_c = PU(r, k); v_c = PV(r, k); v1_c = PV(r + 1, k);
-        u_l = k ? PU(r, k - 1) : u_c;
-        v1_l = k ? PV(r + 1, k - 1) : v_c;
-        v1_0 = PV(r + 1, 0);
-        u_n = PU(r, k + 1); u1_c = PU(r + 1, k); u1_n = PU(r + 1, k + 1);
-        v_n = PV(r, k + 1); v1_n = PV(r + 1, k + 1);
+    uint32_t q[4] = {0u, 0u, 0u, 0u};
+    if constexpr (L2YUV) {
+      const FlatPlanes P2 = {T.y2[z], T.u2[z], T.v2[z], T.usize2, T.vsize2, T.ys2, T.us2, T.vs2, T.lowq2, T.fix_edges2};
+      const bool own = T.tables2 != nullptr;      // wave-uniform
+      const FlatK2Lds L2 = {own ? s_l2.ty : s_ty, own ? s_l2.rg : s_rg, own ? s_l2.gb : s_gb};
+      flat_cell<SWAP>(P2, L2, unit, k, hw, H, npairs, [&](auto, int, int, uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1) __attribute__((always_inline)) {
+        q[0] = a0; q[1] = a1; q[2] = b0; q[3] = b1;
+      });
+    }
+    flat_cell<SWAP>(P1, L1, unit, k, hw, H, npairs, [&](auto cell, int i, int r, uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1) __attribute__((always_inline)) {
+      constexpr int kind = decltype(cell)::value;
+      emit(i, a0, a1, q[0], q[1], cu0, cv0);       // row 0's chroma is never kept
+      if constexpr (kind == 1) {
+        emit(i + 1, b0, b1, q[2], q[3], cu1, cv1);
+        if constexpr (SINK == 2) {      // chroma row r = cavg(row 2r + 2, row 2r + 1): the argument order of the reference
+          const int cl = !A.unclamped;
+          T.dst[1][z][(size_t)r * A.urow + k] = (uint8_t)cavg_arith(cl, cu1, cu0);
+          T.dst[2][z][(size_t)r * A.vrow + k] = (uint8_t)cavg_arith(cl, cv1, cv0);
+        }
       }
-      // left pixel: the second row's U sum rebuilt from the first row (:3461); V of row r with the previous V of row r + 1, "last V" frozen at column 0 (:3544)
-      const uint32_t su = u_c + u_l, s1v = v_c + v1_l, s2v = v1_c + v1_0;
-      const uint32_t a0 = px(ya & 0xFF, vtop(su, su), vtop(s1v, s2v)), b0 = px(yb & 0xFF, vbot(su, su), vbot(s1v, s2v));
-      // right pixel
-      const uint32_t s1u = u_c + u_n, s2u = u1_c + u1_n, s1w = v_c + v_n, s2w = v1_c + v1_n;
-      const uint32_t a1 = px(ya >> 8, vtop(s1u, s2u), vtop(s1w, s2w)), b1 = px(yb >> 8, vbot(s1u, s2u), vbot(s1w, s2w));
-      emit(i, a0, a1, cu0, cv0);
-      emit(i + 1, b0, b1, cu1, cv1);
-      if constexpr (SINK == 2) {      // chroma row r = cavg(row 2r + 2, row 2r + 1): the argument order of the reference
-        const int cl = !A.unclamped;
-        T.dst[1][z][(size_t)r * A.urow + k] = (uint8_t)cavg_arith(cl, cu1, cu0);
-        T.dst[2][z][(size_t)r * A.vrow + k] = (uint8_t)cavg_arith(cl, cv1, cv0);
-      }
-    } else {
-      // trailing row H - 1 (:3556-3592)
-      const int i = H - 1, r = i >> 1;
-      const int kp = k ? k - 1 : 0, kn = (k + 1 < hw) ? k + 1 : hw - 1;
-      const uint32_t yy = ld16(py + (size_t)i * A.ys + 2 * k), uk = PU(r, k), vk = PV(r, k);
-      uint32_t p0;
-      if (A.fix_edges) p0 = px(yy & 0xFF, (uk + PU(r, kp)) >> 1, (vk + PV(r, kp)) >> 1);
-      else {
-        // 1-thread reference: luma from row 0; this / last walk = {row r col 0, row r col 0, row 0 col 1, row 0 col 2, ...}
-        const uint32_t tu = k ? PU(0, k) : PU(r, 0), tv = k ? PV(0, k) : PV(r, 0);
-        const uint32_t lu = (k >= 2) ? PU(0, k - 1) : PU(r, 0), lv = (k >= 2) ? PV(0, k - 1) : PV(r, 0);
-        p0 = px(py[2 * k], (tu + lu) >> 1, (tv + lv) >> 1);
-      }
-      const uint32_t p1 = px(yy >> 8, (uk + PU(r, kn)) >> 1, (vk + PV(r, kn)) >> 1);
-      emit(i, p0, p1, cu0, cv0);
-      if constexpr (SINK == 2) {      // the last chroma row is row dh - 1's alone
+      if constexpr (kind == 2 && SINK == 2) {      // the last chroma row is row dh - 1's alone
         T.dst[1][z][(size_t)r * A.urow + k] = (uint8_t)cu0;
         T.dst[2][z][(size_t)r * A.vrow + k] = (uint8_t)cv0;
       }
-    }
+    });
   }
 }
 
@@ -221,24 +286,33 @@ __global__ __launch_bounds__(256) void k_flat_yuv420(const FlatArgs A, const typ
 
 using namespace lgpu;
 
-// both entry points: tracks in the sink form's layout (the RGBA form's destination is dst_d[0]); cv or sk is null
+// all three entry points: tracks in the sink form's layout (the RGBA form's destination is dst_d[0]); cv or sk is null.  ys2 / mix: the second source and the
+// caller's tracks of lgpu_chain_flat_yuv420p_mix (layer 2's planes are read from them; tracks[].layer2_d is null then), null otherwise
 static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv_source *ys, const lgpu_canvas *cv, const lgpu_chain_sink *sk,
-                     const lgpu_chain_yuv_sink_track *tracks, int ntracks, const uint8_t *amounts, void *stream) {
+                     const lgpu_chain_yuv_sink_track *tracks, int ntracks, const uint8_t *amounts, void *stream, const lgpu_yuv_source *ys2 = nullptr,
+                     const lgpu_chain_yuv_mix_track *mix = nullptr) {
 #define FLAT_REQUIRE(cond, msg) do { if (!(cond)) { set_error("%s: %s", fn, msg); return LGPU_E_BADARG; } } while (0)
 #define FLAT_REFUSE(msg) do { set_error("%s: %s", fn, msg); return LGPU_E_UNSUPPORTED; } while (0)
   const bool noblend = (pr->interp & LGPU_INTERP_NOBLEND) != 0;
+  const bool l2rgba = !noblend && !ys2;      // layer 2 is an RGBA frame of rowstride params->irow2
   FLAT_REQUIRE(pr->interp & LGPU_INTERP_PIXBUF, "the gdk-pixbuf arithmetic only (LGPU_INTERP_PIXBUF)");
+  FLAT_REQUIRE(!ys2 || !noblend, "LGPU_INTERP_NOBLEND leaves nothing to mix: lgpu_chain_flat_yuv420p[_to_yuv]");
   FLAT_REQUIRE(amounts || noblend, "null amounts");
-  // the source's own (lgpu_chain_yuv420p)
+  // the sources' own (lgpu_chain_yuv420p)
   FLAT_REQUIRE(pr->sw >= 2 && !(pr->sw & 1) && pr->sh >= 1 && pr->dw > 0 && pr->dh > 0, "empty geometry or an odd 4:2:0 width");
-  FLAT_REQUIRE(ys->out_order == 0 || ys->out_order == 1, "out_order is 0 (RGBA) or 1 (BGRA)");
-  FLAT_REQUIRE(ys->which_tables >= 0 && ys->which_tables <= 3, "source which_tables is 0..3");
-  FLAT_REQUIRE(ys->pb_quality >= 1 && ys->pb_quality <= 3, "pb_quality is 1 (LOW), 2 (MED) or 3 (HIGH)");
-  FLAT_REQUIRE(!(ys->flags & ~LGPU_YUV_FIX_EDGES), "unknown flags");
   const int hw = pr->sw >> 1, hh = (pr->sh + 1) >> 1, lys = ys->istrides[0], us = ys->istrides[1], vs = ys->istrides[2];
-  FLAT_REQUIRE(lys >= pr->sw && us >= hw && vs >= hw, "plane rowstride smaller than a row");
-  FLAT_REQUIRE(ys->u_size >= (long)(hh - 1) * us + hw && ys->v_size >= (long)(hh - 1) * vs + hw, "chroma plane smaller than its (sw / 2) x (sh / 2) samples");
+  for (const lgpu_yuv_source *s : {ys, ys2}) {
+    if (!s) continue;
+    FLAT_REQUIRE(s->out_order == 0 || s->out_order == 1, "out_order is 0 (RGBA) or 1 (BGRA)");
+    FLAT_REQUIRE(s->which_tables >= 0 && s->which_tables <= 3, "source which_tables is 0..3");
+    FLAT_REQUIRE(s->pb_quality >= 1 && s->pb_quality <= 3, "pb_quality is 1 (LOW), 2 (MED) or 3 (HIGH)");
+    FLAT_REQUIRE(!(s->flags & ~LGPU_YUV_FIX_EDGES), "unknown flags");
+    FLAT_REQUIRE(s->istrides[0] >= pr->sw && s->istrides[1] >= hw && s->istrides[2] >= hw, "plane rowstride smaller than a row");
+    FLAT_REQUIRE(s->u_size >= (long)(hh - 1) * s->istrides[1] + hw && s->v_size >= (long)(hh - 1) * s->istrides[2] + hw,
+                 "chroma plane smaller than its (sw / 2) x (sh / 2) samples");
+  }
   const int chain_order = (ys->out_order ^ (pr->swap_rb ? 1 : 0)) & 1;
+  FLAT_REQUIRE(!ys2 || ys2->out_order == chain_order, "src2->out_order must state the byte order the blend works in: src->out_order ^ params->swap_rb");
   const bool planar = sk && sk->out_fmt >= 4;
   const int nplanes = planar ? 3 : 1;
   int cw = pr->dw, ch = pr->dh;
@@ -252,26 +326,29 @@ static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv
     FLAT_REQUIRE(pr->sw < 32768 && pr->sh < 32768, "frame sides must stay below 32768");
     FLAT_REQUIRE(sk->in_order == chain_order, "sink->in_order must state the byte order of the chain's result: src->out_order ^ params->swap_rb");
     const int cwid = pr->dw >> 1;
-    FLAT_REQUIRE(noblend || pr->irow2 >= pr->dw * 4, "rowstride smaller than a row");
+    FLAT_REQUIRE(!l2rgba || pr->irow2 >= pr->dw * 4, "rowstride smaller than a row");
     FLAT_REQUIRE(sk->orow[0] >= (planar ? pr->dw : pr->dw * 2) && (!planar || (sk->orow[1] >= cwid && sk->orow[2] >= cwid)), "sink rowstride smaller than a row");
-    FLAT_REQUIRE(noblend || !(pr->irow2 & 3), "rowstrides must be multiples of 4");
+    FLAT_REQUIRE(!l2rgba || !(pr->irow2 & 3), "rowstrides must be multiples of 4");
   } else {
     if (cv) {
       FLAT_REQUIRE(cv->nwidth >= pr->dw && cv->nheight >= pr->dh && cv->offs_x >= 0 && cv->offs_y >= 0 && cv->offs_x + pr->dw <= cv->nwidth &&
                    cv->offs_y + pr->dh <= cv->nheight, "the frame must lie inside the canvas");
       cw = cv->nwidth; ch = cv->nheight;
     }
-    FLAT_REQUIRE(pr->orow >= cw * 4 && (noblend || pr->irow2 >= cw * 4), "rowstride smaller than a row");
-    FLAT_REQUIRE(((pr->orow | (noblend ? 0 : pr->irow2)) & 3) == 0, "rowstrides must be multiples of 4");
+    FLAT_REQUIRE(pr->orow >= cw * 4 && (!l2rgba || pr->irow2 >= cw * 4), "rowstride smaller than a row");
+    FLAT_REQUIRE(((pr->orow | (l2rgba ? pr->irow2 : 0)) & 3) == 0, "rowstrides must be multiples of 4");
   }
   uintptr_t pb = 0;
   for (int i = 0; i < ntracks; i++) {
     const lgpu_chain_yuv_sink_track &t = tracks[i];
-    FLAT_REQUIRE(t.y_d && t.u_d && t.v_d && (noblend || t.layer2_d), "null track pointer");
-    FLAT_REQUIRE(noblend || multiple_of((uintptr_t)t.layer2_d, 4), "layer 2 must be 4-byte aligned");
+    FLAT_REQUIRE(t.y_d && t.u_d && t.v_d && (!l2rgba || t.layer2_d), "null track pointer");
+    FLAT_REQUIRE(!l2rgba || multiple_of((uintptr_t)t.layer2_d, 4), "layer 2 must be 4-byte aligned");
+    FLAT_REQUIRE(!mix || (mix[i].y2_d && mix[i].u2_d && mix[i].v2_d), "null layer-2 plane");
     for (int k = 0; k < nplanes; k++) {
       FLAT_REQUIRE(t.dst_d[k], "null destination plane");
       FLAT_REQUIRE((const uint8_t *)t.dst_d[k] != t.y_d && (const uint8_t *)t.dst_d[k] != t.u_d && (const uint8_t *)t.dst_d[k] != t.v_d, "the chain cannot run in place");
+      FLAT_REQUIRE(!mix || ((const uint8_t *)t.dst_d[k] != mix[i].y2_d && (const uint8_t *)t.dst_d[k] != mix[i].u2_d && (const uint8_t *)t.dst_d[k] != mix[i].v2_d),
+                   "a destination plane is one of layer 2's planes");
     }
     FLAT_REQUIRE(sk || multiple_of((uintptr_t)t.dst_d[0], 4), "the destination must be 4-byte aligned");
     pb |= (uintptr_t)t.dst_d[0];
@@ -290,8 +367,8 @@ static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv
   }
   const long long lim = 1ll << 31;
   const int drow = sk ? sk->orow[0] : pr->orow;
-  if ((long long)pr->sh * lys >= lim || ys->u_size >= lim || ys->v_size >= lim || (long long)ch * drow >= lim || (!noblend && (long long)ch * pr->irow2 >= lim) ||
-      (planar && ((long long)(pr->dh >> 1) * sk->orow[1] >= lim || (long long)(pr->dh >> 1) * sk->orow[2] >= lim)))
+  if ((long long)pr->sh * lys >= lim || ys->u_size >= lim || ys->v_size >= lim || (long long)ch * drow >= lim || (l2rgba && (long long)ch * pr->irow2 >= lim) ||
+      (ys2 && ((long long)pr->sh * ys2->istrides[0] >= lim || ys2->u_size >= lim || ys2->v_size >= lim)) || (planar && ((long long)(pr->dh >> 1) * sk->orow[1] >= lim || (long long)(pr->dh >> 1) * sk->orow[2] >= lim)))
     FLAT_REFUSE("planes of 2 GiB or more");
   int rc;
   FlatArgs a;
@@ -300,7 +377,7 @@ static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv
   if (sk && (rc = get_sink_tables(sk->which_tables, sk->in_order, &a.stab))) return rc;
   a.tables = device_tables()->yuv2rgb[ys->which_tables & 3];
   a.usize = (uint32_t)ys->u_size; a.vsize = (uint32_t)ys->v_size; a.ys = lys; a.us = us; a.vs = vs; a.w = pr->sw; a.h = pr->sh;
-  a.orow = drow; a.irow2 = noblend ? 0 : pr->irow2;
+  a.orow = drow; a.irow2 = l2rgba ? pr->irow2 : 0;
   a.urow = planar ? sk->orow[1] : 0; a.vrow = planar ? sk->orow[2] : 0;
   if (cv) { a.cw = cv->nwidth; a.ch = cv->nheight; a.ox = cv->offs_x; a.oy = cv->offs_y; }
   a.clamped = !(ys->which_tables & 1); a.lowq = ys->pb_quality == 1; a.fix_edges = (ys->flags & LGPU_YUV_FIX_EDGES) ? 1 : 0; a.use_lut = pr->use_lut ? 1 : 0;
@@ -309,7 +386,7 @@ static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv
   const int nunits = pr->sh / 2 + 1;
   const unsigned gx = cdiv((unsigned)hw, 256u);
   const long long bar_px = cv ? (long long)cw * ch - (long long)pr->sw * pr->sh : 0;
-  const int per_launch = planar ? kFlatPlanarTracks : LGPU_CHAIN_MAX_TRACKS;
+  const int per_launch = ys2 ? LGPU_CHAIN_MIX_TRACKS : planar ? kFlatPlanarTracks : LGPU_CHAIN_MAX_TRACKS;
   hipStream_t st = (hipStream_t)stream;
   for (int t0 = 0; t0 < ntracks; t0 += per_launch) {
     const int n = std::min(per_launch, ntracks - t0);
@@ -321,7 +398,29 @@ static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv
     a.gy_units = gy;
     const unsigned bar_gy = bar_px > 0 ? (unsigned)std::min<long long>(64, (bar_px + 1024ll * gx - 1) / (1024ll * gx)) : 0u;
     const dim3 grid(gx, (unsigned)gy + bar_gy, (unsigned)n);
-    if (planar) {
+    if (ys2) {
+      // L2YUV: one staged copy of the K2 tables serves both layers when the sources name the same set
+      const bool own = (ys2->which_tables & 3) != (ys->which_tables & 3);
+      auto fill = [&](auto &T) {
+        for (int i = 0; i < n; i++) {
+          const lgpu_chain_yuv_mix_track &t = mix[t0 + i];
+          T.y[i] = t.y_d; T.u[i] = t.u_d; T.v[i] = t.v_d; T.y2[i] = t.y2_d; T.u2[i] = t.u2_d; T.v2[i] = t.v2_d; T.bf[i] = amounts[t0 + i];
+          for (int k = 0; k < nplanes; k++) T.dst[k][i] = t.dst_d[k];
+        }
+        T.tables2 = own ? device_tables()->yuv2rgb[ys2->which_tables & 3] : nullptr;
+        T.usize2 = (uint32_t)ys2->u_size; T.vsize2 = (uint32_t)ys2->v_size; T.ys2 = ys2->istrides[0]; T.us2 = ys2->istrides[1]; T.vs2 = ys2->istrides[2];
+        T.clamped2 = !(ys2->which_tables & 1); T.lowq2 = ys2->pb_quality == 1; T.fix_edges2 = (ys2->flags & LGPU_YUV_FIX_EDGES) ? 1 : 0;
+      };
+#define FLAT_MIX_LAUNCH(SK) do {                                                                                                             \
+        FlatTr<SK, 1>::type T;                                                                                                               \
+        memset(&T, 0, sizeof T);                                                                                                             \
+        fill(T);                                                                                                                             \
+        if (chain_order) hipLaunchKernelGGL((k_flat_yuv420<1, 1, SK, 1>), grid, dim3(256), 0, st, a, T, l);                                 \
+        else hipLaunchKernelGGL((k_flat_yuv420<1, 0, SK, 1>), grid, dim3(256), 0, st, a, T, l);                                             \
+      } while (0)
+      if (planar) FLAT_MIX_LAUNCH(2); else if (sk) FLAT_MIX_LAUNCH(1); else FLAT_MIX_LAUNCH(0);
+#undef FLAT_MIX_LAUNCH
+    } else if (planar) {
       FlatTr<2>::type T;
       for (int i = 0; i < n; i++) {
         const lgpu_chain_yuv_sink_track &t = tracks[t0 + i];
@@ -374,4 +473,19 @@ extern "C" int lgpu_chain_flat_yuv420p_to_yuv(const lgpu_chain_params *pr, const
   if (rc) return rc;
   LGPU_REQUIRE(pr && ys && sk && tracks && ntracks > 0 && ntracks <= LGPU_CHAIN_MAX_TRACKS, "params, source, sink and 1..64 tracks required");
   return flat_impl("lgpu_chain_flat_yuv420p_to_yuv", pr, ys, nullptr, sk, tracks, ntracks, amounts, stream);
+}
+
+// lgpu_chain_flat_yuv420p_mix: lgpu_yuv420p_to_rgb on each track's layer-2 planes (opsize 4, src2's settings, no LUT) + lgpu_chain_flat_yuv420p[_to_yuv] with that
+// frame as layer 2, as ONE launch per LGPU_CHAIN_MIX_TRACKS tracks and with no RGBA frame anywhere; every argument is checked before anything is enqueued
+extern "C" int lgpu_chain_flat_yuv420p_mix(const lgpu_chain_params *pr, const lgpu_yuv_source *ys, const lgpu_yuv_source *ys2, const lgpu_chain_sink *sk,
+                                           const lgpu_chain_yuv_mix_track *tracks, int ntracks, const uint8_t *amounts, void *stream) {
+  int rc = ensure_init();
+  if (rc) return rc;
+  LGPU_REQUIRE(pr && ys && ys2 && tracks && ntracks > 0 && ntracks <= LGPU_CHAIN_MAX_TRACKS, "params, both sources and 1..64 tracks required");
+  lgpu_chain_yuv_sink_track tr[LGPU_CHAIN_MAX_TRACKS];
+  for (int i = 0; i < ntracks; i++) {
+    tr[i].y_d = tracks[i].y_d; tr[i].u_d = tracks[i].u_d; tr[i].v_d = tracks[i].v_d; tr[i].layer2_d = nullptr;
+    for (int k = 0; k < 3; k++) tr[i].dst_d[k] = tracks[i].dst_d[k];
+  }
+  return flat_impl("lgpu_chain_flat_yuv420p_mix", pr, ys, nullptr, sk, tr, ntracks, amounts, stream, ys2, tracks);
 }

@@ -150,6 +150,12 @@ __device__ __forceinline__ uint32_t pb_chroma_rgba(uint32_t p1, uint32_t p2, uin
   const uint32_t hi = ((__umul24((s2 >> 8) & 0xFFu, bf) + __umul24((s1 >> 8) & 0xFFu, nbf))) & 0x0000FF00u;
   return lo | hi | (p1 & 0xFF000000u);
 }
+// the same blend where layer 2 is opaque by construction (a frame K2 has just converted: alpha 255): the integer expression alone, no float path to instantiate
+__device__ __forceinline__ uint32_t pb_chroma_opaque(uint32_t p1, uint32_t p2, uint32_t bf, uint32_t nbf) {
+  const uint32_t lo = ((__umul24(p2 & 0x00FF00FFu, bf) + __umul24(p1 & 0x00FF00FFu, nbf)) >> 8) & 0x00FF00FFu;
+  const uint32_t hi = ((__umul24((p2 >> 8) & 0xFFu, bf) + __umul24((p1 >> 8) & 0xFFu, nbf))) & 0x0000FF00u;
+  return lo | hi | (p1 & 0xFF000000u);
+}
 // [1 4 6 4 1] on packed 16-bit lanes, a + e + 4 (b + d) + 6 c + k, without a 32-bit multiply: the operands of the vertical pass exceed 24 bits, so `6u * c` became
 // v_mul_lo_u32 (a quarter of the vector rate); ((b + c + d) << 2) + (c << 1) + (a + e + k) is two v_add3 and two v_lshl_add
 __device__ __forceinline__ uint32_t gauss5_taps(uint32_t a, uint32_t b, uint32_t c, uint32_t d, uint32_t e, uint32_t k = 0u) { return ((b + c + d) << 2) + (c << 1) + (a + e + k); }

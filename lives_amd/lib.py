@@ -17,6 +17,7 @@ cd = ctypes.c_double
 u8p = ctypes.POINTER(ctypes.c_uint8)
 
 LGPU_CHAIN_MAX_TRACKS = 64
+LGPU_CHAIN_MIX_TRACKS = 32
 
 (SWAP3, SWAP4, SWAP3ADDPOST, SWAP3ADDPRE, SWAP3POSTALPHA, SWAP3PREALPHA, ADDPOST, ADDPRE, SWAP3DELPOST, DELPOST,
  DELPRE, SWAP3DELPRE, SWAPPREPOST) = range(13)
@@ -54,6 +55,11 @@ class ChainSinkTrack(ctypes.Structure):
 class ChainYuvSinkTrack(ctypes.Structure):
     """lgpu_chain_yuv_sink_track"""
     _fields_ = [("y_d", vp), ("u_d", vp), ("v_d", vp), ("layer2_d", vp), ("dst_d", vp * 3)]
+
+
+class ChainYuvMixTrack(ctypes.Structure):
+    """lgpu_chain_yuv_mix_track"""
+    _fields_ = [("y_d", vp), ("u_d", vp), ("v_d", vp), ("y2_d", vp), ("u2_d", vp), ("v2_d", vp), ("dst_d", vp * 3)]
 
 
 class YuvSource(ctypes.Structure):
@@ -170,6 +176,7 @@ PROTOTYPES = {
     "lgpu_chain_yuv420p_to_yuv": [vp, vp, vp, vp, ci, vp, vp],
     "lgpu_chain_flat_yuv420p": [vp, vp, vp, vp, ci, vp, vp],
     "lgpu_chain_flat_yuv420p_to_yuv": [vp, vp, vp, vp, ci, vp, vp],
+    "lgpu_chain_flat_yuv420p_mix": [vp, vp, vp, vp, vp, ci, vp, vp],
     "lgpu_pixbuf_scale_check": [ci, ci, ci, ci, ci, ci, vp],
     "lgpu_pixbuf_scale_batch": [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp],
     "lgpu_fx_batch": [ctypes.POINTER(FxParams), ctypes.POINTER(FxFrame), ci, vp],

@@ -510,6 +510,30 @@ def chain_flat_yuv420p_to_yuv(params, src, sink, tracks, amounts, check=True):
     return lib.call("lgpu_chain_flat_yuv420p_to_yuv", *args)
 
 
+def chain_yuv_mix_tracks(ys, us, vs, y2s, u2s, v2s, dst_planes):
+    """lgpu_chain_yuv_mix_track[]: the planes of each track's two 4:2:0 layers (u / v swapped for YVU420P, per layer) and its destination planes (one tensor for RGBA /
+    UYVY / YUYV; Y, U, V for YUV420P -- the chroma planes swapped for YVU420P)"""
+    n = len(ys)
+    arr = (lib.ChainYuvMixTrack * n)()
+    for i in range(n):
+        arr[i].y_d, arr[i].u_d, arr[i].v_d = ys[i].data_ptr(), us[i].data_ptr(), vs[i].data_ptr()
+        arr[i].y2_d, arr[i].u2_d, arr[i].v2_d = y2s[i].data_ptr(), u2s[i].data_ptr(), v2s[i].data_ptr()
+        for k, t in enumerate(dst_planes[i]):
+            arr[i].dst_d[k] = t.data_ptr()
+    return arr
+
+
+def chain_flat_yuv420p_mix(params, src, src2, tracks, amounts, sink=None, check=True):
+    """lgpu_chain_flat_yuv420p_mix: two decoded 4:2:0 frames of the project's size mixed in one launch, to RGBA (sink=None, rowstride params.orow) or to a YUV sink; no
+    RGBA frame anywhere.  src2 describes layer 2 (its out_order is src.out_order ^ params.swap_rb).  check=False returns the library's code instead of raising (tests
+    of the refusals)"""
+    am = (ctypes.c_uint8 * max(1, len(tracks)))(*[int(a) & 0xFF for a in amounts]) if amounts is not None else None
+    args = (ctypes.byref(params), ctypes.byref(src), ctypes.byref(src2), ctypes.byref(sink) if sink is not None else None, tracks, len(tracks), am, stream_ptr())
+    if not check:
+        return lib.load().lgpu_chain_flat_yuv420p_mix(*args)
+    return lib.call("lgpu_chain_flat_yuv420p_mix", *args)
+
+
 def stream_probe(params, tracks, reps):
     """lgpu_debug_stream_probe: the chain's algorithmic bytes as a bare stream on the same frames, ms for `reps` launches (destinations left dirty)"""
     ms = ctypes.c_float()
