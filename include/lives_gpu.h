@@ -269,6 +269,7 @@ int lgpu_colorkey(const uint8_t *src0_d, int irow0, const uint8_t *src1_d, int i
    dst_d / orow: one entry per destination plane.  which_tables: bit 0 unclamped, bit 1 BT.709 (4:2:0 / 4:2:2 only --
    the reference's other entry points are YCbCr only).  The reference's sampling is kept: U of the first and V of the
    second pixel of a pair, YUYV without the upper chroma clamp, 4:2:0 chroma row k = avg_chroma(row 2k+2, row 2k+1).
+   YUV422P converts height & ~1 rows, as 4:2:0 does: the reference trims the height to even for both (:6276-6277), so the last row of an odd frame is left alone.
    LGPU_E_UNSUPPORTED for ARGB32 -> 4:2:0 / 4:2:2 (the reference reads the wrong bytes there). */
 int lgpu_rgb_to_yuv(const uint8_t *src_d, int irow, int width, int height, int in_order, int in_alpha,
                     uint8_t *const dst_d[4], const int orow[4], int out_fmt, int out_alpha, int which_tables,

@@ -1448,6 +1448,7 @@ static int rgb_to_yuv_impl_n(const uint8_t *const *srcs, int irow, int width, in
   LGPU_REQUIRE(out_fmt != 4 || !(height & 1), "4:2:0 needs an even height");
   LGPU_REQUIRE(out_fmt >= 4 || !(which_tables & 2), "only the 4:2:0 / 4:2:2 conversions take a BT.709 subspace (the reference's other entry points are YCbCr only)");
   if (out_fmt >= 4 && in_order == 2) { set_error("ARGB32 -> planar 4:2:0 / 4:2:2 is declined: the reference reads the wrong bytes there (src/colourspace.c:6353)"); return LGPU_E_UNSUPPORTED; }
+  if (out_fmt == 5) height &= ~1;       // the reference trims vsize to even for 4:2:2 too (src/colourspace.c:6276-6277, quirk K4-f): an odd frame's last row is never written
   PalArgs a;
   __builtin_memset(&a, 0, sizeof a);
   const int ips = (in_order == 2 || in_alpha) ? 4 : 3;
@@ -1471,7 +1472,7 @@ static int rgb_to_yuv_impl_n(const uint8_t *const *srcs, int irow, int width, in
     if (out_fmt == 2 || out_fmt == 3) LGPU_REQUIRE(!((uintptr_t)dsts[f][0] & 3), "UYVY / YUYV rows must be 4-byte aligned");
   }
   const int npairs = width >> 1;
-  if (npairs == 0) return LGPU_OK;
+  if (npairs == 0 || height == 0) return LGPU_OK;
   // aligned 4-byte pixels -> 4:2:0: the cell form
   if (out_fmt == 4 && ips == 4 && in_order <= 1 && (width & 3) == 0 && height >= 2 &&
       (sbits & 15) == 0 && (d0bits & 3) == 0 && (d12bits & 1) == 0) {

@@ -717,8 +717,11 @@ int orc_rgb_to_yuv(const uint8_t *src, int irow, int width, int height, int in_o
     }
     return 0;
   }
-  /* pair formats: rgb2uyvy / rgb2yuyv (:2162-2192): U from the first pixel, V from the second */
-  for (int y = 0; y < height; y++) {
+  /* pair formats: rgb2uyvy / rgb2yuyv (:2162-2192): U from the first pixel, V from the second.
+     convert_rgb_to_yuv420_frame trims vsize to even for 4:2:2 as well (:6276-6277, quirk K4-f): the last row of an odd-height
+     YUV422P frame is never written, in any of the three planes */
+  const int rows = out_fmt == 5 ? height & ~1 : height;
+  for (int y = 0; y < rows; y++) {
     const uint8_t *s = src + (size_t)y * irow;
     for (int x = 0; x < width; x += 2) {
       int r1, g1, b1;

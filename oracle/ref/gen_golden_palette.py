@@ -78,6 +78,23 @@ def main():
             rec[key + "|i%d" % i] = a
         rec[key + "|out"] = out
         names.append(key)
+    # odd heights into YUV422P: convert_rgb_to_yuv420_frame trims vsize to even for 4:2:2 too (:6276-6277, quirk K4-f), so the last row of all three
+    # planes keeps the 0x5A pre-fill, and a one-row frame is left untouched.  Own seed stream, after every older record: those keep their bytes.
+    rng5 = np.random.default_rng(0x4221F)
+    for (w, h) in ((12, 5), (6, 1)):
+        for in_order in (0, 1):
+            for in_alpha in (0, 1):
+                for which in (0, 3):
+                    src = po.make_frame(rng5, w, h, 4 if in_alpha else 3)
+                    src[0, :2 * (4 if in_alpha else 3)] = [0] * (4 if in_alpha else 3) + [255] * (4 if in_alpha else 3)
+                    out, _ = po.k4_out_planes(0x5A, w, h, 5, 0)
+                    op, os_ = po.planes_args(out)
+                    assert R.csref_k4(in_order, in_alpha, 5, 0, P(src), src.strides[0], w, h, ctypes.addressof(op), ctypes.addressof(os_), which & 1, which >> 1) == 0
+                    key = "k4|%d|%d|%d|%d|%d|%d|%d" % (in_order, in_alpha, 5, 0, which, w, h)
+                    rec[key + "|in"] = src
+                    for i, a in enumerate(out):
+                        rec[key + "|o%d" % i] = a
+                    names.append(key)
     t = [np.zeros(256, np.uint8) for _ in range(4)]                     # K5 tables (init_YUV_to_YUV_tables, :1108-1139)
     R.csref_yuv_yuv_tables(*[P(x) for x in t])
     np.savez_compressed(os.path.join(OUT, "yuvyuv.npz"), yc2u=t[0], uvc2u=t[1], yu2c=t[2], uvu2c=t[3])
@@ -87,7 +104,8 @@ def main():
     man = json.load(open(mpath))
     man["groups"]["k34_palette.npz"] = ("src/colourspace.c:5129-6440 (RGB/BGR/ARGB -> YUV888, YUVA8888, YUV(A)444(4)P, UYVY, YUYV, YUV420P, YUV422P; record "
                                         "k4|in_order|in_alpha|out_fmt|out_alpha|which|w|h) and :2750-3258, :6616-7102, :7200-7498 (the reverse; record "
-                                        "k3|in_fmt|in_alpha|out_order|out_alpha|which|w|h); which: bit0 unclamped, bit1 BT.709; nfx_threads = 1; compact destination strides")
+                                        "k3|in_fmt|in_alpha|out_order|out_alpha|which|w|h); which: bit0 unclamped, bit1 BT.709; nfx_threads = 1; compact destination strides; "
+                                        "the k4 records with out_fmt 5 at 12x5 and 6x1 pin the height trim of 4:2:2 (:6276-6277): the last row of an odd-height frame keeps the 0x5A pre-fill")
     man["groups"]["yuvyuv.npz"] = "src/colourspace.c:1108-1139 init_YUV_to_YUV_tables: Yclamped_to_Yunclamped, UVclamped_to_UVunclamped, Yunclamped_to_Yclamped, UVunclamped_to_UVclamped"
     json.dump(man, open(mpath, "w"), indent=1)
     print("k34_palette.npz: %d records, %d KB" % (len(names), os.path.getsize(os.path.join(OUT, "k34_palette.npz")) // 1024))
