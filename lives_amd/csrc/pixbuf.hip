@@ -474,6 +474,7 @@ template <> struct PbExtraArg<1, 1> { typedef PbYuvSink type; };
 template <> struct PbExtraArg<1, 2> { typedef PbYuvSink type; };
 template <> struct PbExtraArg<0, 0> { typedef PbYuvArg<0>::type type; };
 template <> struct PbExtraArg<1, 0> { typedef PbYuvArg<1>::type type; };
+template <bool B> struct PbFlag { static constexpr bool value = B; };       // a compile-time flag as a lambda argument
 template <int SINK> struct PbSinkLds { pb_u2 t[6 * 256]; };
 template <> struct PbSinkLds<0> {};
 
@@ -931,11 +932,13 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
   }
   // carry[i] = (outer tap) * H[first row] + (inner tap) * H[second row] of a scaled row: the half that is known before its last two source rows arrive
   uint32_t carry[8], hr[8], hs[8];
+  // requested in the row loop's own order -- rows, layer-2 pixels, edge pixels -- and the edge pixels of the two rows that the set-up below consumes LAST: when the
+  // loop is entered nothing of this is outstanding, so the wait counts of its first half are those of the trip before it and not a compromise with this entry
   pb_u4 q0 = load_row(S0), q1 = load_row(S0 + d), qa = load_row(S0 + 2 * d), qb = load_row(S0 + 3 * d);
-  uint32_t e0 = load_e(S0), e1 = load_e(S0 + d), ea = load_e(S0 + 2 * d), eb = load_e(S0 + 3 * d);
   pb_u2 l2;
   l2.x = 0; l2.y = 0;
   if (CHAIN == 1 && !fastp) l2 = load_l2(d > 0 ? y0 : y0 + rows - 1);
+  uint32_t ea = load_e(S0 + 2 * d), eb = load_e(S0 + 3 * d), e0 = load_e(S0), e1 = load_e(S0 + d);
   if (CHAIN) {        // the two small tables, requested while the first source rows are in flight; first read an output row later
     reinterpret_cast<uint32_t *>(s_lut)[lane] = lut.w[lane];
 #pragma unroll
@@ -981,32 +984,43 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
 
   if (!BLUR) {
     // two scaled rows per trip, the source rows of one in (qa, qb), of the other in (na, nb): a row's loads land in the registers its arithmetic reads, issued a whole
-    // row of arithmetic earlier, and nothing is moved between registers
+    // row of arithmetic earlier, and nothing is moved between registers.  Whether a row step prefetches is a COMPILE-TIME argument (more): the loop runs while two more
+    // rows follow, both of its halves requesting without a condition, and the band's last one or two rows are peeled behind it.  Under a run-time `if (r + 1 < rows)`
+    // the wait-count pass has to choose one vmcnt for the path with the requests and the path without, and chooses the latter: the second half of every trip then
+    // waited for the source row it had requested a few instructions before (tools/isa_waits.py, tests/test_pbh_wait_counts.py, profiles/r13/pbh_row_pipeline.md)
     pb_u4 na = qa, nb = qb;
     uint32_t nea = 0, neb = 0;
     pb_u2 nl2;
     nl2.x = 0; nl2.y = 0;
-    auto one = [&](int r, pb_u4 &ca, pb_u4 &cb, uint32_t &cea, uint32_t &ceb, pb_u2 &cl2, pb_u4 &xa, pb_u4 &xb, uint32_t &xea, uint32_t &xeb, pb_u2 &xl2) __attribute__((always_inline)) {
+    auto one = [&](auto more, int r, pb_u4 &ca, pb_u4 &cb, uint32_t &cea, uint32_t &ceb, pb_u2 &cl2, pb_u4 &xa, pb_u4 &xb, uint32_t &xea, uint32_t &xeb, pb_u2 &xl2) __attribute__((always_inline)) {
       const int yy = d > 0 ? ystart + r : ystart - r;
-      if (r + 1 < rows) {       // the next scaled row's two new source rows and the layer-2 pixels of the next output row: in flight during this row's arithmetic
+      // a row step is a scheduling region of its own (the run-time branch used to see to that): otherwise the copy of this step's edge pixel, which the lane exchange
+      // makes before it overwrites one, is moved up into the step before, behind the request for that pixel, and takes a wait for the whole request with it
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (decltype(more)::value) {
+        // the next scaled row's two new source rows, the layer-2 pixels of the next output row and the strip's edge pixels (HYPER strips of 64 quads; 0 otherwise):
+        // in flight during this row's arithmetic.  The edge pixels are redefined by every step that has a successor, so the lane exchange may overwrite them where they lie
         xa = load_row(S0 + d * (2 * r + 4)); xb = load_row(S0 + d * (2 * r + 5));
         if (CHAIN == 1) xl2 = load_l2(yy + d);
+        xea = load_e(S0 + d * (2 * r + 4)); xeb = load_e(S0 + d * (2 * r + 5));
       }
-      // the strip's edge pixels (HYPER strips of 64 quads; 0 otherwise) are requested on the band's last row too -- 4 bytes in two lanes, the row index clamped into
-      // the frame, never used: each is then redefined on every trip, so the lane exchange may overwrite it where it lies instead of working on a copy
-      xea = load_e(S0 + d * (2 * r + 4)); xeb = load_e(S0 + d * (2 * r + 5));
       uint32_t cc[2][3], al[2];
       scale_row(ca, cb, cea, ceb, cc, al);
       if constexpr (SINK) sink_row(yy, finish(cc[0][0], cc[0][1], cc[0][2], al[0], cl2.x), finish(cc[1][0], cc[1][1], cc[1][2], al[1], cl2.y));
       else
       store_row(yy, finish(cc[0][0], cc[0][1], cc[0][2], al[0], cl2.x), finish(cc[1][0], cc[1][1], cc[1][2], al[1], cl2.y));
     };
+    const PbFlag<true> more;
+    const PbFlag<false> last;
     int r = 0;
-    for (; r + 1 < rows; r += 2) {
-      one(r, qa, qb, ea, eb, l2, na, nb, nea, neb, nl2);
-      one(r + 1, na, nb, nea, neb, nl2, qa, qb, ea, eb, l2);
+    for (; r + 2 < rows; r += 2) {
+      one(more, r, qa, qb, ea, eb, l2, na, nb, nea, neb, nl2);
+      one(more, r + 1, na, nb, nea, neb, nl2, qa, qb, ea, eb, l2);
     }
-    if (r < rows) one(r, qa, qb, ea, eb, l2, na, nb, nea, neb, nl2);
+    if (r + 1 < rows) {
+      one(more, r, qa, qb, ea, eb, l2, na, nb, nea, neb, nl2);
+      one(last, r + 1, na, nb, nea, neb, nl2, qa, qb, ea, eb, l2);
+    } else if (r < rows) one(last, r, qa, qb, ea, eb, l2, na, nb, nea, neb, nl2);
     return;
   }
 
