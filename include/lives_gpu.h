@@ -545,6 +545,29 @@ typedef struct { const uint8_t *y_d, *u_d, *v_d;      /* layer 1 */
 int lgpu_chain_flat_yuv420p_mix(const lgpu_chain_params *params, const lgpu_yuv_source *src, const lgpu_yuv_source *src2,
                                 const lgpu_chain_sink *sink /* NULL: RGBA into dst_d[0], rowstride params->orow */,
                                 const lgpu_chain_yuv_mix_track *tracks, int ntracks, const uint8_t *amounts, void *stream);
+/* the unscaled tick from 4:2:2 frames as ONE launch -- planar YUV422P (MJPEG, DV and the 4:2:2 intermediates decode to it) or packed UYVY / YUYV (what a capture
+   card or camera delivers): the same kernel under another source policy, and again no RGBA frame is read or written in between.  The bytes are those of
+     YUV422P: lgpu_yuv420p_to_rgb(.., opsize 4, src->out_order, is_422 = 1, src->which_tables, src->pb_quality, no LUT, flags 0) into a tight sw x sh RGBA frame
+              (every quirk of that walk kept: the first pair of row i takes its left chroma samples from chroma row i >> 1, the read one past a row's end is the next
+              row's first sample or is clamped to the plane's last byte);
+     packed:  lgpu_yuv_to_rgb(.., src->in_fmt, in_alpha 0, .., src->out_order, out_alpha 1, src->which_tables) into a tight sw x sh RGBA frame (chroma replicated);
+   then lgpu_chain_amounts with sw == dw, sh == dh and [canvas] (LGPU_INTERP_PIXBUF required; LGPU_INTERP_NOBLEND: no layer 2, amounts may be NULL; layer 2 is the
+   RGBA frame of rowstride params->irow2); with a sink, then lgpu_rgb_to_yuv(.., sink->in_order, 1, .., sink->out_fmt, 0, sink->which_tables) with sink->in_order ==
+   src->out_order ^ params->swap_rb.  Without a sink the result is RGBA in dst_d[0] with rowstride params->orow.  A packed frame is tracks[].y_d with rowstride
+   src->istrides[0]; u_d / v_d are not read.  src->pb_quality is checked and changes nothing (as in lgpu_yuv420p_to_rgb's 4:2:2 walk).  LGPU_E_BADARG: what
+   lgpu_chain_flat_yuv420p[_to_yuv] call a bad argument; another in_fmt; which_tables & 2 with a packed source (as lgpu_yuv_to_rgb); a YUV422P chroma plane smaller
+   than (sh - 1) * stride + sw / 2 or a null u_d / v_d with YUV422P; a canvas together with a sink; a destination plane that is one of the source planes.
+   LGPU_E_UNSUPPORTED: sw != dw or sh != dh, do_blur, out_fmt 5, an odd dh with out_fmt 4, the sinks' store-alignment classes, planes of 2 GiB or more, a packed
+   source whose plane or rowstride is not a multiple of 4 (a macropixel is one 4-byte load; the reference divides that rowstride by 4).  Nothing is enqueued or
+   written in either case.  Up to 64 tracks in one launch, to YUV420P 32 per launch (two launches on `stream` from 33 on). */
+typedef struct { int in_fmt;              /* 2 UYVY, 3 YUYV, 5 YUV422P: the numbers lgpu_rgb_to_yuv gives these palettes */
+                 int istrides[3];         /* packed: [0] only */
+                 long u_size, v_size;     /* YUV422P: chroma plane bytes (sh rows); packed: ignored */
+                 int out_order, which_tables, pb_quality; } lgpu_yuv422_source;
+int lgpu_chain_flat_yuv422(const lgpu_chain_params *params, const lgpu_yuv422_source *src, const lgpu_canvas *canvas /* RGBA only */,
+                           const lgpu_chain_sink *sink /* NULL: RGBA into dst_d[0], rowstride params->orow */,
+                           const lgpu_chain_yuv_sink_track *tracks /* packed: y_d is the frame, u_d / v_d NULL */, int ntracks,
+                           const uint8_t *amounts, void *stream);
 
 /* ---- timing helper: HIP events on `stream` around `reps` launches of the last-configured chain; used by
    bench.py to measure the kernel's average launch duration on the stream it is launched on. */

@@ -168,7 +168,12 @@ int lives_gpu_set_deferred(int on);
    project's size, letterboxed or not -- with a swap, letterbox, blend or gamma table behind the conversion as ONE lgpu_chain_flat_yuv420p launch instead of the
    batched conversion followed by lgpu_chain_amounts, and such a group (no canvas) that ends in a UYVY / YUYV / YUV420P / YVU420P sink as ONE
    lgpu_chain_flat_yuv420p_to_yuv launch instead of three; no RGBA frame is written.  Same bytes either way (tests/test_deferred_flat.py); shapes the one-launch
-   forms refuse, and LGPU_SEAM_STAGED, keep today's launches.  A process-wide setting like lives_gpu_set_deferred. */
+   forms refuse, and LGPU_SEAM_STAGED, keep today's launches.  With the switch on -- and only then -- convert_layer_palette[_full] of a pinned YUV422P, UYVY or YUYV
+   layer to RGBA32 / BGRA32 without a gamma change is recorded as the program's first stage too (a packed layer has one plane and its width leaf counts macropixels:
+   the RGBA frame is twice as wide; every leaf changes as in the eager call), and a group of such programs that keeps its size runs as ONE lgpu_chain_flat_yuv422
+   launch, with or without such a sink, counted as its 4:2:0 siblings are ([13] / [14] below).  A scaled group, a conversion alone or LGPU_SEAM_STAGED take
+   lgpu_yuv420p_to_rgb_batch (is_422) / lgpu_yuv_to_rgb_batch into scratch and the RGBA paths: the 2:1 YUV chains are 4:2:0 only (tests/test_deferred_flat422.py).
+   With the switch off nothing is recorded for these palettes.  A process-wide setting like lives_gpu_set_deferred. */
 int lives_gpu_set_flat_yuv(int on);
 int lives_gpu_layers_flush(lives_gpu_layer_t *const *layers, int nlayers);
 /* counters since load: [0] stages recorded, [1] fused chain launches made for pending programs, [2] programs (tracks) those carried, [3] programs run stage by stage */
@@ -179,7 +184,8 @@ void lives_gpu_deferred_stats(unsigned long long out[4]);
    lgpu_rgb_to_yuv_batch / lgpu_rgb_to_yuv -- and [10] the tracks they carried, [11] how many of [9] were fused launches, [12] launches that ran from YUV planes to
    YUV planes (lgpu_chain_yuv420p_to_yuv: a group of programs that start at a YUV420P / YVU420P conversion, have the exact 2:1 scale, no canvas and end in the sink;
    each is also counted in [1], [5], [9] and [11] with its tracks in [2], [6] and [10], and makes no pre-launch [7]), [13] launches of the unscaled one-launch forms
-   (lives_gpu_set_flat_yuv(1): lgpu_chain_flat_yuv420p, also counted in [1]; lgpu_chain_flat_yuv420p_to_yuv, also counted in [1], [9] and [11]; no pre-launch [7]) and
+   (lives_gpu_set_flat_yuv(1): lgpu_chain_flat_yuv420p, also counted in [1]; lgpu_chain_flat_yuv420p_to_yuv, also counted in [1], [9] and [11]; lgpu_chain_flat_yuv422
+   from YUV422P / UYVY / YUYV layers, counted as whichever of the two it stands for, its conversions in [4] and its batched fallback conversions in [7]; no pre-launch [7]) and
    [14] the tracks they carried; at most n entries are written (callers that pass n = 12 or 13 see what they saw before) */
 void lives_gpu_deferred_stats_n(unsigned long long *out, int n);
 /* (for livesgpu_fx.so) record an in-place "chroma blend" of the pending plane dst_host with the resident plane layer2_host; 1 = recorded, 0 = run the kernel */

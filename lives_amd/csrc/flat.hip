@@ -15,6 +15,9 @@
 //
 // lgpu_chain_flat_yuv420p_mix (the L2YUV policy): layer 2 is a decoded 4:2:0 frame of the same size.  The lane that owns a cell of layer 1 owns the same cell of layer
 // 2 and converts it with the same walk (flat_cell) under layer 2's own description; 1.5 + 1.5 + 4 bytes per pixel to RGBA and no RGBA frame anywhere.
+//
+// lgpu_chain_flat_yuv422 (the SRC policy): layer 1 is a planar 4:2:2 frame (YUV422P) or a packed one (UYVY / YUYV).  The unit walk, emit and the sink stores stay; a lane
+// converts its two pixels of each row of its unit with flat_row422 -- yuv.hip's 4:2:2 walk with the reference's seed quirk, or K3's macropixel conversion.
 #include "lgpu_common.h"
 #include <algorithm>
 #include <string.h>
@@ -39,7 +42,9 @@ struct FlatArgs {
   int clamped, lowq, fix_edges, use_lut;
   int fmt, unclamped;            // sink: 2 UYVY, 3 YUYV, 4 YUV420P
   int gy_units, per;             // blockIdx.y < gy_units: the workgroup walks units [y * per, (y + 1) * per); the others write the canvas's bars
+  int sfmt;                      // SRC == 2: 2 UYVY, 3 YUYV (wave-uniform, as fmt is for the sink).  It sits in what was the struct's tail padding: no other offset moves
 };
+static_assert(sizeof(FlatArgs) == 112, "the argument layout of the SRC == 0 instantiations is fixed (docs/KERNELS.md, k_flat_yuv420<.., SRC>)");
 template <int NT, int NDST> struct FlatTracksT {
   const uint8_t *y[NT], *u[NT], *v[NT], *l2[NT];
   uint8_t *dst[NDST][NT];
@@ -153,11 +158,78 @@ __device__ __forceinline__ void flat_cell(const FlatPlanes &P, const FlatK2Lds &
   }
 }
 
+// one row's pixel pair of cell k of a 4:2:2 frame (the SRC policies of k_flat_yuv420).
+// SRC == 1, planar (YUV422P): yuv.hip's yuv422_cell walk (:3593-3640 / :3858-3901).  "this / last" are seeded from chroma row i >> 1 (reference), so the first pair of a
+// row takes its left samples from there; the read one past a row's end is the next row's first sample or is clamped to the plane's last byte; pb_quality and
+// LGPU_YUV_FIX_EDGES change nothing in this walk.  THE 4:2:2 SEED QUIRK IS NOW WRITTEN DOWN TWICE (yuv.hip yuv422_cell / k_yuv420p_to_rgb_s<.., V422>, and here): a quirk
+// changed there must change here too.
+// SRC == 2, packed (UYVY / YUYV): K3's conversion (palette.hip k_yuv_to_rgb / k_uyvy_to_rgb_s, uyvy2rgb :2410-2415, yuyv2rgb :2418-2423): both pixels of a macropixel
+// under its own U and V, no interpolation and no chroma clamp (the host stages the tables with the identity index); one aligned dword per lane and row
+template <int SWAP, int SRC>
+__device__ __forceinline__ void flat_row422(const FlatPlanes &P, const FlatK2Lds &L, int sfmt, int i, int k, uint32_t &p0, uint32_t &p1) {
+  auto px = [&](uint32_t yv, uint32_t iu, uint32_t iv) -> uint32_t {
+    const uint32_t yy = L.ty[yv];
+    const uint2 rg = L.rg[iv], gb = L.gb[iu];
+    uint32_t r, g, b;
+    yuv_rgb(yy, rg.x, rg.y, gb.x, gb.y, r, g, b);
+    return SWAP ? (b | (g << 8) | (r << 16) | 0xFF000000u) : (r | (g << 8) | (b << 16) | 0xFF000000u);
+  };
+  if constexpr (SRC == 2) {
+    const uint32_t m = *reinterpret_cast<const uint32_t *>(P.y + (size_t)i * P.ys + 4 * (size_t)k);
+    uint32_t y0, y1, u, v;
+    if (sfmt == 2) { u = m & 0xFF; y0 = (m >> 8) & 0xFF; v = (m >> 16) & 0xFF; y1 = m >> 24; }
+    else { y0 = m & 0xFF; u = (m >> 8) & 0xFF; y1 = (m >> 16) & 0xFF; v = m >> 24; }
+    p0 = px(y0, u, v); p1 = px(y1, u, v);
+  } else {
+    const uint8_t *pu = P.u, *pv = P.v;
+    auto PU = [&](int r, int kk) -> uint32_t { long q = (long)r * P.us + kk; return pu[q < (long)P.usize ? q : (long)P.usize - 1]; };
+    auto PV = [&](int r, int kk) -> uint32_t { long q = (long)r * P.vs + kk; return pv[q < (long)P.vsize ? q : (long)P.vsize - 1]; };
+    uint16_t yy;
+    __builtin_memcpy(&yy, P.y + (size_t)i * P.ys + 2 * k, 2);
+    const long ou = (long)i * P.us + k, ov = (long)i * P.vs + k;
+    uint32_t tu, lu, nu, tv, lv, nv;
+    if (k >= 2 && ou + 3 <= (long)P.usize && ov + 3 <= (long)P.vsize) {
+      // interior: one 4-byte window (columns k - 1 .. k + 2, the last unused) per chroma plane
+      uint32_t wu, wv;
+      __builtin_memcpy(&wu, pu + (ou - 1), 4); __builtin_memcpy(&wv, pv + (ov - 1), 4);
+      lu = wu & 0xFF; tu = (wu >> 8) & 0xFF; nu = (wu >> 16) & 0xFF;
+      lv = wv & 0xFF; tv = (wv >> 8) & 0xFF; nv = (wv >> 16) & 0xFF;
+    } else {
+      tu = k ? PU(i, k) : PU(i >> 1, 0); tv = k ? PV(i, k) : PV(i >> 1, 0);
+      lu = (k >= 2) ? PU(i, k - 1) : PU(i >> 1, 0); lv = (k >= 2) ? PV(i, k - 1) : PV(i >> 1, 0);
+      nu = PU(i, k + 1); nv = PV(i, k + 1);
+    }
+    p0 = px(yy & 0xFFu, (tu + lu) >> 1, (tv + lv) >> 1);
+    p1 = px((uint32_t)yy >> 8, (tu + nu) >> 1, (tv + nv) >> 1);
+  }
+}
+
+// the unit walk of flat_cell over a 4:2:2 frame: the same cells go to out() -- row 0, a row pair, the trailing row -- each row converted on its own
+template <int SWAP, int SRC, class Out>
+__device__ __forceinline__ void flat_cell422(const FlatPlanes &P, const FlatK2Lds &L, int sfmt, int unit, int k, int H, int npairs, Out &&out) {
+  uint32_t a0, a1, b0, b1;
+  if (unit == 0) {
+    flat_row422<SWAP, SRC>(P, L, sfmt, 0, k, a0, a1);
+    out(FlatCell<0>(), 0, 0, a0, a1, 0u, 0u);
+  } else if (unit <= npairs) {
+    const int i = 2 * unit - 1;
+    flat_row422<SWAP, SRC>(P, L, sfmt, i, k, a0, a1);
+    flat_row422<SWAP, SRC>(P, L, sfmt, i + 1, k, b0, b1);
+    out(FlatCell<1>(), i, unit - 1, a0, a1, b0, b1);
+  } else {
+    flat_row422<SWAP, SRC>(P, L, sfmt, H - 1, k, a0, a1);
+    out(FlatCell<2>(), H - 1, (H - 1) >> 1, a0, a1, 0u, 0u);
+  }
+}
+
 // SINK: 0 RGBA, 1 packed 4:2:2 (UYVY / YUYV), 2 planar 4:2:0.  SWAP: the finished pixel is BGRA (src->out_order ^ params->swap_rb).  L2YUV: layer 2 is a 4:2:0 frame
 // of the same size (BLEND is 1, no canvas): the lane converts ITS cell of layer 2 first, with the same walk, keeps the two or four finished pixels and only then
-// walks layer 1, so the temporaries of the two walks are never live together.  Layer 2's alpha is 255 by construction: the blend is the opaque one
-template <int BLEND, int SWAP, int SINK, int L2YUV = 0>
+// walks layer 1, so the temporaries of the two walks are never live together.  Layer 2's alpha is 255 by construction: the blend is the opaque one.
+// SRC: layer 1 is 0 planar 4:2:0, 1 planar 4:2:2 (YUV422P), 2 packed 4:2:2 (A.sfmt: UYVY / YUYV; T.y is the frame, T.u / T.v are not read).  The units, emit and
+// the chroma-row stores are the same for all three: a 4:2:2 lane owns two pixels of each row of its unit too (flat_cell422)
+template <int BLEND, int SWAP, int SINK, int L2YUV = 0, int SRC = 0>
 __global__ __launch_bounds__(256) void k_flat_yuv420(const FlatArgs A, const typename FlatTr<SINK, L2YUV>::type T, const Lut8 lut) {
+  static_assert(SRC >= 0 && SRC <= 2 && !(SRC && L2YUV), "layer 2 of the mix form is a 4:2:0 frame beside a 4:2:0 layer 1");
   __shared__ uint32_t s_ty[256];
   __shared__ uint2 s_rg[256], s_gb[256];
   __shared__ __attribute__((aligned(16))) uint8_t s_lut[256];
@@ -263,7 +335,7 @@ __global__ __launch_bounds__(256) void k_flat_yuv420(const FlatArgs A, const typ
         q[0] = a0; q[1] = a1; q[2] = b0; q[3] = b1;
       });
     }
-    flat_cell<SWAP>(P1, L1, unit, k, hw, H, npairs, [&](auto cell, int i, int r, uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1) __attribute__((always_inline)) {
+    auto rows = [&](auto cell, int i, int r, uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1) __attribute__((always_inline)) {
       constexpr int kind = decltype(cell)::value;
       emit(i, a0, a1, q[0], q[1], cu0, cv0);       // row 0's chroma is never kept
       if constexpr (kind == 1) {
@@ -278,7 +350,9 @@ __global__ __launch_bounds__(256) void k_flat_yuv420(const FlatArgs A, const typ
         T.dst[1][z][(size_t)r * A.urow + k] = (uint8_t)cu0;
         T.dst[2][z][(size_t)r * A.vrow + k] = (uint8_t)cv0;
       }
-    });
+    };
+    if constexpr (SRC == 0) flat_cell<SWAP>(P1, L1, unit, k, hw, H, npairs, rows);
+    else flat_cell422<SWAP, SRC>(P1, L1, A.sfmt, unit, k, H, npairs, rows);
   }
 }
 
@@ -286,11 +360,12 @@ __global__ __launch_bounds__(256) void k_flat_yuv420(const FlatArgs A, const typ
 
 using namespace lgpu;
 
-// all three entry points: tracks in the sink form's layout (the RGBA form's destination is dst_d[0]); cv or sk is null.  ys2 / mix: the second source and the
-// caller's tracks of lgpu_chain_flat_yuv420p_mix (layer 2's planes are read from them; tracks[].layer2_d is null then), null otherwise
+// all four entry points: tracks in the sink form's layout (the RGBA form's destination is dst_d[0]); cv or sk is null.  ys2 / mix: the second source and the
+// caller's tracks of lgpu_chain_flat_yuv420p_mix (layer 2's planes are read from them; tracks[].layer2_d is null then), null otherwise.  sfmt: layer 1's format,
+// 4 planar 4:2:0, 5 planar 4:2:2, 2 UYVY, 3 YUYV (lgpu_chain_flat_yuv422; a packed frame is tracks[].y_d with rowstride ys->istrides[0], the rest of ys unread)
 static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv_source *ys, const lgpu_canvas *cv, const lgpu_chain_sink *sk,
                      const lgpu_chain_yuv_sink_track *tracks, int ntracks, const uint8_t *amounts, void *stream, const lgpu_yuv_source *ys2 = nullptr,
-                     const lgpu_chain_yuv_mix_track *mix = nullptr) {
+                     const lgpu_chain_yuv_mix_track *mix = nullptr, int sfmt = 4) {
 #define FLAT_REQUIRE(cond, msg) do { if (!(cond)) { set_error("%s: %s", fn, msg); return LGPU_E_BADARG; } } while (0)
 #define FLAT_REFUSE(msg) do { set_error("%s: %s", fn, msg); return LGPU_E_UNSUPPORTED; } while (0)
   const bool noblend = (pr->interp & LGPU_INTERP_NOBLEND) != 0;
@@ -300,16 +375,24 @@ static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv
   FLAT_REQUIRE(amounts || noblend, "null amounts");
   // the sources' own (lgpu_chain_yuv420p)
   FLAT_REQUIRE(pr->sw >= 2 && !(pr->sw & 1) && pr->sh >= 1 && pr->dw > 0 && pr->dh > 0, "empty geometry or an odd 4:2:0 width");
-  const int hw = pr->sw >> 1, hh = (pr->sh + 1) >> 1, lys = ys->istrides[0], us = ys->istrides[1], vs = ys->istrides[2];
+  const bool packed = sfmt == 2 || sfmt == 3;
+  const int srcp = packed ? 2 : sfmt == 5 ? 1 : 0;      // the kernel's SRC policy
+  const int hw = pr->sw >> 1, hh = srcp ? pr->sh : (pr->sh + 1) >> 1, lys = ys->istrides[0], us = packed ? 0 : ys->istrides[1], vs = packed ? 0 : ys->istrides[2];
+  const long usz = packed ? 0 : ys->u_size, vsz = packed ? 0 : ys->v_size;
   for (const lgpu_yuv_source *s : {ys, ys2}) {
     if (!s) continue;
     FLAT_REQUIRE(s->out_order == 0 || s->out_order == 1, "out_order is 0 (RGBA) or 1 (BGRA)");
     FLAT_REQUIRE(s->which_tables >= 0 && s->which_tables <= 3, "source which_tables is 0..3");
     FLAT_REQUIRE(s->pb_quality >= 1 && s->pb_quality <= 3, "pb_quality is 1 (LOW), 2 (MED) or 3 (HIGH)");
     FLAT_REQUIRE(!(s->flags & ~LGPU_YUV_FIX_EDGES), "unknown flags");
+    if (packed) {
+      FLAT_REQUIRE(!(s->which_tables & 2), "UYVY / YUYV are converted with the YCbCr tables only (as lgpu_yuv_to_rgb)");
+      FLAT_REQUIRE(s->istrides[0] >= pr->sw * 2, "plane rowstride smaller than a row");
+      continue;
+    }
     FLAT_REQUIRE(s->istrides[0] >= pr->sw && s->istrides[1] >= hw && s->istrides[2] >= hw, "plane rowstride smaller than a row");
     FLAT_REQUIRE(s->u_size >= (long)(hh - 1) * s->istrides[1] + hw && s->v_size >= (long)(hh - 1) * s->istrides[2] + hw,
-                 "chroma plane smaller than its (sw / 2) x (sh / 2) samples");
+                 srcp ? "chroma plane smaller than its (sw / 2) x sh samples" : "chroma plane smaller than its (sw / 2) x (sh / 2) samples");
   }
   const int chain_order = (ys->out_order ^ (pr->swap_rb ? 1 : 0)) & 1;
   FLAT_REQUIRE(!ys2 || ys2->out_order == chain_order, "src2->out_order must state the byte order the blend works in: src->out_order ^ params->swap_rb");
@@ -338,10 +421,11 @@ static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv
     FLAT_REQUIRE(pr->orow >= cw * 4 && (!l2rgba || pr->irow2 >= cw * 4), "rowstride smaller than a row");
     FLAT_REQUIRE(((pr->orow | (l2rgba ? pr->irow2 : 0)) & 3) == 0, "rowstrides must be multiples of 4");
   }
-  uintptr_t pb = 0;
+  uintptr_t pb = 0, sb = 0;
   for (int i = 0; i < ntracks; i++) {
     const lgpu_chain_yuv_sink_track &t = tracks[i];
-    FLAT_REQUIRE(t.y_d && t.u_d && t.v_d && (!l2rgba || t.layer2_d), "null track pointer");
+    FLAT_REQUIRE(t.y_d && (packed || (t.u_d && t.v_d)) && (!l2rgba || t.layer2_d), "null track pointer");
+    sb |= (uintptr_t)t.y_d;
     FLAT_REQUIRE(!l2rgba || multiple_of((uintptr_t)t.layer2_d, 4), "layer 2 must be 4-byte aligned");
     FLAT_REQUIRE(!mix || (mix[i].y2_d && mix[i].u2_d && mix[i].v2_d), "null layer-2 plane");
     for (int k = 0; k < nplanes; k++) {
@@ -355,9 +439,12 @@ static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv
   }
   // the one-launch form; anything else is refused, never run some other way
   if (pr->sw != pr->dw || pr->sh != pr->dh)
-    FLAT_REFUSE(sk ? "frames that keep their size only (sw == dw, sh == dh); the exact 2:1 reduction is lgpu_chain_yuv420p_to_yuv"
+    FLAT_REFUSE(srcp ? "frames that keep their size only (sw == dw, sh == dh); convert with lgpu_yuv420p_to_rgb_batch (is_422) / lgpu_yuv_to_rgb_batch and run lgpu_chain_amounts"
+                : sk ? "frames that keep their size only (sw == dw, sh == dh); the exact 2:1 reduction is lgpu_chain_yuv420p_to_yuv"
                    : "frames that keep their size only (sw == dw, sh == dh); the exact 2:1 reduction is lgpu_chain_yuv420p");
-  if (pr->do_blur) FLAT_REFUSE("the gaussian is not offered with a 4:2:0 source");
+  if (pr->do_blur) FLAT_REFUSE("the gaussian is not offered with a 4:2:0 or 4:2:2 source");
+  // K3 reads a macropixel as one aligned dword; the reference divides that rowstride by 4 (docs/QUIRKS.md, K3-c): there is no behaviour to follow elsewhere
+  if (packed && !multiple_of(sb | (uintptr_t)lys, 4)) FLAT_REFUSE("a UYVY / YUYV source is read as 4-byte macropixels (plane and rowstride % 4 == 0)");
   if (sk) {
     if (sk->out_fmt == 5) FLAT_REFUSE("YUV422P is not served (lgpu_chain_flat_yuv420p + lgpu_rgb_to_yuv_batch)");
     if (planar && (pr->dh & 1)) FLAT_REFUSE("the 4:2:0 sink needs an even height");
@@ -367,7 +454,7 @@ static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv
   }
   const long long lim = 1ll << 31;
   const int drow = sk ? sk->orow[0] : pr->orow;
-  if ((long long)pr->sh * lys >= lim || ys->u_size >= lim || ys->v_size >= lim || (long long)ch * drow >= lim || (l2rgba && (long long)ch * pr->irow2 >= lim) ||
+  if ((long long)pr->sh * lys >= lim || usz >= lim || vsz >= lim || (long long)ch * drow >= lim || (l2rgba && (long long)ch * pr->irow2 >= lim) ||
       (ys2 && ((long long)pr->sh * ys2->istrides[0] >= lim || ys2->u_size >= lim || ys2->v_size >= lim)) || (planar && ((long long)(pr->dh >> 1) * sk->orow[1] >= lim || (long long)(pr->dh >> 1) * sk->orow[2] >= lim)))
     FLAT_REFUSE("planes of 2 GiB or more");
   int rc;
@@ -376,11 +463,13 @@ static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv
   if (planar && (rc = cavg_forms_checked())) return rc;
   if (sk && (rc = get_sink_tables(sk->which_tables, sk->in_order, &a.stab))) return rc;
   a.tables = device_tables()->yuv2rgb[ys->which_tables & 3];
-  a.usize = (uint32_t)ys->u_size; a.vsize = (uint32_t)ys->v_size; a.ys = lys; a.us = us; a.vs = vs; a.w = pr->sw; a.h = pr->sh;
+  a.usize = (uint32_t)usz; a.vsize = (uint32_t)vsz; a.ys = lys; a.us = us; a.vs = vs; a.w = pr->sw; a.h = pr->sh;
   a.orow = drow; a.irow2 = l2rgba ? pr->irow2 : 0;
   a.urow = planar ? sk->orow[1] : 0; a.vrow = planar ? sk->orow[2] : 0;
   if (cv) { a.cw = cv->nwidth; a.ch = cv->nheight; a.ox = cv->offs_x; a.oy = cv->offs_y; }
-  a.clamped = !(ys->which_tables & 1); a.lowq = ys->pb_quality == 1; a.fix_edges = (ys->flags & LGPU_YUV_FIX_EDGES) ? 1 : 0; a.use_lut = pr->use_lut ? 1 : 0;
+  a.clamped = !packed && !(ys->which_tables & 1);      // K3 indexes its tables with the sample itself
+  a.sfmt = packed ? sfmt : 0;
+  a.lowq = ys->pb_quality == 1; a.fix_edges = (ys->flags & LGPU_YUV_FIX_EDGES) ? 1 : 0; a.use_lut = pr->use_lut ? 1 : 0;
   a.fmt = sk ? sk->out_fmt : 0; a.unclamped = sk ? (sk->which_tables & 1) : 0;
   const Lut8 l = pack_lut(pr->use_lut ? pr->lut8 : nullptr);
   const int nunits = pr->sh / 2 + 1;
@@ -388,6 +477,11 @@ static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv
   const long long bar_px = cv ? (long long)cw * ch - (long long)pr->sw * pr->sh : 0;
   const int per_launch = ys2 ? LGPU_CHAIN_MIX_TRACKS : planar ? kFlatPlanarTracks : LGPU_CHAIN_MAX_TRACKS;
   hipStream_t st = (hipStream_t)stream;
+#define FLAT_LAUNCH_SRC(SK, SR) do {                                                                                                                     \
+    if (noblend) { if (chain_order) hipLaunchKernelGGL((k_flat_yuv420<0, 1, SK, 0, SR>), grid, dim3(256), 0, st, a, T, l); else hipLaunchKernelGGL((k_flat_yuv420<0, 0, SK, 0, SR>), grid, dim3(256), 0, st, a, T, l); } \
+    else { if (chain_order) hipLaunchKernelGGL((k_flat_yuv420<1, 1, SK, 0, SR>), grid, dim3(256), 0, st, a, T, l); else hipLaunchKernelGGL((k_flat_yuv420<1, 0, SK, 0, SR>), grid, dim3(256), 0, st, a, T, l); }     \
+  } while (0)
+#define FLAT_LAUNCH(SK) do { if (srcp == 2) FLAT_LAUNCH_SRC(SK, 2); else if (srcp == 1) FLAT_LAUNCH_SRC(SK, 1); else FLAT_LAUNCH_SRC(SK, 0); } while (0)
   for (int t0 = 0; t0 < ntracks; t0 += per_launch) {
     const int n = std::min(per_launch, ntracks - t0);
     // about kFlatWgTarget workgroups per launch, each walking a run of consecutive units on one staging of the tables
@@ -427,8 +521,7 @@ static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv
         T.y[i] = t.y_d; T.u[i] = t.u_d; T.v[i] = t.v_d; T.l2[i] = noblend ? nullptr : t.layer2_d; T.bf[i] = amounts ? amounts[t0 + i] : 0;
         for (int k = 0; k < 3; k++) T.dst[k][i] = t.dst_d[k];
       }
-      if (noblend) { if (chain_order) hipLaunchKernelGGL((k_flat_yuv420<0, 1, 2>), grid, dim3(256), 0, st, a, T, l); else hipLaunchKernelGGL((k_flat_yuv420<0, 0, 2>), grid, dim3(256), 0, st, a, T, l); }
-      else { if (chain_order) hipLaunchKernelGGL((k_flat_yuv420<1, 1, 2>), grid, dim3(256), 0, st, a, T, l); else hipLaunchKernelGGL((k_flat_yuv420<1, 0, 2>), grid, dim3(256), 0, st, a, T, l); }
+      FLAT_LAUNCH(2);
     } else {
       FlatTr<0>::type T;
       for (int i = 0; i < n; i++) {
@@ -436,16 +529,13 @@ static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv
         T.y[i] = t.y_d; T.u[i] = t.u_d; T.v[i] = t.v_d; T.l2[i] = noblend ? nullptr : t.layer2_d; T.bf[i] = amounts ? amounts[t0 + i] : 0;
         T.dst[0][i] = t.dst_d[0];
       }
-#define FLAT_LAUNCH(SK) do {                                                                                                                             \
-        if (noblend) { if (chain_order) hipLaunchKernelGGL((k_flat_yuv420<0, 1, SK>), grid, dim3(256), 0, st, a, T, l); else hipLaunchKernelGGL((k_flat_yuv420<0, 0, SK>), grid, dim3(256), 0, st, a, T, l); } \
-        else { if (chain_order) hipLaunchKernelGGL((k_flat_yuv420<1, 1, SK>), grid, dim3(256), 0, st, a, T, l); else hipLaunchKernelGGL((k_flat_yuv420<1, 0, SK>), grid, dim3(256), 0, st, a, T, l); }     \
-      } while (0)
       if (sk) FLAT_LAUNCH(1); else FLAT_LAUNCH(0);
-#undef FLAT_LAUNCH
     }
     LGPU_CHECK_LAUNCH();
   }
   return LGPU_OK;
+#undef FLAT_LAUNCH
+#undef FLAT_LAUNCH_SRC
 #undef FLAT_REQUIRE
 #undef FLAT_REFUSE
 }
@@ -488,4 +578,22 @@ extern "C" int lgpu_chain_flat_yuv420p_mix(const lgpu_chain_params *pr, const lg
     for (int k = 0; k < 3; k++) tr[i].dst_d[k] = tracks[i].dst_d[k];
   }
   return flat_impl("lgpu_chain_flat_yuv420p_mix", pr, ys, nullptr, sk, tr, ntracks, amounts, stream, ys2, tracks);
+}
+
+// lgpu_chain_flat_yuv422: lgpu_yuv420p_to_rgb (is_422) or lgpu_yuv_to_rgb (UYVY / YUYV) + lgpu_chain_amounts with sw == dw, sh == dh [+ lgpu_rgb_to_yuv] as ONE launch
+// per 64 tracks (32 to YUV420P); every argument is checked before anything is enqueued
+extern "C" int lgpu_chain_flat_yuv422(const lgpu_chain_params *pr, const lgpu_yuv422_source *s4, const lgpu_canvas *cv, const lgpu_chain_sink *sk,
+                                      const lgpu_chain_yuv_sink_track *tracks, int ntracks, const uint8_t *amounts, void *stream) {
+  int rc = ensure_init();
+  if (rc) return rc;
+  LGPU_REQUIRE(pr && s4 && tracks && ntracks > 0 && ntracks <= LGPU_CHAIN_MAX_TRACKS, "params, source and 1..64 tracks required");
+  LGPU_REQUIRE(s4->in_fmt == 2 || s4->in_fmt == 3 || s4->in_fmt == 5, "in_fmt must be 2 (UYVY), 3 (YUYV) or 5 (YUV422P); YUV420P: lgpu_chain_flat_yuv420p[_to_yuv]");
+  LGPU_REQUIRE(!(cv && sk), "a canvas and a sink together: chroma rows would straddle the bar / frame edge");
+  lgpu_yuv_source ys;
+  memset(&ys, 0, sizeof ys);
+  const bool packed = s4->in_fmt != 5;
+  ys.istrides[0] = s4->istrides[0]; ys.istrides[1] = packed ? 0 : s4->istrides[1]; ys.istrides[2] = packed ? 0 : s4->istrides[2];
+  ys.u_size = packed ? 0 : s4->u_size; ys.v_size = packed ? 0 : s4->v_size;
+  ys.out_order = s4->out_order; ys.which_tables = s4->which_tables; ys.pb_quality = s4->pb_quality;
+  return flat_impl("lgpu_chain_flat_yuv422", pr, &ys, cv, sk, tracks, ntracks, amounts, stream, nullptr, nullptr, s4->in_fmt);
 }

@@ -607,8 +607,10 @@ struct Lazy {
   bool blend = false; int bf = 0; const void *l2h = nullptr; Dev l2; int l2rs = 0;
   bool lut = false; uint8_t lut8[256];
   int w = 0, h = 0, rs = 0;         // the plane the program stands for
-  // LZ_YUV: src is the luma plane; yu / yv the chroma planes (U, V order: a YVU420P layer's planes are swapped when recorded)
-  bool yuv = false; Dev yu, yv; int ystr[3] = {0, 0, 0}; long usz = 0, vsz = 0; int order = 0, which = 0, quality = 2;
+  // LZ_YUV: src is the luma plane; yu / yv the chroma planes (U, V order: a YVU420P layer's planes are swapped when recorded).  yfmt: the source's format in
+  // lgpu_rgb_to_yuv's numbers -- 4 planar 4:2:0, 5 YUV422P, 2 UYVY, 3 YUYV (src is the one packed plane, yu / yv are empty, ystr[0] its rowstride).  The 2:1 and
+  // 4:2:0 flat chains (lgpu_chain_yuv420p[_to_yuv], lgpu_chain_flat_yuv420p*) take yfmt 4 ONLY: every read of `yuv` that leads to one of them tests it
+  bool yuv = false; int yfmt = 4; Dev yu, yv; int ystr[3] = {0, 0, 0}; long usz = 0, vsz = 0; int order = 0, which = 0, quality = 2;
   // LZ_SINK: K4 on the w x h RGBA plane above (sww x shh of it: 4:2:0 truncates to even sides) into snp planes of sors / sbytes, registered under host planes sph
   bool sink = false; int sfmt = 0, swhich = 0, sorder = 0, snp = 0, sww = 0, shh = 0, sors[3] = {0, 0, 0}; size_t sbytes[3] = {0, 0, 0}; const void *sph[3] = {nullptr, nullptr, nullptr};
 };
@@ -650,7 +652,7 @@ bool lazy_same_shape(const Lazy *a, const Lazy *b) {
   return a->sw == b->sw && a->sh == b->sh && a->srs == b->srs && a->swap == b->swap && a->scale == b->scale && a->dw == b->dw && a->dh == b->dh &&
          a->interp == b->interp && a->opaque == b->opaque && a->canvas == b->canvas && a->nw == b->nw && a->nh == b->nh && a->ox == b->ox && a->oy == b->oy && a->blend == b->blend &&
          a->l2rs == b->l2rs &&          /* (not the blend amount: every track of a launch has its own, lgpu_chain_amounts) */ a->lut == b->lut && (!a->lut || !memcmp(a->lut8, b->lut8, 256)) && a->w == b->w && a->h == b->h && a->rs == b->rs &&
-         a->yuv == b->yuv && (!a->yuv || (!memcmp(a->ystr, b->ystr, sizeof a->ystr) && a->usz == b->usz && a->vsz == b->vsz && a->order == b->order && a->which == b->which && a->quality == b->quality)) &&
+         a->yuv == b->yuv && (!a->yuv || (a->yfmt == b->yfmt && !memcmp(a->ystr, b->ystr, sizeof a->ystr) && a->usz == b->usz && a->vsz == b->vsz && a->order == b->order && a->which == b->which && a->quality == b->quality)) &&
          a->sink == b->sink && (!a->sink || (a->sfmt == b->sfmt && a->swhich == b->swhich && a->sorder == b->sorder && a->snp == b->snp && a->sww == b->sww && a->shh == b->shh &&
                                              !memcmp(a->sors, b->sors, sizeof a->sors)));
 }
@@ -718,8 +720,8 @@ int lazy_run_rgba(Lazy *const *zs, int n, uint8_t *const *outp) {
   const lgpu_canvas cv = {z0->nw, z0->nh, z0->ox, z0->oy};
   if (!rc && z0->yuv) {
     const int strides[3] = {z0->ystr[0], z0->ystr[1], z0->ystr[2]};
-    if (!staged && z0->scale && n <= LGPU_CHAIN_MAX_TRACKS) {
-      // the one-launch form: the conversion rides in the chain's loads (lgpu_chain_yuv420p); every other shape is refused there and takes the two launches below
+    if (!staged && z0->scale && z0->yfmt == 4 && n <= LGPU_CHAIN_MAX_TRACKS) {
+      // the one-launch form: the conversion rides in the chain's loads (lgpu_chain_yuv420p, 4:2:0 planes only); every other shape is refused there and takes the two launches below
       lgpu_yuv_source ys;
       memset(&ys, 0, sizeof ys);
       ys.istrides[0] = strides[0]; ys.istrides[1] = strides[1]; ys.istrides[2] = strides[2]; ys.u_size = z0->usz; ys.v_size = z0->vsz;
@@ -735,7 +737,23 @@ int lazy_run_rgba(Lazy *const *zs, int n, uint8_t *const *outp) {
     }
     // lives_gpu_set_flat_yuv(1): a group that keeps its size (letterboxed or not) with anything behind the conversion takes lgpu_chain_flat_yuv420p, ONE launch and no
     // converted frame; a conversion that is all there is stays with K2's own kernel below (the same bytes either way, and that kernel is the faster converter)
-    if (!rc && !done && !staged && !z0->scale && g_flat_yuv.load() && n <= LGPU_CHAIN_MAX_TRACKS && (z0->swap || z0->canvas || z0->blend || z0->lut)) {
+    if (!rc && !done && !staged && !z0->scale && z0->yfmt != 4 && g_flat_yuv.load() && n <= LGPU_CHAIN_MAX_TRACKS && (z0->swap || z0->canvas || z0->blend || z0->lut)) {
+      // the same from YUV422P / UYVY / YUYV frames: lgpu_chain_flat_yuv422
+      lgpu_yuv422_source y4;
+      memset(&y4, 0, sizeof y4);
+      y4.in_fmt = z0->yfmt; y4.istrides[0] = strides[0]; y4.istrides[1] = strides[1]; y4.istrides[2] = strides[2]; y4.u_size = z0->usz; y4.v_size = z0->vsz;
+      y4.out_order = z0->order; y4.which_tables = z0->which; y4.pb_quality = z0->quality;
+      std::vector<lgpu_chain_yuv_sink_track> yt((size_t)n);
+      for (int i = 0; i < n; i++) {
+        memset(&yt[(size_t)i], 0, sizeof yt[0]);
+        yt[(size_t)i].y_d = (const uint8_t *)zs[i]->src.d; yt[(size_t)i].u_d = (const uint8_t *)zs[i]->yu.d; yt[(size_t)i].v_d = (const uint8_t *)zs[i]->yv.d;
+        yt[(size_t)i].layer2_d = (const uint8_t *)zs[i]->l2.d; yt[(size_t)i].dst_d[0] = outp[i];
+      }
+      const int crc = lgpu_chain_flat_yuv422(&pr, &y4, z0->canvas ? &cv : nullptr, nullptr, yt.data(), n, z0->blend ? amounts.data() : nullptr, S());
+      if (crc == LGPU_OK) { done = true; g_lz_chain_launches++; g_lz_chain_tracks += (unsigned long long)n; g_lz_flat_launches++; g_lz_flat_tracks += (unsigned long long)n; }
+      else if (crc != LGPU_E_BADARG && crc != LGPU_E_UNSUPPORTED) rc = crc;          // a refused shape takes the two launches below
+    }
+    if (!rc && !done && !staged && !z0->scale && z0->yfmt == 4 && g_flat_yuv.load() && n <= LGPU_CHAIN_MAX_TRACKS && (z0->swap || z0->canvas || z0->blend || z0->lut)) {
       lgpu_yuv_source ys;
       memset(&ys, 0, sizeof ys);
       ys.istrides[0] = strides[0]; ys.istrides[1] = strides[1]; ys.istrides[2] = strides[2]; ys.u_size = z0->usz; ys.v_size = z0->vsz;
@@ -761,13 +779,26 @@ int lazy_run_rgba(Lazy *const *zs, int n, uint8_t *const *outp) {
         fr[(size_t)i].dst_d = only ? outp[i] : (uint8_t *)scr + (size_t)i * per;
       }
       const int orow = only ? z0->rs : z0->sw * 4;
-      if (!rc && !staged && n <= LGPU_CHAIN_MAX_TRACKS) {
-        rc = lgpu_yuv420p_to_rgb_batch(n, fr.data(), strides, z0->usz, z0->vsz, orow, z0->sw, z0->sh, 4, z0->order, 0, z0->which, z0->quality, nullptr, 0, S());
+      const int is_422 = z0->yfmt == 5 ? 1 : 0;
+      if (z0->yfmt == 2 || z0->yfmt == 3) {
+        // a packed frame: K3 (lgpu_yuv_to_rgb), LGPU_FX_MAX_FRAMES frames per batch
+        const int irs[4] = {strides[0], 0, 0, 0};
+        for (int i0 = 0; i0 < n && !rc; i0 += (staged ? 1 : LGPU_FX_MAX_FRAMES)) {
+          const int m = staged ? 1 : std::min(n - i0, (int)LGPU_FX_MAX_FRAMES);
+          const uint8_t *sp[LGPU_FX_MAX_FRAMES * 4];
+          uint8_t *dp[LGPU_FX_MAX_FRAMES];
+          memset(sp, 0, sizeof sp);
+          for (int i = 0; i < m; i++) { sp[i * 4] = fr[(size_t)(i0 + i)].y_d; dp[i] = fr[(size_t)(i0 + i)].dst_d; }
+          if (staged) rc = lgpu_yuv_to_rgb(sp, irs, z0->sw, z0->sh, z0->yfmt, 0, dp[0], orow, z0->order, 1, z0->which, S());
+          else { rc = lgpu_yuv_to_rgb_batch(sp, irs, z0->sw, z0->sh, z0->yfmt, 0, dp, orow, z0->order, 1, z0->which, m, S()); if (!rc) g_lz_yuv_pre++; }
+        }
+      } else if (!rc && !staged && n <= LGPU_CHAIN_MAX_TRACKS) {
+        rc = lgpu_yuv420p_to_rgb_batch(n, fr.data(), strides, z0->usz, z0->vsz, orow, z0->sw, z0->sh, 4, z0->order, is_422, z0->which, z0->quality, nullptr, 0, S());
         if (!rc) g_lz_yuv_pre++;
       } else
         for (int i = 0; i < n && !rc; i++)
           rc = lgpu_yuv420p_to_rgb(fr[(size_t)i].y_d, fr[(size_t)i].u_d, fr[(size_t)i].v_d, strides, z0->usz, z0->vsz, fr[(size_t)i].dst_d, orow, z0->sw, z0->sh, 4,
-                                   z0->order, 0, z0->which, z0->quality, nullptr, 0, S());
+                                   z0->order, is_422, z0->which, z0->quality, nullptr, 0, S());
       if (only) done = true;
       for (int i = 0; i < n; i++) srcp[(size_t)i] = (const uint8_t *)fr[(size_t)i].dst_d;
       srow = z0->sw * 4;
@@ -869,7 +900,7 @@ int lazy_run_sink(Lazy *const *zs, int n, Dev (*souts)[3]) {
   // taken, and YUYV with it (the same instantiation); to YUV420P 258.9 us against 243.4 (spread 1.9 us) -- the 4:2:0 form's 98-105 registers hold it to four waves per
   // SIMD -- so 4:2:0 keeps today's two launches.
   const bool transcode_fused = z0->sfmt == 2 || z0->sfmt == 3;
-  if (transcode_fused && !staged && z0->yuv && z0->scale && !z0->canvas && z0->sww == z0->w && z0->shh == z0->h && n <= LGPU_CHAIN_MAX_TRACKS) {
+  if (transcode_fused && !staged && z0->yuv && z0->yfmt == 4 && z0->scale && !z0->canvas && z0->sww == z0->w && z0->shh == z0->h && n <= LGPU_CHAIN_MAX_TRACKS) {
     // from YUV planes to YUV planes: ONE launch, neither RGBA frame exists.  The source planes are awaited as in lazy_run_rgba; lazy_run_group gives them back with
     // their reader streams kept.
     for (int i = 0; i < n; i++) { await(zs[i]->src, false); await(zs[i]->yu, false); await(zs[i]->yv, false); if (zs[i]->blend) await(zs[i]->l2, false); }
@@ -920,6 +951,10 @@ int lazy_run_sink(Lazy *const *zs, int n, Dev (*souts)[3]) {
     memset(&ys, 0, sizeof ys);
     ys.istrides[0] = z0->ystr[0]; ys.istrides[1] = z0->ystr[1]; ys.istrides[2] = z0->ystr[2]; ys.u_size = z0->usz; ys.v_size = z0->vsz;
     ys.out_order = z0->order; ys.which_tables = z0->which; ys.pb_quality = z0->quality; ys.flags = 0;
+    lgpu_yuv422_source y4;                    // the same description for a YUV422P / UYVY / YUYV group (lgpu_chain_flat_yuv422)
+    memset(&y4, 0, sizeof y4);
+    y4.in_fmt = z0->yfmt; y4.istrides[0] = z0->ystr[0]; y4.istrides[1] = z0->ystr[1]; y4.istrides[2] = z0->ystr[2]; y4.u_size = z0->usz; y4.v_size = z0->vsz;
+    y4.out_order = z0->order; y4.which_tables = z0->which; y4.pb_quality = z0->quality;
     lgpu_chain_sink sk;
     memset(&sk, 0, sizeof sk);
     sk.out_fmt = z0->sfmt; sk.which_tables = z0->swhich; sk.in_order = z0->sorder;
@@ -933,7 +968,8 @@ int lazy_run_sink(Lazy *const *zs, int n, Dev (*souts)[3]) {
       for (int p = 0; p < z0->snp; p++) tr[(size_t)i].dst_d[p] = (uint8_t *)souts[i][p].d;
       amounts[(size_t)i] = (uint8_t)zs[i]->bf;
     }
-    const int crc = lgpu_chain_flat_yuv420p_to_yuv(&pr, &ys, &sk, tr.data(), n, z0->blend ? amounts.data() : nullptr, S());
+    const int crc = z0->yfmt == 4 ? lgpu_chain_flat_yuv420p_to_yuv(&pr, &ys, &sk, tr.data(), n, z0->blend ? amounts.data() : nullptr, S())
+                                  : lgpu_chain_flat_yuv422(&pr, &y4, nullptr, &sk, tr.data(), n, z0->blend ? amounts.data() : nullptr, S());
     if (crc == LGPU_OK) {
       const unsigned long long nl = z0->sfmt == 4 ? (unsigned long long)((n + 31) / 32) : 1ull;      // the call's launches: 32 tracks each to YUV420P
       g_lz_chain_launches += nl; g_lz_chain_tracks += (unsigned long long)n; g_lz_sink_launches += nl; g_lz_sink_tracks += (unsigned long long)n; g_lz_sink_fused += nl;
@@ -1104,42 +1140,48 @@ bool lazy_commit(weed_plant_t *layer, const Layer &l, Lazy *z, int pal, int widt
 
 // convert_layer_palette_full(YUV420P / YVU420P -> RGBA32 / BGRA32) on a pinned layer whose three planes are resident: recorded as stage LZ_YUV of a new program
 // that takes the planes out of the table (owned; external surfaces borrowed) and stands for the new RGBA host plane.  false: not recorded, nothing changed.
+// Under lives_gpu_set_flat_yuv(1) ONLY, YUV422P (three planes, full-height chroma) and UYVY / YUYV (one plane whose width leaf counts macropixels: the RGBA frame
+// is twice as wide) are recorded the same way; with the switch off these palettes keep the eager conversion and no counter moves.
 bool lazy_record_yuv(weed_plant_t *layer, const Layer &l, int outpl, int which, int new_gamma, int flags) {
-  if (!g_deferred.load(std::memory_order_relaxed) || !t_pinned || !lazy_pal(outpl) || l.nplanes != 3 || l.width < 2 || (l.width & 1) ||
-      (l.pal != WEED_PALETTE_YUV420P && l.pal != WEED_PALETTE_YVU420P))
-    return false;
-  const int iu = (l.pal == WEED_PALETTE_YVU420P) ? 2 : 1, iv = 3 - iu;            // swap_chroma_planes (:12353)
-  const int ch = plane_h(l, 1);
+  const bool p420 = l.pal == WEED_PALETTE_YUV420P || l.pal == WEED_PALETTE_YVU420P, packed = l.pal == WEED_PALETTE_UYVY || l.pal == WEED_PALETTE_YUYV;
+  if (!g_deferred.load(std::memory_order_relaxed) || !t_pinned || !lazy_pal(outpl)) return false;
+  if (!p420 && !((l.pal == WEED_PALETTE_YUV422P || packed) && g_flat_yuv.load())) return false;
+  const int np = packed ? 1 : 3, owidth = packed ? l.width * 2 : l.width;          // macropixels -> pixels (:13010)
+  if (l.nplanes != np || owidth < 2 || (owidth & 1)) return false;
+  if (packed && ((l.rs[0] & 3) || l.rs[0] < owidth * 2)) return false;            // rows that are not 4-byte aligned or too short: the one launch refuses them (and so does the batched fallback), so nothing is recorded and the eager call answers
+  const int iu = packed ? 0 : (l.pal == WEED_PALETTE_YVU420P) ? 2 : 1, iv = packed ? 0 : 3 - iu;            // swap_chroma_planes (:12353)
+  const int ch = packed ? 0 : plane_h(l, 1);
   const void *hp[3] = {l.pd[0], l.pd[iu], l.pd[iv]};
   const size_t need[3] = {(size_t)l.rs[0] * l.height, (size_t)l.rs[iu] * ch, (size_t)l.rs[iv] * ch};
-  for (int p = 0; p < 3; p++) {
+  for (int p = 0; p < np; p++) {
     ResShard &sh = shard_of(hp[p]);
     std::lock_guard<SpinLock> lk(sh.mu);
     auto it = sh.m.find(hp[p]);
     if (it == sh.m.end() || !it->second.d || it->second.lazy || it->second.bytes < need[p] || it->second.lazy_readers > 0) return false;
   }
   Dev d[3];
-  for (int p = 0; p < 3; p++) {
+  for (int p = 0; p < np; p++) {
     ResShard &sh = shard_of(hp[p]);
     std::lock_guard<SpinLock> lk(sh.mu);
     auto it = sh.m.find(hp[p]);
     if (it != sh.m.end()) { d[p] = it->second; sh.m.erase(it); }
   }
   auto put_back = [&]() {
-    for (int p = 0; p < 3; p++) {
+    for (int p = 0; p < np; p++) {
       if (!d[p].d) continue;
       ResShard &sh = shard_of(hp[p]);
       std::lock_guard<SpinLock> lk(sh.mu);
       sh.m[hp[p]] = d[p];
     }
   };
-  if (!d[0].d || !d[1].d || !d[2].d) { put_back(); return false; }
+  if (!d[0].d || (!packed && (!d[1].d || !d[2].d))) { put_back(); return false; }
   Lazy *z = new Lazy;
   z->src = d[0]; z->yu = d[1]; z->yv = d[2]; z->yuv = true; z->stage = LZ_YUV;
-  z->sw = l.width; z->sh = l.height; z->srs = l.width * 4;
-  z->ystr[0] = l.rs[0]; z->ystr[1] = l.rs[iu]; z->ystr[2] = l.rs[iv]; z->usz = (long)need[1]; z->vsz = (long)need[2];
-  z->order = pal_red_first(outpl) ? 0 : 1; z->which = which; z->quality = g_prefs.pb_quality;
-  if (!lazy_commit(layer, l, z, outpl, l.width, l.height, 0)) { delete z; put_back(); return false; }
+  z->yfmt = p420 ? 4 : l.pal == WEED_PALETTE_YUV422P ? 5 : l.pal == WEED_PALETTE_UYVY ? 2 : 3;
+  z->sw = owidth; z->sh = l.height; z->srs = owidth * 4;
+  z->ystr[0] = l.rs[0]; z->ystr[1] = packed ? 0 : l.rs[iu]; z->ystr[2] = packed ? 0 : l.rs[iv]; z->usz = packed ? 0 : (long)need[1]; z->vsz = packed ? 0 : (long)need[2];
+  z->order = pal_red_first(outpl) ? 0 : 1; z->which = packed ? (which & 1) : which; z->quality = g_prefs.pb_quality;      // K3 takes the YCbCr tables only
+  if (!lazy_commit(layer, l, z, outpl, owidth, l.height, 0)) { delete z; put_back(); return false; }
   g_lz_yuv_recorded++;
   if (new_gamma != l.gamma) set_int(layer, WEED_LEAF_GAMMA_TYPE, new_gamma);
   if (flags != l.flags) set_int(layer, kLeafHostFlags, flags);
@@ -1533,7 +1575,7 @@ static lives_gpu_boolean convert_layer_palette_full_body(lives_gpu_layer_t *laye
       return 1;
     }
   }
-  if (!lutp && (inpl == WEED_PALETTE_YUV420P || inpl == WEED_PALETTE_YVU420P) && lazy_pal(outpl) &&
+  if (!lutp && (in_planar_sub || inpl == WEED_PALETTE_UYVY || inpl == WEED_PALETTE_YUYV) && lazy_pal(outpl) &&
       lazy_record_yuv(layer, l, outpl, (iclamping == WEED_YUV_CLAMPING_UNCLAMPED ? 1 : 0) | (l.subspace == WEED_YUV_SUBSPACE_BT709 ? 2 : 0), new_gamma, flags))
     return 1;                                   // a decoder frame on a pinned layer: recorded, not launched (deferred execution, above)
   NewPlanes np;
@@ -2317,7 +2359,8 @@ void lives_gpu_deferred_stats(unsigned long long out[4]) {
 // [7] conversion pre-launches of the two-launch path (lgpu_yuv420p_to_rgb_batch), [8] sink conversions recorded (LZ_SINK), [9] sink launches (a fused
 // lgpu_chain_to_yuv launch, also counted in [1], or one lgpu_rgb_to_yuv_batch / lgpu_rgb_to_yuv) and [10] the tracks they carried, [11] those of [9] that were fused lgpu_chain_to_yuv launches (the others converted an
 // RGBA frame), [12] launches that ran from YUV planes to YUV planes (lgpu_chain_yuv420p_to_yuv; each is also counted in [1], [5], [9] and [11]), [13] launches of the
-// unscaled one-launch forms (lives_gpu_set_flat_yuv: lgpu_chain_flat_yuv420p, counted in [1] too, and lgpu_chain_flat_yuv420p_to_yuv, counted in [1], [9] and [11] too) and
+// unscaled one-launch forms (lives_gpu_set_flat_yuv: lgpu_chain_flat_yuv420p, counted in [1] too, and lgpu_chain_flat_yuv420p_to_yuv, counted in [1], [9] and [11] too;
+// lgpu_chain_flat_yuv422 from YUV422P / UYVY / YUYV layers as whichever of the two it stands for, such layers' recorded conversions in [4], their batched fallback in [7]) and
 // [14] the tracks they carried; at most n entries are written
 void lives_gpu_deferred_stats_n(unsigned long long *out, int n) {
   if (!out || n <= 0) return;

@@ -187,6 +187,8 @@ __global__ __launch_bounds__(kBlock) void k_yuv420p_to_rgb(YuvArgs a, Lut8 lut, 
 
 // one (row i, chroma column k) cell of the 4:2:2 walk (:3593-3640 / :3858-3901): "last / this" are seeded from chroma row i >> 1 (reference), so the first pair of a
 // row takes its left samples from there
+// (THE 4:2:2 SEED QUIRK IS WRITTEN DOWN TWICE: here, with the V422 fast path of k_yuv420p_to_rgb_s below, and in flat.hip's flat_row422, the unscaled chain from
+// YUV422P frames (lgpu_chain_flat_yuv422): a quirk changed here must change there too)
 __device__ __forceinline__ void yuv422_cell(const YuvArgs &a, const YuvCtx &c, int i, int k) {
   auto PU = [&](int r, int kk) -> int { long q = (long)r * a.us + kk; return a.u[q < a.usize ? q : a.usize - 1]; };
   auto PV = [&](int r, int kk) -> int { long q = (long)r * a.vs + kk; return a.v[q < a.vsize ? q : a.vsize - 1]; };
@@ -233,6 +235,7 @@ __global__ __launch_bounds__(1024) void k_yuv420p_to_rgb_s(YuvArgs a, Lut8 lut, 
     q.ya = q.yb = 0; q.u0 = q.u1 = q.v0 = q.v1 = 0; q.lv2 = 0;
     if (V422) {
       // row q.unit; columns k0 >= 2 only (the first pairs of a row take their left samples from chroma row i >> 1), the window k0 - 1 .. inside the plane
+      // (the same split -- seeded cells sample by sample, interior cells on a window -- is written a second time in flat.hip's flat_row422: change both)
       const int i2 = q.unit;
       // plane offsets are 32-bit products of 24-bit operands (the host sends larger planes to the general kernel): v_mul_u32_u24 instead of 64-bit multiply-adds at a quarter of the rate
       const uint32_t ou = __umul24((uint32_t)i2, (uint32_t)a.us) + (uint32_t)q.k0 - 1u, ov = __umul24((uint32_t)i2, (uint32_t)a.vs) + (uint32_t)q.k0 - 1u;

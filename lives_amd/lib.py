@@ -73,6 +73,11 @@ class CompLayer(ctypes.Structure):
                 ("offs_x", ctypes.c_int), ("offs_y", ctypes.c_int), ("alpha", ctypes.c_double)]
 
 
+class Yuv422Source(ctypes.Structure):
+    """lgpu_yuv422_source"""
+    _fields_ = [("in_fmt", ci), ("istrides", ci * 3), ("u_size", cl), ("v_size", cl), ("out_order", ci), ("which_tables", ci), ("pb_quality", ci)]
+
+
 class Canvas(ctypes.Structure):
     """lgpu_canvas"""
     _fields_ = [("nwidth", ci), ("nheight", ci), ("offs_x", ci), ("offs_y", ci)]
@@ -177,6 +182,7 @@ PROTOTYPES = {
     "lgpu_chain_flat_yuv420p": [vp, vp, vp, vp, ci, vp, vp],
     "lgpu_chain_flat_yuv420p_to_yuv": [vp, vp, vp, vp, ci, vp, vp],
     "lgpu_chain_flat_yuv420p_mix": [vp, vp, vp, vp, vp, ci, vp, vp],
+    "lgpu_chain_flat_yuv422": [vp, vp, vp, vp, vp, ci, vp, vp],
     "lgpu_pixbuf_scale_check": [ci, ci, ci, ci, ci, ci, vp],
     "lgpu_pixbuf_scale_batch": [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp],
     "lgpu_fx_batch": [ctypes.POINTER(FxParams), ctypes.POINTER(FxFrame), ci, vp],

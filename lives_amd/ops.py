@@ -252,6 +252,20 @@ def yuv_to_rgb(src_planes, dst, width, height, in_fmt, in_alpha, out_order, out_
              out_order, int(out_alpha), which_tables, stream_ptr())
 
 
+def yuv_to_rgb_batch(src_planes, dsts, width, height, in_fmt, in_alpha, out_order, out_alpha, which_tables):
+    """lgpu_yuv_to_rgb_batch: K3 on up to 16 frames of one geometry in one launch; src_planes: a list of plane tensors per frame (strides are taken from frame 0),
+    dsts: 2-D uint8 device tensors"""
+    n = len(dsts)
+    sp = (ctypes.c_void_p * (4 * n))()
+    for f in range(n):
+        for k, t in enumerate(src_planes[f]):
+            sp[4 * f + k] = t.data_ptr()
+    ss = (ctypes.c_int * 4)(*([t.stride(0) for t in src_planes[0]] + [0] * (4 - len(src_planes[0]))))
+    dp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in dsts])
+    lib.call("lgpu_yuv_to_rgb_batch", ctypes.addressof(sp), ctypes.addressof(ss), width, height, in_fmt, int(in_alpha), ctypes.addressof(dp), dsts[0].stride(0),
+             out_order, int(out_alpha), which_tables, n, stream_ptr())
+
+
 def yuv_switch_clamping(planes, palette, height, to_unclamped):
     pp, ss = _plane_tables(planes)
     lib.call("lgpu_yuv_switch_clamping", ctypes.addressof(pp), ctypes.addressof(ss), palette, height, int(to_unclamped), stream_ptr())
@@ -472,7 +486,8 @@ def chain_yuv_sink_tracks(ys, us, vs, layer2s, dst_planes):
     n = len(ys)
     arr = (lib.ChainYuvSinkTrack * n)()
     for i in range(n):
-        arr[i].y_d, arr[i].u_d, arr[i].v_d = ys[i].data_ptr(), us[i].data_ptr(), vs[i].data_ptr()
+        arr[i].y_d = ys[i].data_ptr()
+        arr[i].u_d, arr[i].v_d = (us[i].data_ptr(), vs[i].data_ptr()) if us is not None else (None, None)      # None: a packed frame (lgpu_chain_flat_yuv422)
         arr[i].layer2_d = layer2s[i].data_ptr() if layer2s is not None else None
         for k, t in enumerate(dst_planes[i]):
             arr[i].dst_d[k] = t.data_ptr()
@@ -508,6 +523,29 @@ def chain_flat_yuv420p_to_yuv(params, src, sink, tracks, amounts, check=True):
     if not check:
         return lib.load().lgpu_chain_flat_yuv420p_to_yuv(*args)
     return lib.call("lgpu_chain_flat_yuv420p_to_yuv", *args)
+
+
+def yuv422_source(in_fmt, istrides, u_size=0, v_size=0, out_order=0, which_tables=0, pb_quality=2):
+    """lgpu_yuv422_source: in_fmt 5 YUV422P (three rowstrides, the chroma planes' sizes) / 2 UYVY / 3 YUYV (one rowstride)"""
+    s = lib.Yuv422Source()
+    s.in_fmt = in_fmt
+    for k, v in enumerate(istrides):
+        s.istrides[k] = int(v)
+    s.u_size, s.v_size, s.out_order, s.which_tables, s.pb_quality = u_size, v_size, out_order, which_tables, pb_quality
+    return s
+
+
+def chain_flat_yuv422(params, src, tracks, amounts, sink=None, canvas=None, check=True):
+    """lgpu_chain_flat_yuv422: the unscaled tick from YUV422P / UYVY / YUYV frames, one launch and no converted frame, to RGBA (sink=None, rowstride params.orow,
+    optionally into canvas = (nwidth, nheight, offs_x, offs_y)) or to a YUV sink.  tracks: chain_yuv_sink_tracks (a packed frame is the y plane; u / v None).
+    check=False returns the library's code instead of raising (tests of the refusals)"""
+    am = (ctypes.c_uint8 * max(1, len(tracks)))(*[int(a) & 0xFF for a in amounts]) if amounts is not None else None      # None: with LGPU_INTERP_NOBLEND (0x400) in params.interp
+    cv = lib.Canvas(*canvas) if canvas is not None else None
+    args = (ctypes.byref(params), ctypes.byref(src), ctypes.byref(cv) if cv is not None else None, ctypes.byref(sink) if sink is not None else None, tracks, len(tracks),
+            am, stream_ptr())
+    if not check:
+        return lib.load().lgpu_chain_flat_yuv422(*args)
+    return lib.call("lgpu_chain_flat_yuv422", *args)
 
 
 def chain_yuv_mix_tracks(ys, us, vs, y2s, u2s, v2s, dst_planes):
