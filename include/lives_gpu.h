@@ -218,6 +218,26 @@ int lgpu_letterbox_bars(uint8_t *dst_d, int orow, int nwidth, int nheight, int p
    lut8 (HOST, may be NULL) is the fused post-pass of :14718-14720. */
 int lgpu_resize(const uint8_t *src_d, int irow, int sw, int sh, uint8_t *dst_d, int orow, int dw, int dh,
                 int psize, int interp, const uint8_t *lut8, void *stream);
+/* test hook: which kernel lgpu_resize / the polyphase lgpu_chain would launch for a call, decided by the very functions the calls go through (resize.hip: the host
+   half of the filter bank, half8_applies, plan_sep, sep2p_taken); host only -- no HIP call, nothing launched, works without a device.  src_bits / dst_bits: the OR
+   of the low four address bits of every source resp. destination (and, in a chain, layer-2) pointer of the call.  mode: the entry point.  LGPU_TUNE "SEP2P_FORCE" is
+   read as the launch reads it.  Returns LGPU_OK with out->path one of LGPU_PATH_*: LGPU_PATH_REFUSED (out->rc = what the call returns, nothing written) included;
+   LGPU_E_BADARG for a query that is no call at all (an empty geometry, a pixel size or mode that does not exist, a rowstride shorter than a row). */
+enum { LGPU_PLAN_RESIZE = 0, LGPU_PLAN_CHAIN = 1, LGPU_PLAN_CHAIN_BLUR = 2 };       /* CHAIN_BLUR: the resize stage of a do_blur chain */
+/* k_half8s; k_sep2<nph>; k_sep2p<nph, 0, 4>; k_sep2p<1, mh_kb, 4> (matrix cores); k_separable<0, 0> (taps at run time); the two generic passes; nothing */
+enum { LGPU_PATH_HALF8S = 1, LGPU_PATH_SEP2, LGPU_PATH_SEP2P, LGPU_PATH_SEP2P_MFMA, LGPU_PATH_SEPARABLE, LGPU_PATH_GENERIC, LGPU_PATH_REFUSED };
+typedef struct { int sw, sh, dw, dh, psize, interp, irow, orow; unsigned src_bits, dst_bits; int ntracks, mode; } lgpu_resize_plan_query;
+typedef struct {
+  int path, rc;                  /* LGPU_PATH_*; rc: LGPU_OK, or the error of a refused call */
+  int kernel;                    /* filter: 0 bilinear, 1 bicubic, 2 lanczos */
+  int nth, ntv, nph, npv;        /* taps per axis; tap pairs of the dot2 passes */
+  int th, th_start, sht, swt;    /* tile height launched and the height the planner started from; window rows and columns */
+  int lds;                       /* dynamic LDS bytes of the launch */
+  int mh_r, mh_c0, mh_kb;        /* LGPU_PATH_SEP2P_MFMA: ratio, first column's offset in its 4-pixel group, K blocks */
+  int tiles_x, tiles_y;
+  int vec, xoff;                 /* the separable kernels' 16-byte window loads; LGPU_PATH_HALF8S: the aligned-window form */
+} lgpu_resize_plan;
+int lgpu_debug_resize_plan(const lgpu_resize_plan_query *q, lgpu_resize_plan *out);
 /* ---- K7, pixbuf arithmetic: the reference's OTHER resize body -- resize_layer_full without swscale scales through
    lives_pixbuf_scale_simple == gdk_pixbuf_scale_simple (src/colourspace.c:15262-15322, call :15295), and the compositor scales its layers with the
    same call (lives-plugins/weed-plugins/gdk/compositor.c:263-265).  PINNED: bit-exact to gdk-pixbuf 2.42.8's output (tests/golden/pixbuf_scale.npz,

@@ -413,7 +413,7 @@ __global__ __launch_bounds__(kBlock) void k_sep2(SepArgs a, SepTracks trk, Lut8 
 
 // =====================================================================================================================
 // k_gauss5x -- 5x5 binomial blur of RGBA32 frames (the chain's blur stage, BASELINE config 4/5, and lgpu_gauss5).
-// Same arithmetic as k_separable<5,5> with the [1 4 6 4 1] bank (bit-identical; rows that are not 8-byte aligned still take that one): exact row sums,
+// Same arithmetic as the separable kernels on the [1 4 6 4 1] bank (bit-identical; rows that are not 8-byte aligned take that bank through k_sep2<3>): exact row sums,
 // one rounding (sum + 128) >> 8, edge pixels replicated.  Because the taps are 1/4/6 the whole thing fits SWAR: a
 // pixel is split once into its even bytes and its odd bytes (two dwords holding two 16-bit lanes each); a row sum is
 // <= 16 * 255 = 4080 and a column sum of row sums <= 65280, + 128 = 65408 < 2^16, so neither pass can carry across a
@@ -560,8 +560,8 @@ __global__ __launch_bounds__(256) void k_gauss5x(G5Args a, SepTracks t, Lut8 l) 
 
 // =====================================================================================================================
 // k_half8s -- fast path for an exact 2:1 reduction with a uniform 8-tap filter (the headline 3840x2160 -> 1920x1080
-// bicubic case of lgpu_chain / lgpu_resize).  Same arithmetic as k_separable<8,8> (bit-identical output; the tests
-// run both), restructured because the generic kernel is VALU-bound on gfx950 (profiles/r01/step1_separable_v1.md:
+// bicubic case of lgpu_chain / lgpu_resize).  Same arithmetic as the separable kernels on 8 taps (bit-identical output: both are held to
+// the oracle), restructured because k_separable, its first form, is VALU-bound on gfx950 (profiles/r01/step1_separable_v1.md:
 // integer VOP3 ops issue at ~4.7 clk each) and, as a one-role kernel, parked its waves on VMEM issue
 // (profiles/r01/step3_half8.md).  A workgroup is 4 compute waves + 2 memory waves, two workgroups per CU, persistent
 // and XCD-aware, walking 64 x 16 output tiles:
@@ -810,7 +810,7 @@ __device__ __forceinline__ void h8s_compute(const Half8Args &a, uint8_t *smem, i
   const int4v b_hi = a.bfrag[lane], b_lo = a.bfrag[64 + lane];
   // The window holds px - 128 and the taps sum to 16384, so the matrix product is 128 * (t - 16384) for the spec's
   // t = clamp_i16((h + 64) >> 7): the intermediate is kept as t' = t - 16384 (fits int16 without wrapping for the
-  // filters try_half8 admits), the clamp becomes min(t', 16383), and the vertical pass adds 16384 * sum(vc) = 2^28 back.
+  // filters half8_applies admits), the clamp becomes min(t', 16383), and the vertical pass adds 16384 * sum(vc) = 2^28 back.
   // The low-part taps are stored doubled so that t' sits in bits 8..23 of (dh << 7) + dl: a byte permute extracts it.
   const int kb = 128;                                     // 2 * 64: the rounding of >> 7, doubled
   const int4v cbias = {kb, kb, kb, kb};
@@ -1490,6 +1490,53 @@ struct Bank {
 static std::mutex g_bank_mu;
 static std::map<std::tuple<int, int, int, int>, Bank> g_banks;   // (device, srcn, dstn, kernel)  kernel 100 = gauss5
 
+// the host half of a bank: the filter, uniform2 / taps8, nph / npv, hpos / hco, and the packed tap pairs of k_sep2 (h2: [dst][nph], v2: [dst][npv]).  No HIP call:
+// get_bank uploads what this builds, lgpu_debug_resize_plan plans on it as it is (device pointers null)
+static int build_bank_host(int srcn, int dstn, int kernel, Bank *bp, std::vector<uint32_t> *h2p, std::vector<uint32_t> *v2p) {
+  Bank &b = *bp;
+  std::vector<int16_t> co;
+  b.hpos.resize(dstn);
+  if (kernel == 100) {
+    b.nt = 5;
+    co.resize((size_t)dstn * 5);
+    static const int16_t g5[5] = {1, 4, 6, 4, 1};
+    for (int i = 0; i < dstn; i++) { b.hpos[i] = i - 2; for (int j = 0; j < 5; j++) co[(size_t)i * 5 + j] = g5[j]; }
+  } else {
+    co.resize((size_t)dstn * 256);
+    int rc = lgpu_make_filter(srcn, dstn, kernel, &b.nt, b.hpos.data(), co.data(), 256);
+    if (rc) { set_error("resize %d -> %d needs more than 256 taps", srcn, dstn); return rc; }
+    co.resize((size_t)dstn * b.nt);
+  }
+  b.hco = co;
+  if (b.nt <= 8 && !(b.nt & 1) && srcn == 2 * dstn && kernel != 100) {
+    // k_half8s takes any uniform 2:1 filter that embeds into its 8-tap window: bicubic (8 taps) and, zero padded on both sides, bilinear (4 taps)
+    const int pad = (8 - b.nt) / 2;
+    b.uniform2 = 1;
+    for (int i = 0; i < dstn && b.uniform2; i++) {
+      if (b.hpos[i] != 2 * i - 3 + pad) b.uniform2 = 0;
+      for (int j = 0; j < b.nt; j++) {
+        const int c = co[(size_t)i * b.nt + j];
+        if (c != co[j] || (c >> 6) < -128 || (c >> 6) > 127) b.uniform2 = 0;
+      }
+    }
+    if (b.uniform2) for (int j = 0; j < b.nt; j++) b.taps8[pad + j] = co[j];
+  }
+  b.nph = (b.nt + 1) / 2; b.npv = b.nt / 2 + 1;
+  std::vector<uint32_t> &h2 = *h2p, &v2 = *v2p;
+  h2.assign((size_t)dstn * b.nph, 0u); v2.assign((size_t)dstn * b.npv, 0u);
+  auto pk = [](int lo, int hi) { return (uint32_t)(uint16_t)lo | ((uint32_t)(uint16_t)hi << 16); };
+  for (int i = 0; i < dstn; i++) {
+    const int16_t *c = co.data() + (size_t)i * b.nt;
+    for (int j = 0; j < b.nph; j++) h2[(size_t)i * b.nph + j] = pk(c[2 * j], 2 * j + 1 < b.nt ? c[2 * j + 1] : 0);
+    const int odd = b.hpos[i] & 1;                                  // first tap on the second row of its (even-aligned) pair
+    for (int j = 0; j < b.npv; j++) {
+      const int t0 = 2 * j - odd, t1 = t0 + 1;
+      v2[(size_t)i * b.npv + j] = pk(t0 >= 0 && t0 < b.nt ? c[t0] : 0, t1 >= 0 && t1 < b.nt ? c[t1] : 0);
+    }
+  }
+  return LGPU_OK;
+}
+
 static int get_bank(int srcn, int dstn, int kernel, const Bank **out) {
   int dev = 0;
   LGPU_HIP(hipGetDevice(&dev));
@@ -1498,55 +1545,17 @@ static int get_bank(int srcn, int dstn, int kernel, const Bank **out) {
   auto it = g_banks.find(key);
   if (it == g_banks.end()) {
     Bank b;
-    std::vector<int16_t> co;
-    b.hpos.resize(dstn);
-    if (kernel == 100) {
-      b.nt = 5;
-      co.resize((size_t)dstn * 5);
-      static const int16_t g5[5] = {1, 4, 6, 4, 1};
-      for (int i = 0; i < dstn; i++) { b.hpos[i] = i - 2; for (int j = 0; j < 5; j++) co[(size_t)i * 5 + j] = g5[j]; }
-    } else {
-      co.resize((size_t)dstn * 256);
-      int rc = lgpu_make_filter(srcn, dstn, kernel, &b.nt, b.hpos.data(), co.data(), 256);
-      if (rc) { set_error("resize %d -> %d needs more than 256 taps", srcn, dstn); return rc; }
-      co.resize((size_t)dstn * b.nt);
-    }
-    b.hco = co;
-    if (b.nt <= 8 && !(b.nt & 1) && srcn == 2 * dstn && kernel != 100) {
-      // k_half8s takes any uniform 2:1 filter that embeds into its 8-tap window: bicubic (8 taps) and, zero padded on both sides, bilinear (4 taps)
-      const int pad = (8 - b.nt) / 2;
-      b.uniform2 = 1;
-      for (int i = 0; i < dstn && b.uniform2; i++) {
-        if (b.hpos[i] != 2 * i - 3 + pad) b.uniform2 = 0;
-        for (int j = 0; j < b.nt; j++) {
-          const int c = co[(size_t)i * b.nt + j];
-          if (c != co[j] || (c >> 6) < -128 || (c >> 6) > 127) b.uniform2 = 0;
-        }
-      }
-      if (b.uniform2) for (int j = 0; j < b.nt; j++) b.taps8[pad + j] = co[j];
-    }
-    {
-      b.nph = (b.nt + 1) / 2; b.npv = b.nt / 2 + 1;
-      std::vector<uint32_t> h2((size_t)dstn * b.nph), v2((size_t)dstn * b.npv);
-      auto pk = [](int lo, int hi) { return (uint32_t)(uint16_t)lo | ((uint32_t)(uint16_t)hi << 16); };
-      for (int i = 0; i < dstn; i++) {
-        const int16_t *c = co.data() + (size_t)i * b.nt;
-        for (int j = 0; j < b.nph; j++) h2[(size_t)i * b.nph + j] = pk(c[2 * j], 2 * j + 1 < b.nt ? c[2 * j + 1] : 0);
-        const int odd = b.hpos[i] & 1;                                  // first tap on the second row of its (even-aligned) pair
-        for (int j = 0; j < b.npv; j++) {
-          const int t0 = 2 * j - odd, t1 = t0 + 1;
-          v2[(size_t)i * b.npv + j] = pk(t0 >= 0 && t0 < b.nt ? c[t0] : 0, t1 >= 0 && t1 < b.nt ? c[t1] : 0);
-        }
-      }
-      LGPU_HIP(hipMalloc((void **)&b.co2h, sizeof(uint32_t) * h2.size()));
-      LGPU_HIP(hipMalloc((void **)&b.co2v, sizeof(uint32_t) * v2.size()));
-      LGPU_HIP(hipMemcpy(b.co2h, h2.data(), sizeof(uint32_t) * h2.size(), hipMemcpyHostToDevice));
-      LGPU_HIP(hipMemcpy(b.co2v, v2.data(), sizeof(uint32_t) * v2.size(), hipMemcpyHostToDevice));
-    }
+    std::vector<uint32_t> h2, v2;
+    int rc = build_bank_host(srcn, dstn, kernel, &b, &h2, &v2);
+    if (rc) return rc;
+    LGPU_HIP(hipMalloc((void **)&b.co2h, sizeof(uint32_t) * h2.size()));
+    LGPU_HIP(hipMalloc((void **)&b.co2v, sizeof(uint32_t) * v2.size()));
+    LGPU_HIP(hipMemcpy(b.co2h, h2.data(), sizeof(uint32_t) * h2.size(), hipMemcpyHostToDevice));
+    LGPU_HIP(hipMemcpy(b.co2v, v2.data(), sizeof(uint32_t) * v2.size(), hipMemcpyHostToDevice));
     LGPU_HIP(hipMalloc((void **)&b.pos, sizeof(int32_t) * dstn));
-    LGPU_HIP(hipMalloc((void **)&b.co, sizeof(int16_t) * co.size()));
+    LGPU_HIP(hipMalloc((void **)&b.co, sizeof(int16_t) * b.hco.size()));
     LGPU_HIP(hipMemcpy(b.pos, b.hpos.data(), sizeof(int32_t) * dstn, hipMemcpyHostToDevice));
-    LGPU_HIP(hipMemcpy(b.co, co.data(), sizeof(int16_t) * co.size(), hipMemcpyHostToDevice));
+    LGPU_HIP(hipMemcpy(b.co, b.hco.data(), sizeof(int16_t) * b.hco.size(), hipMemcpyHostToDevice));
     it = g_banks.emplace(key, std::move(b)).first;
   }
   *out = &it->second;
@@ -1646,25 +1655,33 @@ static int xcd_stride_grid(int grid, int tiles_x) {
   return w << 3;
 }
 
-// returns LGPU_OK and launches when the fast path applies; LGPU_E_UNSUPPORTED when it does not
-static int try_half8(const Bank *hb, const Bank *vb, int sw, int sh, int irow, int dw, int dh, int orow, int swap_rb, int blend,
-                     int irow2, uint32_t bf, const int32_t *bf_d, int use_lut, const SepTracks &t, int ntracks, const Lut8 &l,
-                     hipStream_t st, int nt_out = 1) {
-  if (!hb->uniform2 || !vb->uniform2) return LGPU_E_UNSUPPORTED;
-  if ((irow & 3) || (orow & 3)) return LGPU_E_UNSUPPORTED;
+// does k_half8s take this resize?  (host only; the caller has checked that frames and rowstrides are 4-byte aligned)
+static bool half8_applies(const Bank *hb, const Bank *vb, int irow, int orow) {
+  if (!hb->uniform2 || !vb->uniform2) return false;
+  if ((irow & 3) || (orow & 3)) return false;
   {   // operand ranges of the int8 / int16 forms used by the kernel
     int hsum = 0, vsum = 0, hneg = 0;
     for (int j = 0; j < 8; j++) {
       const int th_ = hb->taps8[j], tv = vb->taps8[j];
-      if (th_ < -8192 || th_ >= 8192) return LGPU_E_UNSUPPORTED;       // tap >> 6 must fit int8
+      if (th_ < -8192 || th_ >= 8192) return false;       // tap >> 6 must fit int8
       hsum += th_; vsum += tv; if (th_ < 0) hneg -= th_;
     }
-    if (hsum != 16384 || vsum != 16384 || hneg > 4096) return LGPU_E_UNSUPPORTED;   // |t - 16384| <= 16384 + 2 * hneg + 1 < 2^15
+    if (hsum != 16384 || vsum != 16384 || hneg > 4096) return false;   // |t - 16384| <= 16384 + 2 * hneg + 1 < 2^15
   }
-  // 16-byte aligned requests when every source row starts 16-byte aligned: the window then starts at source x = 2 * tx0 - 4
-  // (a multiple of four pixels) and the tap matrix is shifted by one pixel instead
-  int xoff = ((irow & 15) == 0) ? 1 : 0;
-  for (int i = 0; i < ntracks; i++) if ((uintptr_t)t.src[i] & 15) xoff = 0;
+  return true;
+}
+// 16-byte aligned requests when every source row starts 16-byte aligned (src_bits: the OR of the source pointers): the window then starts at source
+// x = 2 * tx0 - 4 (a multiple of four pixels) and the tap matrix is shifted by one pixel instead
+static void half8_tiles(int dw, int dh, int *tiles_x, int *tiles_y) { *tiles_x = (dw + kTileW - 1) / kTileW; *tiles_y = (dh + H8S::kTileH - 1) / H8S::kTileH; }
+static int half8_xoff(uintptr_t src_bits, int irow) { return ((src_bits | (uintptr_t)irow) & 15) == 0 ? 1 : 0; }
+
+// k_half8s for a resize half8_applies admitted
+static int launch_half8(const Bank *hb, const Bank *vb, int sw, int sh, int irow, int dw, int dh, int orow, int swap_rb, int blend,
+                        int irow2, uint32_t bf, const int32_t *bf_d, int use_lut, const SepTracks &t, int ntracks, const Lut8 &l,
+                        hipStream_t st, int nt_out = 1) {
+  uintptr_t src_bits = 0;
+  for (int i = 0; i < ntracks; i++) src_bits |= (uintptr_t)t.src[i];
+  const int xoff = half8_xoff(src_bits, irow);
   const Half8Const *hc;
   int rc = get_half8_const(hb->taps8, swap_rb, xoff, &hc);
   if (rc) return rc;
@@ -1679,7 +1696,7 @@ static int try_half8(const Bank *hb, const Bank *vb, int sw, int sh, int irow, i
   a.nt_out = nt_out;
   // persistent grid: as many workgroups as stay resident (two per CU by LDS), each walks its XCD's share of the work list
   const int g_cus = device_cus();
-  a.tiles_x = (dw + kTileW - 1) / kTileW; a.tiles_y = (dh + H8S::kTileH - 1) / H8S::kTileH;
+  half8_tiles(dw, dh, &a.tiles_x, &a.tiles_y);
   const int nwork = a.tiles_x * a.tiles_y * ntracks;
   const size_t lds = H8SL::kLds;
   int grid = g_cus * (int)(160 * 1024 / lds);
@@ -1700,7 +1717,9 @@ struct SepPlan {
   SepArgs a;
   size_t lds;
   dim3 grid;
-  int variant;   // 0 generic taps, 1 = (8,8), 2 = (5,5), 3 = (4,4), 4 = (2,2), 5 = (6,6); 100 + nph: k_sep2
+  int variant;   // 0: k_separable<0, 0> (taps at run time): tap pair counts without a k_sep2 instantiation, more than 64 vertical taps, or a k_sep2 count whose
+                 // (slightly larger: even row pairs + 2) window passes 160 KB at one-row tiles while k_separable's still fits; 100 + nph: k_sep2
+  int th_start = 16;   // the tile height the LDS budget started from (a.th, and p_th, below it: halved to fit)
   // k_sep2p (persistent workgroups, prefetched windows) for the same taps: its own tile height / window rows; taken at launch when the source rows
   // are 16-byte aligned
   bool pers = false;
@@ -1714,6 +1733,7 @@ struct SepPlan {
 static int plan_sep(const Bank *hb, const Bank *vb, int sw, int sh, int irow, int dw, int dh, int orow, int ntracks,
                     int hround, int hshift, int vround, int vshift, SepPlan *p) {
   SepArgs &a = p->a;
+  p->th_start = 16; p->pers = false; p->mh_r = p->mh_c0 = p->mh_kb = p->mh_nt = 0;
   a.ntracks = ntracks; a.hco2 = a.vco2 = nullptr; a.nph = a.npv = 0; a.bfrag = nullptr; a.mh_r = 0;
   a.sw = sw; a.sh = sh; a.irow = irow; a.dw = dw; a.dh = dh; a.orow = orow;
   a.hpos = hb->pos; a.hco = hb->co; a.nth = hb->nt;
@@ -1731,8 +1751,7 @@ static int plan_sep(const Bank *hb, const Bank *vb, int sw, int sh, int irow, in
   a.tiles_x = (dw + kTileW - 1) / kTileW;
   a.tiles_y = (dh + a.th - 1) / a.th;
   p->grid = dim3((unsigned)(a.tiles_x * a.tiles_y), (unsigned)ntracks, 1);
-  p->variant = (a.nth == 8 && a.ntv == 8) ? 1 : (a.nth == 5 && a.ntv == 5) ? 2 : (a.nth == 4 && a.ntv == 4) ? 3 :
-               (a.nth == 2 && a.ntv == 2) ? 4 : (a.nth == 6 && a.ntv == 6) ? 5 : 0;
+  p->variant = 0;
   // k_sep2 (dot2 on both passes): tap pair counts with an instantiation, windows that leave two workgroups per CU
   const int nph = hb->nph;
   if ((nph == 1 || nph == 2 || nph == 3 || nph == 4 || nph == 5 || nph == 6 || nph == 7 || nph == 8 || nph == 10 || nph == 12) && vb->nt <= 64) {
@@ -1757,7 +1776,8 @@ static int plan_sep(const Bank *hb, const Bank *vb, int sw, int sh, int irow, in
     };
     // tile height: 16 rows, 32 when enlarging (small windows: taller tiles amortise a workgroup's three phases; measured 29.8 against 33.9 us for
     // 1080p -> 4K, profiles/r02/resize_ratios.md)
-    for (int th2 = dh > sh ? 32 : 16;; th2 >>= 1) {
+    const int th2_start = dh > sh ? 32 : 16;
+    for (int th2 = th2_start;; th2 >>= 1) {
       const int sht2 = window_rows(th2);
       const size_t lds2 = (size_t)sht2 * b.swt * 4 + (size_t)(sht2 >> 1) * kTileW * 16 + 256 + (size_t)th2 * (vb->npv + 1) * 4;
       if (lds2 <= 80 * 1024 || th2 == 1) {
@@ -1768,6 +1788,7 @@ static int plan_sep(const Bank *hb, const Bank *vb, int sw, int sh, int irow, in
           p->lds = lds2;
           p->grid = dim3((unsigned)(a.tiles_x * a.tiles_y), (unsigned)ntracks, 1);
           p->variant = 100 + nph;
+          p->th_start = th2_start;
         }
         break;
       }
@@ -1793,7 +1814,7 @@ static int plan_sep(const Bank *hb, const Bank *vb, int sw, int sh, int irow, in
     }
     // k_sep2p: two window slots + double-buffered tables must leave two workgroups per CU; a window is at most kS2pMaxReq DMA requests
     if (pers_ok) {
-      for (int th2 = dh > sh ? 32 : 16; th2 >= 1; th2 >>= 1) {
+      for (int th2 = th2_start; th2 >= 1; th2 >>= 1) {
         const int sht2 = window_rows(th2);
         const S2pLds L(sht2, a.swt, th2, vb->npv, p->mh_r ? 1 : nph);
         if (L.total <= 80 * 1024 && sht2 * (a.swt >> 2) <= kS2pMaxReq * 64 && th2 * (vb->npv + 1) <= 256 && vb->npv <= kS2pMaxNpv) {
@@ -1841,6 +1862,43 @@ static int sep2p_bfrag(const SepPlan &p, const void **out) {
   return LGPU_OK;
 }
 
+// does a planned launch go to k_sep2p (p.a.vec set by the caller: 16-byte aligned source rows)?  It pays when a workgroup gets a few tiles to pipeline and the
+// windows are the heavy part (shrinking); measured in profiles/r02/resize_ratios.md.  SEP2P_FORCE (tests): the persistent kernel on small frames
+static bool sep2p_taken(const SepPlan &p) {
+  const bool s2p_force = tune_on(TUNE_SEP2P_FORCE);
+  return p.pers && p.a.vec && p.variant >= 100 &&
+         (s2p_force || (p.p_th >= 4 && (p.mh_r || (p.a.dh < p.a.sh && (long)p.a.tiles_x * p.p_tiles_y * (long)p.grid.y >= 3L * 512))));      // 2-row tiles (4:1: 498 against 470 us for 16 x 4K -> 960 x 540) lose to k_sep2
+}
+// k_sep2p's arguments for a plan (bfrag left to the launch); returns the dynamic LDS bytes
+static size_t sep2p_args(const SepPlan &p, SepArgs *out) {
+  SepArgs &ap = *out;
+  ap = p.a;
+  ap.th = p.p_th; ap.sht = p.p_sht; ap.tiles_y = p.p_tiles_y; ap.ntracks = (int)p.grid.y;
+  ap.bfrag = nullptr; ap.mh_r = p.mh_r;
+  return p.mh_r ? S2pLds(ap.sht, ap.swt, ap.th, ap.npv, 1).total : p.p_lds;
+}
+
+// Which kernel serves a resize: the one decision lgpu_resize, lgpu_chain's polyphase stage and lgpu_debug_resize_plan share.  mode LGPU_PLAN_*; al4: every frame
+// and rowstride of the call is 4-byte aligned; src_bits: the OR of the source addresses.  *path = LGPU_PATH_*; for the separable paths *p is the plan with a.vec set (the per-call
+// fields -- src_sel, blend, LUT -- are the caller's).  LGPU_PATH_REFUSED comes with the error code as the return value.
+static int route_resize(const Bank *hb, const Bank *vb, int sw, int sh, int irow, int dw, int dh, int orow, int psize, bool al4, uintptr_t src_bits,
+                        int ntracks, int mode, SepPlan *p, int *path) {
+  *path = LGPU_PATH_GENERIC;
+  if (!(psize == 4 && al4)) {
+    if (mode == LGPU_PLAN_RESIZE) return LGPU_OK;                                // the two generic passes
+    *path = LGPU_PATH_REFUSED;                                                   // (lgpu_chain_check has refused such frames before a chain comes here)
+    set_error("the chain takes 4-byte aligned RGBA frames");
+    return LGPU_E_BADARG;
+  }
+  if (half8_applies(hb, vb, irow, orow)) { *path = LGPU_PATH_HALF8S; return LGPU_OK; }
+  const int rc = plan_sep(hb, vb, sw, sh, irow, dw, dh, orow, ntracks, 64, 7, 1 << 20, 21, p);
+  if (rc == LGPU_E_UNSUPPORTED && mode == LGPU_PLAN_RESIZE) return LGPU_OK;      // a window no LDS holds: generic
+  if (rc) { *path = LGPU_PATH_REFUSED; return rc; }
+  p->a.vec = ((src_bits | (uintptr_t)irow) & 15) == 0;
+  *path = sep2p_taken(*p) ? (p->mh_r ? LGPU_PATH_SEP2P_MFMA : LGPU_PATH_SEP2P) : p->variant >= 100 ? LGPU_PATH_SEP2 : LGPU_PATH_SEPARABLE;
+  return LGPU_OK;
+}
+
 static int launch_sep(const SepPlan &p, const SepTracks &t, const Lut8 &l, hipStream_t st) {
   const dim3 blk(kBlock);
 #define SEP_LAUNCH(H, V)                                                                                     \
@@ -1855,18 +1913,12 @@ static int launch_sep(const SepPlan &p, const SepTracks &t, const Lut8 &l, hipSt
       LGPU_HIP(hipFuncSetAttribute((const void *)k_sep2<N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds)); \
     hipLaunchKernelGGL((k_sep2<N>), p.grid, blk, p.lds, st, p.a, t, l);                                      \
   } while (0)
-  const bool s2p_force = tune_on(TUNE_SEP2P_FORCE);          // tests: the persistent kernel on small frames
-  // k_sep2p pays when a workgroup gets a few tiles to pipeline and the windows are the heavy part (shrinking); measured in profiles/r02/resize_ratios.md
-  if (p.pers && p.a.vec && p.variant >= 100 &&
-      (s2p_force || (p.p_th >= 4 && (p.mh_r || (p.a.dh < p.a.sh && (long)p.a.tiles_x * p.p_tiles_y * (long)p.grid.y >= 3L * 512))))) {      // 2-row tiles (4:1: 498 against 470 us for 16 x 4K -> 960 x 540) lose to k_sep2
-    SepArgs ap = p.a;
-    ap.th = p.p_th; ap.sht = p.p_sht; ap.tiles_y = p.p_tiles_y; ap.ntracks = (int)p.grid.y;
-    ap.bfrag = nullptr; ap.mh_r = p.mh_r;
-    size_t lds_launch = p.p_lds;
+  if (sep2p_taken(p)) {
+    SepArgs ap;
+    const size_t lds_launch = sep2p_args(p, &ap);
     if (p.mh_r) {
       int rc = sep2p_bfrag(p, &ap.bfrag);
       if (rc) return rc;
-      lds_launch = S2pLds(ap.sht, ap.swt, ap.th, ap.npv, 1).total;
     }
     const int g_cus = device_cus();
     const int nwork = ap.tiles_x * ap.tiles_y * ap.ntracks;
@@ -1915,11 +1967,6 @@ static int launch_sep(const SepPlan &p, const SepTracks &t, const Lut8 &l, hipSt
   case 108: SEP2_LAUNCH(8); break;
   case 110: SEP2_LAUNCH(10); break;
   case 112: SEP2_LAUNCH(12); break;
-  case 1: SEP_LAUNCH(8, 8); break;
-  case 2: SEP_LAUNCH(5, 5); break;
-  case 3: SEP_LAUNCH(4, 4); break;
-  case 4: SEP_LAUNCH(2, 2); break;
-  case 5: SEP_LAUNCH(6, 6); break;
   default: SEP_LAUNCH(0, 0); break;
   }
 #undef SEP_LAUNCH
@@ -1988,23 +2035,16 @@ extern "C" int lgpu_resize(const uint8_t *src_d, int irow, int sw, int sh, uint8
   if ((rc = get_bank(sh, dh, kernel, &vb))) return rc;
   hipStream_t st = (hipStream_t)stream;
   const Lut8 l = pack_lut(lut8);
+  SepPlan p;
+  int path;
   const bool al4 = (((uintptr_t)src_d | (uintptr_t)irow | (uintptr_t)dst_d | (uintptr_t)orow) & 3) == 0;
-  if (psize == 4 && al4) {
-    SepPlan p;
-    {
-      SepTracks t1;
-      t1.src[0] = src_d; t1.l2[0] = nullptr; t1.dst[0] = dst_d;
-      rc = try_half8(hb, vb, sw, sh, irow, dw, dh, orow, 0, 0, 0, 0, nullptr, lut8 ? 1 : 0, t1, 1, l, st);
-      if (rc != LGPU_E_UNSUPPORTED) return rc;
-    }
-    if ((rc = plan_sep(hb, vb, sw, sh, irow, dw, dh, orow, 1, 64, 7, 1 << 20, 21, &p)) == LGPU_OK) {
-      p.a.src_sel = 0x03020100u; p.a.blend = 0; p.a.irow2 = 0; p.a.bf = 0; p.a.nbf = 255; p.a.bf_d = nullptr; p.a.use_lut = lut8 ? 1 : 0;
-      p.a.vec = (((uintptr_t)src_d | (uintptr_t)irow) & 15) == 0;
-      SepTracks t;
-      t.src[0] = src_d; t.l2[0] = nullptr; t.dst[0] = dst_d;
-      return launch_sep(p, t, l, st);
-    }
-    if (rc != LGPU_E_UNSUPPORTED) return rc;
+  if ((rc = route_resize(hb, vb, sw, sh, irow, dw, dh, orow, psize, al4, (uintptr_t)src_d, 1, LGPU_PLAN_RESIZE, &p, &path))) return rc;
+  if (path != LGPU_PATH_GENERIC) {
+    SepTracks t;
+    t.src[0] = src_d; t.l2[0] = nullptr; t.dst[0] = dst_d;
+    if (path == LGPU_PATH_HALF8S) return launch_half8(hb, vb, sw, sh, irow, dw, dh, orow, 0, 0, 0, 0, nullptr, lut8 ? 1 : 0, t, 1, l, st);
+    p.a.src_sel = 0x03020100u; p.a.blend = 0; p.a.irow2 = 0; p.a.bf = 0; p.a.nbf = 255; p.a.bf_d = nullptr; p.a.use_lut = lut8 ? 1 : 0;
+    return launch_sep(p, t, l, st);
   }
   // generic: horizontal into an int16 scratch, then vertical
   void *scratch;
@@ -2099,20 +2139,19 @@ static int chain_launch(const lgpu_chain_params *pr, const lgpu_chain_track *tra
   const uint32_t sel = pr->swap_rb ? 0x03000102u : 0x03020100u;   // swap3postalpha: [in2 in1 in0 in3]
   const Bank *hb, *vb, *gh, *gv;
   SepTracks t;
-  uintptr_t src_bits = (uintptr_t)pr->irow;
+  uintptr_t src_bits = 0;
   for (int i = 0; i < ntracks; i++) src_bits |= (uintptr_t)tracks[i].src_d;
-  const int src_vec = (src_bits & 15) == 0;
+  int path;
   if (!pr->do_blur) {
     if ((rc = get_bank(pr->sw, pr->dw, kernel, &hb)) || (rc = get_bank(pr->sh, pr->dh, kernel, &vb))) return rc;
     for (int i = 0; i < ntracks; i++) { t.src[i] = tracks[i].src_d; t.l2[i] = tracks[i].layer2_d; t.dst[i] = tracks[i].dst_d; }
-    rc = try_half8(hb, vb, pr->sw, pr->sh, pr->irow, pr->dw, pr->dh, pr->orow, pr->swap_rb ? 1 : 0, 1, pr->irow2, (uint32_t)pr->bf & 0xFF,
-                   pr->param_block_d, pr->use_lut ? 1 : 0, t, ntracks, l, st);
-    if (rc != LGPU_E_UNSUPPORTED) return rc;
     SepPlan p;
-    if ((rc = plan_sep(hb, vb, pr->sw, pr->sh, pr->irow, pr->dw, pr->dh, pr->orow, ntracks, 64, 7, 1 << 20, 21, &p))) return rc;
+    if ((rc = route_resize(hb, vb, pr->sw, pr->sh, pr->irow, pr->dw, pr->dh, pr->orow, 4, true, src_bits, ntracks, LGPU_PLAN_CHAIN, &p, &path))) return rc;      // (4-byte frames and pitches: lgpu_chain_check)
+    if (path == LGPU_PATH_HALF8S)
+      return launch_half8(hb, vb, pr->sw, pr->sh, pr->irow, pr->dw, pr->dh, pr->orow, pr->swap_rb ? 1 : 0, 1, pr->irow2, (uint32_t)pr->bf & 0xFF,
+                          pr->param_block_d, pr->use_lut ? 1 : 0, t, ntracks, l, st);
     p.a.src_sel = sel; p.a.blend = 1; p.a.irow2 = pr->irow2; p.a.bf = (uint32_t)pr->bf & 0xFF; p.a.nbf = 0xFF - p.a.bf; p.a.bf_d = pr->param_block_d;
-    p.a.use_lut = pr->use_lut ? 1 : 0; p.a.vec = src_vec;
-    for (int i = 0; i < ntracks; i++) { t.src[i] = tracks[i].src_d; t.l2[i] = tracks[i].layer2_d; t.dst[i] = tracks[i].dst_d; }
+    p.a.use_lut = pr->use_lut ? 1 : 0;
     return launch_sep(p, t, l, st);
   }
   // with blur: resize into scratch (per track), then gaussian with the blend + gamma epilogue
@@ -2123,12 +2162,15 @@ static int chain_launch(const lgpu_chain_params *pr, const lgpu_chain_track *tra
   if ((rc = get_bank(pr->sw, pr->dw, kernel, &hb)) || (rc = get_bank(pr->sh, pr->dh, kernel, &vb))) return rc;
   if ((rc = get_bank(pr->dw, pr->dw, 100, &gh)) || (rc = get_bank(pr->dh, pr->dh, 100, &gv))) return rc;
   SepPlan p1, p2;
-  if ((rc = plan_sep(hb, vb, pr->sw, pr->sh, pr->irow, pr->dw, pr->dh, pr->dw * 4, ntracks, 64, 7, 1 << 20, 21, &p1))) return rc;
-  p1.a.src_sel = sel; p1.a.blend = 0; p1.a.irow2 = 0; p1.a.bf = 0; p1.a.nbf = 255; p1.a.bf_d = nullptr; p1.a.use_lut = 0; p1.a.vec = src_vec;
+  if ((rc = route_resize(hb, vb, pr->sw, pr->sh, pr->irow, pr->dw, pr->dh, pr->dw * 4, 4, true, src_bits, ntracks, LGPU_PLAN_CHAIN_BLUR, &p1, &path))) return rc;
   for (int i = 0; i < ntracks; i++) { t.src[i] = tracks[i].src_d; t.l2[i] = nullptr; t.dst[i] = (uint8_t *)scratch + per * i; }
-  rc = try_half8(hb, vb, pr->sw, pr->sh, pr->irow, pr->dw, pr->dh, pr->dw * 4, pr->swap_rb ? 1 : 0, 0, 0, 0, nullptr, 0, t, ntracks, pack_lut(nullptr), st,
-                 0);      // the scratch frames are read back by the gaussian launch right behind: ordinary stores (non-temporal measured the same, 250.4 against 250.1 us)
-  if (rc == LGPU_E_UNSUPPORTED) rc = launch_sep(p1, t, pack_lut(nullptr), st);
+  if (path == LGPU_PATH_HALF8S) {
+    rc = launch_half8(hb, vb, pr->sw, pr->sh, pr->irow, pr->dw, pr->dh, pr->dw * 4, pr->swap_rb ? 1 : 0, 0, 0, 0, nullptr, 0, t, ntracks, pack_lut(nullptr), st,
+                      0);      // the scratch frames are read back by the gaussian launch right behind: ordinary stores (non-temporal measured the same, 250.4 against 250.1 us)
+  } else {
+    p1.a.src_sel = sel; p1.a.blend = 0; p1.a.irow2 = 0; p1.a.bf = 0; p1.a.nbf = 255; p1.a.bf_d = nullptr; p1.a.use_lut = 0;
+    rc = launch_sep(p1, t, pack_lut(nullptr), st);
+  }
   if (rc) return rc;
   for (int i = 0; i < ntracks; i++) { t.src[i] = (uint8_t *)scratch + per * i; t.l2[i] = tracks[i].layer2_d; t.dst[i] = tracks[i].dst_d; }
   rc = try_gauss5x(pr->dw, pr->dh, pr->dw * 4, pr->orow, 1, pr->irow2, (uint32_t)pr->bf, pr->param_block_d, pr->use_lut ? 1 : 0, t, ntracks, l, st);
@@ -2165,4 +2207,42 @@ extern "C" int lgpu_chain_timed(const lgpu_chain_params *params, const lgpu_chai
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   return rc;
+}
+
+// the plan of a call on host-built banks: the same route_resize, and for k_sep2p the same sep2p_args, as the launches
+extern "C" int lgpu_debug_resize_plan(const lgpu_resize_plan_query *q, lgpu_resize_plan *out) {
+  LGPU_REQUIRE(q && out, "null query");
+  LGPU_REQUIRE(q->mode == LGPU_PLAN_RESIZE || q->mode == LGPU_PLAN_CHAIN || q->mode == LGPU_PLAN_CHAIN_BLUR, "mode must be LGPU_PLAN_*");
+  LGPU_REQUIRE(q->sw > 0 && q->sh > 0 && q->dw > 0 && q->dh > 0, "empty geometry");
+  LGPU_REQUIRE(q->psize == 1 || q->psize == 3 || q->psize == 4, "psize must be 1, 3 or 4");
+  LGPU_REQUIRE(q->irow >= q->sw * q->psize && q->orow >= q->dw * q->psize, "rowstride smaller than a row");
+  LGPU_REQUIRE(q->ntracks > 0 && q->ntracks <= LGPU_CHAIN_MAX_TRACKS && (q->mode != LGPU_PLAN_RESIZE || q->ntracks == 1), "1 track for a resize, 1..64 for a chain");
+  LGPU_REQUIRE(q->mode == LGPU_PLAN_RESIZE || !(q->sw == q->dw && q->sh == q->dh), "the chain needs a resize stage");
+  *out = lgpu_resize_plan{};
+  const int kernel = kernel_for_interp(q->mode == LGPU_PLAN_RESIZE ? q->interp : q->interp & 0xFF, q->dw > q->sw || q->dh > q->sh);      // as lgpu_resize / chain_launch pass it
+  out->kernel = kernel;
+  Bank hb, vb;
+  std::vector<uint32_t> h2, v2;
+  int rc;
+  if ((rc = build_bank_host(q->sw, q->dw, kernel, &hb, &h2, &v2)) || (rc = build_bank_host(q->sh, q->dh, kernel, &vb, &h2, &v2))) {
+    out->path = LGPU_PATH_REFUSED; out->rc = rc;
+    return LGPU_OK;
+  }
+  out->nth = hb.nt; out->ntv = vb.nt; out->nph = hb.nph; out->npv = vb.npv;
+  const int orow = q->mode == LGPU_PLAN_CHAIN_BLUR ? q->dw * 4 : q->orow;          // the blur's intermediate frames are compact
+  SepPlan p;
+  const bool al4 = ((q->src_bits | q->dst_bits | (unsigned)q->irow | (unsigned)q->orow) & 3) == 0;      // lgpu_resize's test; what lgpu_chain_check demands of a chain
+  out->rc = route_resize(&hb, &vb, q->sw, q->sh, q->irow, q->dw, q->dh, orow, q->psize, al4, q->src_bits, q->ntracks, q->mode, &p, &out->path);
+  if (out->path == LGPU_PATH_HALF8S) {
+    out->th = out->th_start = H8S::kTileH; out->lds = (int)H8SL::kLds; out->xoff = half8_xoff(q->src_bits, q->irow);
+    half8_tiles(q->dw, q->dh, &out->tiles_x, &out->tiles_y);
+  } else if (out->path != LGPU_PATH_GENERIC && out->path != LGPU_PATH_REFUSED) {
+    SepArgs a = p.a;
+    size_t lds = p.lds;
+    if (out->path == LGPU_PATH_SEP2P || out->path == LGPU_PATH_SEP2P_MFMA) lds = sep2p_args(p, &a);
+    out->th = a.th; out->th_start = p.th_start; out->sht = a.sht; out->swt = a.swt; out->lds = (int)lds;
+    out->tiles_x = a.tiles_x; out->tiles_y = a.tiles_y; out->vec = a.vec;
+    if (out->path == LGPU_PATH_SEP2P_MFMA) { out->mh_r = p.mh_r; out->mh_c0 = p.mh_c0; out->mh_kb = p.mh_kb; }
+  }
+  return LGPU_OK;
 }

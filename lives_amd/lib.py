@@ -89,6 +89,22 @@ class ChainParams(ctypes.Structure):
                 ("lut8", ctypes.c_uint8 * 256), ("param_block_d", vp)]
 
 
+class ResizePlanQuery(ctypes.Structure):
+    """lgpu_resize_plan_query"""
+    _fields_ = [("sw", ci), ("sh", ci), ("dw", ci), ("dh", ci), ("psize", ci), ("interp", ci), ("irow", ci), ("orow", ci),
+                ("src_bits", ctypes.c_uint), ("dst_bits", ctypes.c_uint), ("ntracks", ci), ("mode", ci)]
+
+
+class ResizePlan(ctypes.Structure):
+    """lgpu_resize_plan"""
+    _fields_ = [(n, ci) for n in ("path", "rc", "kernel", "nth", "ntv", "nph", "npv", "th", "th_start", "sht", "swt", "lds",
+                                  "mh_r", "mh_c0", "mh_kb", "tiles_x", "tiles_y", "vec", "xoff")]
+
+
+PLAN_RESIZE, PLAN_CHAIN, PLAN_CHAIN_BLUR = range(3)
+PLAN_PATHS = {1: "HALF8S", 2: "SEP2", 3: "SEP2P", 4: "SEP2P_MFMA", 5: "SEPARABLE", 6: "GENERIC", 7: "REFUSED"}      # LGPU_PATH_*
+
+
 class FxFrame(ctypes.Structure):
     _fields_ = [("in0", vp * 4), ("in1", vp * 4), ("out", vp * 4)]
 
@@ -166,6 +182,7 @@ PROTOTYPES = {
     "lgpu_letterbox_at": [vp, ci, ci, ci, vp, ci, ci, ci, ci, vp, ci, ci, vp],
     "lgpu_letterbox_bars": [vp, ci, ci, ci, ci, vp, ci, ci, ci, ci, vp],
     "lgpu_resize": [vp, ci, ci, ci, vp, ci, ci, ci, ci, ci, vp, vp],
+    "lgpu_debug_resize_plan": [ctypes.POINTER(ResizePlanQuery), ctypes.POINTER(ResizePlan)],
     "lgpu_pixbuf_scale": [vp, ci, ci, ci, vp, ci, ci, ci, ci, ci, vp],
     "lgpu_swizzle_batch": [ci, ci, vp, ci, vp, ci, ci, ci, vp, ci, vp],
     "lgpu_gamma_apply_batch": [vp, ci, ci, ci, ci, ci, ci, ci, vp, ci, vp],

@@ -116,6 +116,19 @@ def resize(src, dst, sw, sh, dw, dh, psize=4, interp=3, lut=None):
              lp[0] if lp else None, stream_ptr())
 
 
+def resize_plan(sw, sh, dw, dh, psize=4, interp=3, irow=None, orow=None, src_bits=0, dst_bits=0, ntracks=1, mode=lib.PLAN_RESIZE):
+    """lgpu_debug_resize_plan: the kernel a resize / polyphase chain of this geometry would launch, as a dict (path by name); host only, no device needed.
+    irow / orow default to compact rows rounded up to 32 bytes; src_bits / dst_bits: the OR of the frames' addresses (only the low four bits count)"""
+    al = lambda n: (n + 31) // 32 * 32
+    q = lib.ResizePlanQuery(sw, sh, dw, dh, psize, interp, al(sw * psize) if irow is None else irow, al(dw * psize) if orow is None else orow,
+                            src_bits & 15, dst_bits & 15, ntracks, mode)
+    out = lib.ResizePlan()
+    lib.call("lgpu_debug_resize_plan", ctypes.byref(q), ctypes.byref(out))
+    d = {n: getattr(out, n) for n, _ in lib.ResizePlan._fields_}
+    d["path"] = lib.PLAN_PATHS[out.path]
+    return d
+
+
 def gauss5_colorkey(src0, src1, dst, width, height, psize, is_bgr, delta, opac, col):
     lib.call("lgpu_gauss5_colorkey", dptr(src0), src0.stride(0), dptr(src1), src1.stride(0), dptr(dst), dst.stride(0), width, height, psize, int(is_bgr),
              float(delta), float(opac), int(col[0]), int(col[1]), int(col[2]), stream_ptr())

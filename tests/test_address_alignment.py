@@ -505,7 +505,7 @@ def run_pixel2(orc, st, kind, ps, extra, n):
 
 # ============================================================================================== resize.hip
 def rule_resize(ps, two_to_one, sb, db):
-    """lgpu_resize: try_half8 (exact 2:1 on 4-aligned frames), then plan_sep with vec on or off, then the generic two passes"""
+    """lgpu_resize: half8_applies (exact 2:1 on 4-aligned frames), then plan_sep with vec on or off, then the generic two passes"""
     if ps == 4 and ((sb | db) & 3) == 0:
         if two_to_one:
             return "k_half8s xoff 1" if (sb & 15) == 0 else "k_half8s xoff 0"
@@ -557,7 +557,7 @@ def l2s_lut(orc):
 
 
 def rule_chain(two_to_one, blur, sb, l2b, db):
-    """lgpu_chain on the polyphase arithmetic: lgpu_chain_check, then try_half8 / plan_sep for the resize stage (into scratch when the blur follows)"""
+    """lgpu_chain on the polyphase arithmetic: lgpu_chain_check, then half8_applies / plan_sep (route_resize) for the resize stage (into scratch when the blur follows)"""
     if (sb | l2b | db) & 3:
         return BADARG
     stage = ("k_half8s xoff 1" if (sb & 15) == 0 else "k_half8s xoff 0") if two_to_one else ("plan_sep vec 1" if (sb & 15) == 0 else "plan_sep vec 0")

@@ -938,13 +938,18 @@ def test_resize_persistent_kernel(gpu, orc, tune):
     cases = [(384, 216, 128, 72, 3), (256, 144, 512, 288, 3), (192, 108, 128, 72, 3), (640, 360, 212, 120, 3), (128, 64, 64, 32, 2), (400, 300, 100, 75, 3),
              (1920, 1080, 1280, 720, 3), (1280, 720, 1920, 1080, 3), (3840, 2160, 1280, 720, 3), (64, 32, 128, 64, 3), (100, 60, 36, 24, 3), (16, 16, 4, 4, 3),
              (3840, 40, 480, 8, 3), (64, 2160, 16, 720, 2), (3840, 2160, 960, 540, 3), (1920, 1080, 480, 270, 3)]
+    # the two cases no switch brings to k_sep2p (lgpu_debug_resize_plan): the exact 2:1 stays with k_half8s, 16 tap pairs per output have no k_sep2 instantiation
+    not_persistent = {(128, 64, 64, 32, 2): "HALF8S", (3840, 40, 480, 8, 3): "SEPARABLE"}
     for (sw, sh, dw, dh, interp) in cases:
         src = frame(rng, sw, sh, 4)
         want = np.zeros((dh, align(dw * 4)), np.uint8)
         assert orc.orc_resize(P(src), src.strides[0], sw, sh, P(want), want.strides[0], dw, dh, 4, interp) == 0
         d = dev(np.zeros_like(want))
-        gpu.resize(dev(src), d, sw, sh, dw, dh, psize=4, interp=interp)
-        assert_same(host(d), want, dw, dh, 4, "resize (k_sep2p) %dx%d->%dx%d interp=%d" % (sw, sh, dw, dh, interp))
+        d_src = dev(src)
+        path = gpu.resize_plan(sw, sh, dw, dh, 4, interp, irow=src.strides[0], orow=want.strides[0], src_bits=d_src.data_ptr(), dst_bits=d.data_ptr())["path"]
+        assert path in ((not_persistent.get((sw, sh, dw, dh, interp)),) if (sw, sh, dw, dh, interp) in not_persistent else ("SEP2P", "SEP2P_MFMA")), (sw, sh, dw, dh, interp, path)
+        gpu.resize(d_src, d, sw, sh, dw, dh, psize=4, interp=interp)
+        assert_same(host(d), want, dw, dh, 4, "resize (%s) %dx%d->%dx%d interp=%d" % (path, sw, sh, dw, dh, interp))
     lut = lut_for(rng, "l2s")
     for (sw, sh, dw, dh, swap, bf, ntr, use_lut) in [(384, 216, 128, 72, 1, 90, 3, 1), (320, 200, 200, 120, 0, 255, 2, 0), (200, 120, 320, 200, 1, 17, 5, 1)]:
         srcs = [frame(rng, sw, sh, 4) for _ in range(ntr)]

@@ -251,7 +251,7 @@ def test_staged_groups(gpu, orc, tune):
 # ---------------------------------------------------------------- e. the polyphase chain
 
 def h8s_grid(dw, dh, n, spare=0):
-    """try_half8's persistent grid (resize.hip): two resident workgroups per CU, less the spare slots, at most the work list, whole groups of 8, and the XCD
+    """launch_half8's persistent grid (resize.hip): two resident workgroups per CU, less the spare slots, at most the work list, whole groups of 8, and the XCD
     stride rule -> (grid, tiles per track)"""
     tiles_x, tiles_y = cdiv(dw, 64), cdiv(dh, 16)
     nwork = tiles_x * tiles_y * n
