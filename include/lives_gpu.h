@@ -506,8 +506,8 @@ int lgpu_chain_to_yuv(const lgpu_chain_params *params, const lgpu_chain_sink *si
                       void *stream);
 /* both ends at once -- a tick from decoded planar 4:2:0 frames to a YUV consumer: the K2 conversion -> [R <-> B] -> scale [-> chroma blend] [-> gamma LUT] -> the K4
    conversion, and neither RGBA frame is ever written.  The bytes are those of lgpu_yuv420p_to_rgb (src's out_order, which_tables, pb_quality, flags), then
-   lgpu_chain_amounts (PIXBUF, optional NOBLEND, LUT), then lgpu_rgb_to_yuv(.., sink->in_order, 1, .., sink->out_fmt, 0, sink->which_tables).  src is read as by
-   lgpu_chain_yuv420p, sink as by lgpu_chain_to_yuv (params->irow and params->orow are ignored in favour of src->istrides and sink->orow); the two table choices are
+   lgpu_chain_amounts (PIXBUF, optional NOBLEND, LUT), then lgpu_rgb_to_yuv(.., sink->in_order, 1, .., sink->out_fmt, 0, sink->which_tables).  src is read and checked
+   as by lgpu_chain_yuv420p, sink as by lgpu_chain_to_yuv -- one set of checks serves these and the lgpu_chain_flat_* forms, docs/KERNELS.md -- (params->irow and params->orow are ignored in favour of src->istrides and sink->orow); the two table choices are
    independent; YVU420P on either end: pass the planes swapped.  sink->in_order states the byte order of the chain's result, which is src->out_order ^
    params->swap_rb: anything else is LGPU_E_BADARG, like every argument either parent refuses (null planes, 0 or 65 tracks, table / format / quality numbers out of
    range, unknown flags, BT.709 with UYVY / YUYV, odd sw or dw, strides or chroma planes too small, no PIXBUF, null amounts with a blend) and a destination plane

@@ -373,68 +373,28 @@ static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv
   FLAT_REQUIRE(pr->interp & LGPU_INTERP_PIXBUF, "the gdk-pixbuf arithmetic only (LGPU_INTERP_PIXBUF)");
   FLAT_REQUIRE(!ys2 || !noblend, "LGPU_INTERP_NOBLEND leaves nothing to mix: lgpu_chain_flat_yuv420p[_to_yuv]");
   FLAT_REQUIRE(amounts || noblend, "null amounts");
-  // the sources' own (lgpu_chain_yuv420p)
-  FLAT_REQUIRE(pr->sw >= 2 && !(pr->sw & 1) && pr->sh >= 1 && pr->dw > 0 && pr->dh > 0, "empty geometry or an odd 4:2:0 width");
   const bool packed = sfmt == 2 || sfmt == 3;
   const int srcp = packed ? 2 : sfmt == 5 ? 1 : 0;      // the kernel's SRC policy
-  const int hw = pr->sw >> 1, hh = srcp ? pr->sh : (pr->sh + 1) >> 1, lys = ys->istrides[0], us = packed ? 0 : ys->istrides[1], vs = packed ? 0 : ys->istrides[2];
+  const int hw = pr->sw >> 1, lys = ys->istrides[0], us = packed ? 0 : ys->istrides[1], vs = packed ? 0 : ys->istrides[2];
   const long usz = packed ? 0 : ys->u_size, vsz = packed ? 0 : ys->v_size;
-  for (const lgpu_yuv_source *s : {ys, ys2}) {
-    if (!s) continue;
-    FLAT_REQUIRE(s->out_order == 0 || s->out_order == 1, "out_order is 0 (RGBA) or 1 (BGRA)");
-    FLAT_REQUIRE(s->which_tables >= 0 && s->which_tables <= 3, "source which_tables is 0..3");
-    FLAT_REQUIRE(s->pb_quality >= 1 && s->pb_quality <= 3, "pb_quality is 1 (LOW), 2 (MED) or 3 (HIGH)");
-    FLAT_REQUIRE(!(s->flags & ~LGPU_YUV_FIX_EDGES), "unknown flags");
-    if (packed) {
-      FLAT_REQUIRE(!(s->which_tables & 2), "UYVY / YUYV are converted with the YCbCr tables only (as lgpu_yuv_to_rgb)");
-      FLAT_REQUIRE(s->istrides[0] >= pr->sw * 2, "plane rowstride smaller than a row");
-      continue;
-    }
-    FLAT_REQUIRE(s->istrides[0] >= pr->sw && s->istrides[1] >= hw && s->istrides[2] >= hw, "plane rowstride smaller than a row");
-    FLAT_REQUIRE(s->u_size >= (long)(hh - 1) * s->istrides[1] + hw && s->v_size >= (long)(hh - 1) * s->istrides[2] + hw,
-                 srcp ? "chroma plane smaller than its (sw / 2) x sh samples" : "chroma plane smaller than its (sw / 2) x (sh / 2) samples");
-  }
+  int rc;
+  if ((rc = check_yuv_source(fn, pr, ys, sfmt)) || (ys2 && (rc = check_yuv_source(fn, pr, ys2, sfmt)))) return rc;
   const int chain_order = (ys->out_order ^ (pr->swap_rb ? 1 : 0)) & 1;
   FLAT_REQUIRE(!ys2 || ys2->out_order == chain_order, "src2->out_order must state the byte order the blend works in: src->out_order ^ params->swap_rb");
   const bool planar = sk && sk->out_fmt >= 4;
   const int nplanes = planar ? 3 : 1;
-  int cw = pr->dw, ch = pr->dh;
-  if (sk) {
-    // the sink's own (lgpu_chain_to_yuv)
-    FLAT_REQUIRE(sk->out_fmt >= 2 && sk->out_fmt <= 5, "out_fmt must be 2 (UYVY), 3 (YUYV), 4 (4:2:0 planar) or 5 (4:2:2 planar)");
-    FLAT_REQUIRE(sk->in_order == 0 || sk->in_order == 1, "in_order is 0 (RGBA) or 1 (BGRA)");
-    FLAT_REQUIRE(sk->which_tables >= 0 && sk->which_tables <= 3, "sink which_tables is 0..3");
-    FLAT_REQUIRE(sk->out_fmt >= 4 || !(sk->which_tables & 2), "only the 4:2:0 / 4:2:2 conversions take a BT.709 subspace (as lgpu_rgb_to_yuv)");
-    FLAT_REQUIRE(!(pr->dw & 1), "an odd destination width");
-    FLAT_REQUIRE(pr->sw < 32768 && pr->sh < 32768, "frame sides must stay below 32768");
-    FLAT_REQUIRE(sk->in_order == chain_order, "sink->in_order must state the byte order of the chain's result: src->out_order ^ params->swap_rb");
-    const int cwid = pr->dw >> 1;
-    FLAT_REQUIRE(!l2rgba || pr->irow2 >= pr->dw * 4, "rowstride smaller than a row");
-    FLAT_REQUIRE(sk->orow[0] >= (planar ? pr->dw : pr->dw * 2) && (!planar || (sk->orow[1] >= cwid && sk->orow[2] >= cwid)), "sink rowstride smaller than a row");
-    FLAT_REQUIRE(!l2rgba || !(pr->irow2 & 3), "rowstrides must be multiples of 4");
-  } else {
-    if (cv) {
-      FLAT_REQUIRE(cv->nwidth >= pr->dw && cv->nheight >= pr->dh && cv->offs_x >= 0 && cv->offs_y >= 0 && cv->offs_x + pr->dw <= cv->nwidth &&
-                   cv->offs_y + pr->dh <= cv->nheight, "the frame must lie inside the canvas");
-      cw = cv->nwidth; ch = cv->nheight;
-    }
-    FLAT_REQUIRE(pr->orow >= cw * 4 && (!l2rgba || pr->irow2 >= cw * 4), "rowstride smaller than a row");
-    FLAT_REQUIRE(((pr->orow | (l2rgba ? pr->irow2 : 0)) & 3) == 0, "rowstrides must be multiples of 4");
-  }
+  const int cw = cv && !sk ? cv->nwidth : pr->dw, ch = cv && !sk ? cv->nheight : pr->dh;
+  if ((rc = sk ? check_yuv_sink(fn, pr, sk, chain_order, l2rgba) : check_rgba_dest(fn, pr, cv, l2rgba))) return rc;
   uintptr_t pb = 0, sb = 0;
   for (int i = 0; i < ntracks; i++) {
     const lgpu_chain_yuv_sink_track &t = tracks[i];
-    FLAT_REQUIRE(t.y_d && (packed || (t.u_d && t.v_d)) && (!l2rgba || t.layer2_d), "null track pointer");
+    const uint8_t *const planes[3] = {t.y_d, t.u_d, t.v_d};
+    if ((rc = check_track(fn, planes, packed ? 1 : 3, false, t.layer2_d, l2rgba, t.dst_d, nplanes, !sk))) return rc;
     sb |= (uintptr_t)t.y_d;
-    FLAT_REQUIRE(!l2rgba || multiple_of((uintptr_t)t.layer2_d, 4), "layer 2 must be 4-byte aligned");
     FLAT_REQUIRE(!mix || (mix[i].y2_d && mix[i].u2_d && mix[i].v2_d), "null layer-2 plane");
-    for (int k = 0; k < nplanes; k++) {
-      FLAT_REQUIRE(t.dst_d[k], "null destination plane");
-      FLAT_REQUIRE((const uint8_t *)t.dst_d[k] != t.y_d && (const uint8_t *)t.dst_d[k] != t.u_d && (const uint8_t *)t.dst_d[k] != t.v_d, "the chain cannot run in place");
+    for (int k = 0; k < nplanes; k++)
       FLAT_REQUIRE(!mix || ((const uint8_t *)t.dst_d[k] != mix[i].y2_d && (const uint8_t *)t.dst_d[k] != mix[i].u2_d && (const uint8_t *)t.dst_d[k] != mix[i].v2_d),
                    "a destination plane is one of layer 2's planes");
-    }
-    FLAT_REQUIRE(sk || multiple_of((uintptr_t)t.dst_d[0], 4), "the destination must be 4-byte aligned");
     pb |= (uintptr_t)t.dst_d[0];
   }
   // the one-launch form; anything else is refused, never run some other way
@@ -452,12 +412,10 @@ static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv
     if (!multiple_of(pb | (uintptr_t)sk->orow[0], planar ? 2 : 4))
       FLAT_REFUSE("packed sinks are stored as 4-byte macropixels (plane and rowstride % 4 == 0), the 4:2:0 luma plane as 2-byte pairs (plane and rowstride % 2 == 0)");
   }
-  const long long lim = 1ll << 31;
   const int drow = sk ? sk->orow[0] : pr->orow;
-  if ((long long)pr->sh * lys >= lim || usz >= lim || vsz >= lim || (long long)ch * drow >= lim || (l2rgba && (long long)ch * pr->irow2 >= lim) ||
-      (ys2 && ((long long)pr->sh * ys2->istrides[0] >= lim || ys2->u_size >= lim || ys2->v_size >= lim)) || (planar && ((long long)(pr->dh >> 1) * sk->orow[1] >= lim || (long long)(pr->dh >> 1) * sk->orow[2] >= lim)))
-    FLAT_REFUSE("planes of 2 GiB or more");
-  int rc;
+  if ((rc = check_plane_sizes(fn, {(long long)pr->sh * lys, usz, vsz, (long long)ch * drow, l2rgba ? (long long)ch * pr->irow2 : 0,
+                                   ys2 ? (long long)pr->sh * ys2->istrides[0] : 0, ys2 ? ys2->u_size : 0, ys2 ? ys2->v_size : 0,
+                                   planar ? (long long)(pr->dh >> 1) * sk->orow[1] : 0, planar ? (long long)(pr->dh >> 1) * sk->orow[2] : 0}))) return rc;
   FlatArgs a;
   memset(&a, 0, sizeof a);
   if (planar && (rc = cavg_forms_checked())) return rc;

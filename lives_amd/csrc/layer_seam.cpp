@@ -25,6 +25,7 @@
 #include <string.h>
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
@@ -632,6 +633,17 @@ void lazy_unread(Lazy *z) {          // (no lock held) the program no longer rea
   if (it != sh.m.end() && it->second.lazy_readers > 0) it->second.lazy_readers--;
   z->l2h = nullptr;
 }
+// the program is over: its source planes go back to the pool.  ran (lazy_run_group): launches on the calling thread's stream have just read them -- the three planes
+// of a YUV program go back with the streams that read them kept (a later taker waits for the writer AND these readers), an RGBA frame with that stream as its last use
+void lazy_free(Lazy *z, bool ran) {
+  Dev src = z->src, yu = z->yu, yv = z->yv;
+  const bool yuv = z->yuv;
+  delete z;
+  if (ran && yuv) { note_use(src, false); note_use(yu, false); note_use(yv, false); }
+  else if (ran) { src.stream = S(); src.nr = 0; }
+  pool_give(src);
+  if (yuv) { pool_give(yu); pool_give(yv); }
+}
 void lazy_discard(Lazy *z) {
   if (!z) return;
   if (z->sink)                          // the entries of the program's other planes point at it too: they go with it (the caller has taken its own out already)
@@ -642,11 +654,7 @@ void lazy_discard(Lazy *z) {
       if (it != sh.m.end() && it->second.lazy == z) sh.m.erase(it);
     }
   lazy_unread(z);
-  Dev src = z->src, yu = z->yu, yv = z->yv;
-  const bool yuv = z->yuv;
-  delete z;
-  pool_give(src);
-  if (yuv) { pool_give(yu); pool_give(yv); }
+  lazy_free(z, false);
 }
 bool lazy_same_shape(const Lazy *a, const Lazy *b) {
   return a->sw == b->sw && a->sh == b->sh && a->srs == b->srs && a->swap == b->swap && a->scale == b->scale && a->dw == b->dw && a->dh == b->dh &&
@@ -691,81 +699,152 @@ int lazy_run_staged(const Lazy *z, uint8_t *out, const uint8_t *src, int srs) {
   for (int i = 0; i < nt; i++) lgpu_free_ordered(tmp[i], S());
   return rc;
 }
-// the RGBA stages of n programs of one shape into outp[i] (rowstride z0->rs): one fused launch where the shape allows, else stage by stage
+// ---- a group of programs of one shape as the arguments of the one-launch forms.  Every public struct is filled from a Lazy HERE and nowhere else. ----
+// to_sink: the group ends at a YUV sink -- no destination rowstride, no layer-2 rowstride without a blend, no OPAQUE word, and the source rowstride is the luma
+// plane's behind YUV planes.  An RGBA destination keeps the recorded frame's rowstride as irow whatever the source (the YUV forms do not read it)
+lgpu_chain_params lazy_params(const Lazy *z, bool to_sink) {
+  lgpu_chain_params pr;
+  memset(&pr, 0, sizeof pr);
+  pr.sw = z->sw; pr.sh = z->sh; pr.dw = z->scale ? z->dw : z->sw; pr.dh = z->scale ? z->dh : z->sh;
+  pr.swap_rb = z->swap ? 1 : 0; pr.interp = (z->scale ? z->interp : 0) | LGPU_INTERP_PIXBUF | (z->blend ? 0 : LGPU_INTERP_NOBLEND); pr.do_blur = 0; pr.use_lut = z->lut ? 1 : 0;
+  if (z->lut) memcpy(pr.lut8, z->lut8, 256);
+  if (to_sink) { pr.irow = z->yuv ? z->ystr[0] : z->srs; pr.irow2 = z->blend ? z->l2rs : 0; pr.orow = 0; }
+  else {
+    pr.irow = z->srs; pr.irow2 = z->blend ? z->l2rs : z->rs; pr.orow = z->rs; pr.bf = z->bf;
+    if (z->scale && z->opaque) pr.interp |= LGPU_INTERP_OPAQUE;
+  }
+  return pr;
+}
+// the decoded frames a YUV program starts from: lgpu_yuv_source (4:2:0 planes; flags stay 0), or lgpu_yuv422_source -- the same description with the format beside
+// it -- for a YUV422P / UYVY / YUYV group (lgpu_chain_flat_yuv422)
+template <class Source> Source lazy_source(const Lazy *z) {
+  Source s;
+  memset(&s, 0, sizeof s);
+  s.istrides[0] = z->ystr[0]; s.istrides[1] = z->ystr[1]; s.istrides[2] = z->ystr[2]; s.u_size = z->usz; s.v_size = z->vsz;
+  s.out_order = z->order; s.which_tables = z->which; s.pb_quality = z->quality;
+  if constexpr (std::is_same<Source, lgpu_yuv422_source>::value) s.in_fmt = z->yfmt;
+  return s;
+}
+lgpu_chain_sink lazy_sink(const Lazy *z) {
+  lgpu_chain_sink sk;
+  memset(&sk, 0, sizeof sk);
+  sk.out_fmt = z->sfmt; sk.which_tables = z->swhich; sk.in_order = z->sorder;
+  for (int p = 0; p < z->snp; p++) sk.orow[p] = z->sors[p];
+  return sk;
+}
+std::vector<uint8_t> lazy_amounts(Lazy *const *zs, int n) {
+  std::vector<uint8_t> am((size_t)n);
+  for (int i = 0; i < n; i++) am[(size_t)i] = (uint8_t)zs[i]->bf;
+  return am;
+}
+// the per-track arrays.  Destinations: outp[i] (one RGBA plane per track) or, for a sink, souts[i][0 .. snp)
+std::vector<lgpu_chain_track> lazy_tracks(Lazy *const *zs, int n, const uint8_t *const *srcp, uint8_t *const *outp) {
+  std::vector<lgpu_chain_track> tr((size_t)n);
+  for (int i = 0; i < n; i++) { tr[(size_t)i].src_d = srcp[i]; tr[(size_t)i].layer2_d = (const uint8_t *)zs[i]->l2.d; tr[(size_t)i].dst_d = outp[i]; }
+  return tr;
+}
+std::vector<lgpu_chain_yuv_track> lazy_yuv_tracks(Lazy *const *zs, int n, uint8_t *const *outp) {
+  std::vector<lgpu_chain_yuv_track> yt((size_t)n);
+  for (int i = 0; i < n; i++) {
+    lgpu_chain_yuv_track &t = yt[(size_t)i];
+    t.y_d = (const uint8_t *)zs[i]->src.d; t.u_d = (const uint8_t *)zs[i]->yu.d; t.v_d = (const uint8_t *)zs[i]->yv.d;
+    t.layer2_d = (const uint8_t *)zs[i]->l2.d; t.dst_d = outp[i];
+  }
+  return yt;
+}
+std::vector<lgpu_chain_yuv_sink_track> lazy_yuv_sink_tracks(Lazy *const *zs, int n, uint8_t *const *outp, Dev (*souts)[3]) {
+  std::vector<lgpu_chain_yuv_sink_track> tr((size_t)n);
+  for (int i = 0; i < n; i++) {
+    lgpu_chain_yuv_sink_track &t = tr[(size_t)i];
+    memset(&t, 0, sizeof t);
+    t.y_d = (const uint8_t *)zs[i]->src.d; t.u_d = (const uint8_t *)zs[i]->yu.d; t.v_d = (const uint8_t *)zs[i]->yv.d;
+    t.layer2_d = (const uint8_t *)zs[i]->l2.d;
+    if (souts) for (int p = 0; p < zs[0]->snp; p++) t.dst_d[p] = (uint8_t *)souts[i][p].d;
+    else t.dst_d[0] = outp[i];
+  }
+  return tr;
+}
+std::vector<lgpu_chain_sink_track> lazy_sink_tracks(Lazy *const *zs, int n, Dev (*souts)[3]) {
+  std::vector<lgpu_chain_sink_track> tr((size_t)n);
+  for (int i = 0; i < n; i++) {
+    lgpu_chain_sink_track &t = tr[(size_t)i];
+    memset(&t, 0, sizeof t);
+    t.src_d = (const uint8_t *)zs[i]->src.d; t.layer2_d = (const uint8_t *)zs[i]->l2.d;
+    for (int p = 0; p < zs[0]->snp; p++) t.dst_d[p] = (uint8_t *)souts[i][p].d;
+  }
+  return tr;
+}
+// the launches of this thread's stream wait for whoever wrote the planes a program reads
+void lazy_await(const Lazy *z) {
+  await(z->src, false);
+  if (z->yuv) { await(z->yu, false); await(z->yv, false); }
+  if (z->blend) await(z->l2, false);
+}
+// What a one-launch route answered: LGPU_OK -- the group is done (true) and the route's counters move: the chain's always, those of the kinds it names beside them,
+// by the call's `launches` and n tracks; LGPU_E_BADARG / LGPU_E_UNSUPPORTED -- the shape is not the form's, the next route takes the group; anything else is the
+// group's error (*rc)
+enum { RT_YUV = 1, RT_SINK = 2, RT_FLAT = 4, RT_TRANSCODE = 8 };
+bool lazy_route(int crc, unsigned kinds, int launches, int n, int *rc) {
+  if (crc != LGPU_OK) {
+    if (crc != LGPU_E_BADARG && crc != LGPU_E_UNSUPPORTED) *rc = crc;
+    return false;
+  }
+  const unsigned long long nl = (unsigned long long)launches, nt = (unsigned long long)n;
+  g_lz_chain_launches += nl; g_lz_chain_tracks += nt;
+  if (kinds & RT_YUV) { g_lz_yuv_launches += nl; g_lz_yuv_tracks += nt; }
+  if (kinds & RT_SINK) { g_lz_sink_launches += nl; g_lz_sink_tracks += nt; g_lz_sink_fused += nl; }
+  if (kinds & RT_FLAT) { g_lz_flat_launches += nl; g_lz_flat_tracks += nt; }
+  if (kinds & RT_TRANSCODE) g_lz_transcode += nl;
+  return true;
+}
+// the RGBA stages of n programs of one shape into outp[i] (rowstride z0->rs): one fused launch where the shape allows, else stage by stage.  The routes, in order:
+//   1. lgpu_chain_yuv420p           YUV 4:2:0 planes, scaled
+//   2. lgpu_chain_flat_yuv422 / lgpu_chain_flat_yuv420p   YUV planes that keep their size, something behind the conversion, lives_gpu_set_flat_yuv(1)
+//   3. the conversion as a launch of its own (a YUV group that took neither), then
+//   4. lgpu_chain_amounts           every RGBA shape
+//   5. lazy_run_staged              track by track (more than 64 tracks, SEAM_STAGED, a shape lgpu_chain_amounts refuses)
 int lazy_run_rgba(Lazy *const *zs, int n, uint8_t *const *outp) {
   const Lazy *z0 = zs[0];
   const size_t bytes = (size_t)z0->rs * z0->h;
   int rc = LGPU_OK;
   for (int i = 0; i < n; i++) {
-    await(zs[i]->src, false);
-    if (zs[i]->yuv) { await(zs[i]->yu, false); await(zs[i]->yv, false); }
-    if (zs[i]->blend) await(zs[i]->l2, false);
+    lazy_await(zs[i]);
     if (z0->rs != z0->w * 4) rc = rc ? rc : lgpu_fill(outp[i], 0, bytes, S());      // the row padding of a fresh plane is zero (calloc in the eager path)
   }
   bool done = false;
   const bool staged = lgpu_tuning_get("SEAM_STAGED") > 0;
+  const bool one_launch = !staged && n <= LGPU_CHAIN_MAX_TRACKS;
   // the RGBA frames the later stages start from: the recorded source planes, or -- behind a YUV stage that is not fused -- converted scratch frames
   std::vector<const uint8_t *> srcp((size_t)n);
   for (int i = 0; i < n; i++) srcp[(size_t)i] = (const uint8_t *)zs[i]->src.d;
   int srow = z0->srs;
   void *scr = nullptr;
-  lgpu_chain_params pr;
-  memset(&pr, 0, sizeof pr);
-  pr.sw = z0->sw; pr.sh = z0->sh; pr.irow = z0->srs; pr.dw = z0->scale ? z0->dw : z0->sw; pr.dh = z0->scale ? z0->dh : z0->sh; pr.irow2 = z0->l2rs; pr.orow = z0->rs;
-  pr.swap_rb = z0->swap ? 1 : 0; pr.interp = (z0->scale ? z0->interp : 0) | LGPU_INTERP_PIXBUF | (z0->blend ? 0 : LGPU_INTERP_NOBLEND) | (z0->scale && z0->opaque ? LGPU_INTERP_OPAQUE : 0); pr.do_blur = 0; pr.bf = z0->bf; pr.use_lut = z0->lut ? 1 : 0;
-  if (!z0->blend) pr.irow2 = z0->rs;
-  if (z0->lut) memcpy(pr.lut8, z0->lut8, 256);
-  std::vector<uint8_t> amounts((size_t)n);
-  for (int i = 0; i < n; i++) amounts[(size_t)i] = (uint8_t)zs[i]->bf;
+  lgpu_chain_params pr = lazy_params(z0, false);
+  const std::vector<uint8_t> amounts = lazy_amounts(zs, n);
+  const uint8_t *const blend_amounts = z0->blend ? amounts.data() : nullptr;
   const lgpu_canvas cv = {z0->nw, z0->nh, z0->ox, z0->oy};
+  const lgpu_canvas *const cvp = z0->canvas ? &cv : nullptr;
   if (!rc && z0->yuv) {
     const int strides[3] = {z0->ystr[0], z0->ystr[1], z0->ystr[2]};
-    if (!staged && z0->scale && z0->yfmt == 4 && n <= LGPU_CHAIN_MAX_TRACKS) {
+    if (one_launch && z0->scale && z0->yfmt == 4) {
       // the one-launch form: the conversion rides in the chain's loads (lgpu_chain_yuv420p, 4:2:0 planes only); every other shape is refused there and takes the two launches below
-      lgpu_yuv_source ys;
-      memset(&ys, 0, sizeof ys);
-      ys.istrides[0] = strides[0]; ys.istrides[1] = strides[1]; ys.istrides[2] = strides[2]; ys.u_size = z0->usz; ys.v_size = z0->vsz;
-      ys.out_order = z0->order; ys.which_tables = z0->which; ys.pb_quality = z0->quality; ys.flags = 0;
-      std::vector<lgpu_chain_yuv_track> yt((size_t)n);
-      for (int i = 0; i < n; i++) {
-        yt[(size_t)i].y_d = (const uint8_t *)zs[i]->src.d; yt[(size_t)i].u_d = (const uint8_t *)zs[i]->yu.d; yt[(size_t)i].v_d = (const uint8_t *)zs[i]->yv.d;
-        yt[(size_t)i].layer2_d = (const uint8_t *)zs[i]->l2.d; yt[(size_t)i].dst_d = outp[i];
-      }
-      const int crc = lgpu_chain_yuv420p(&pr, &ys, z0->canvas ? &cv : nullptr, yt.data(), n, z0->blend ? amounts.data() : nullptr, S());
-      if (crc == LGPU_OK) { done = true; g_lz_chain_launches++; g_lz_chain_tracks += (unsigned long long)n; g_lz_yuv_launches++; g_lz_yuv_tracks += (unsigned long long)n; }
-      else if (crc != LGPU_E_BADARG && crc != LGPU_E_UNSUPPORTED) rc = crc;
+      const lgpu_yuv_source ys = lazy_source<lgpu_yuv_source>(z0);
+      const std::vector<lgpu_chain_yuv_track> yt = lazy_yuv_tracks(zs, n, outp);
+      done = lazy_route(lgpu_chain_yuv420p(&pr, &ys, cvp, yt.data(), n, blend_amounts, S()), RT_YUV, 1, n, &rc);
     }
     // lives_gpu_set_flat_yuv(1): a group that keeps its size (letterboxed or not) with anything behind the conversion takes lgpu_chain_flat_yuv420p, ONE launch and no
-    // converted frame; a conversion that is all there is stays with K2's own kernel below (the same bytes either way, and that kernel is the faster converter)
-    if (!rc && !done && !staged && !z0->scale && z0->yfmt != 4 && g_flat_yuv.load() && n <= LGPU_CHAIN_MAX_TRACKS && (z0->swap || z0->canvas || z0->blend || z0->lut)) {
-      // the same from YUV422P / UYVY / YUYV frames: lgpu_chain_flat_yuv422
-      lgpu_yuv422_source y4;
-      memset(&y4, 0, sizeof y4);
-      y4.in_fmt = z0->yfmt; y4.istrides[0] = strides[0]; y4.istrides[1] = strides[1]; y4.istrides[2] = strides[2]; y4.u_size = z0->usz; y4.v_size = z0->vsz;
-      y4.out_order = z0->order; y4.which_tables = z0->which; y4.pb_quality = z0->quality;
-      std::vector<lgpu_chain_yuv_sink_track> yt((size_t)n);
-      for (int i = 0; i < n; i++) {
-        memset(&yt[(size_t)i], 0, sizeof yt[0]);
-        yt[(size_t)i].y_d = (const uint8_t *)zs[i]->src.d; yt[(size_t)i].u_d = (const uint8_t *)zs[i]->yu.d; yt[(size_t)i].v_d = (const uint8_t *)zs[i]->yv.d;
-        yt[(size_t)i].layer2_d = (const uint8_t *)zs[i]->l2.d; yt[(size_t)i].dst_d[0] = outp[i];
+    // converted frame; a conversion that is all there is stays with K2's own kernel below (the same bytes either way, and that kernel is the faster converter).
+    // The same from YUV422P / UYVY / YUYV frames: lgpu_chain_flat_yuv422.  A refused shape takes the two launches below
+    if (!rc && !done && one_launch && !z0->scale && g_flat_yuv.load() && (z0->swap || z0->canvas || z0->blend || z0->lut)) {
+      if (z0->yfmt != 4) {
+        const lgpu_yuv422_source y4 = lazy_source<lgpu_yuv422_source>(z0);
+        const std::vector<lgpu_chain_yuv_sink_track> yt = lazy_yuv_sink_tracks(zs, n, outp, nullptr);
+        done = lazy_route(lgpu_chain_flat_yuv422(&pr, &y4, cvp, nullptr, yt.data(), n, blend_amounts, S()), RT_FLAT, 1, n, &rc);
+      } else {
+        const lgpu_yuv_source ys = lazy_source<lgpu_yuv_source>(z0);
+        const std::vector<lgpu_chain_yuv_track> yt = lazy_yuv_tracks(zs, n, outp);
+        done = lazy_route(lgpu_chain_flat_yuv420p(&pr, &ys, cvp, yt.data(), n, blend_amounts, S()), RT_FLAT, 1, n, &rc);
       }
-      const int crc = lgpu_chain_flat_yuv422(&pr, &y4, z0->canvas ? &cv : nullptr, nullptr, yt.data(), n, z0->blend ? amounts.data() : nullptr, S());
-      if (crc == LGPU_OK) { done = true; g_lz_chain_launches++; g_lz_chain_tracks += (unsigned long long)n; g_lz_flat_launches++; g_lz_flat_tracks += (unsigned long long)n; }
-      else if (crc != LGPU_E_BADARG && crc != LGPU_E_UNSUPPORTED) rc = crc;          // a refused shape takes the two launches below
-    }
-    if (!rc && !done && !staged && !z0->scale && z0->yfmt == 4 && g_flat_yuv.load() && n <= LGPU_CHAIN_MAX_TRACKS && (z0->swap || z0->canvas || z0->blend || z0->lut)) {
-      lgpu_yuv_source ys;
-      memset(&ys, 0, sizeof ys);
-      ys.istrides[0] = strides[0]; ys.istrides[1] = strides[1]; ys.istrides[2] = strides[2]; ys.u_size = z0->usz; ys.v_size = z0->vsz;
-      ys.out_order = z0->order; ys.which_tables = z0->which; ys.pb_quality = z0->quality; ys.flags = 0;
-      std::vector<lgpu_chain_yuv_track> yt((size_t)n);
-      for (int i = 0; i < n; i++) {
-        yt[(size_t)i].y_d = (const uint8_t *)zs[i]->src.d; yt[(size_t)i].u_d = (const uint8_t *)zs[i]->yu.d; yt[(size_t)i].v_d = (const uint8_t *)zs[i]->yv.d;
-        yt[(size_t)i].layer2_d = (const uint8_t *)zs[i]->l2.d; yt[(size_t)i].dst_d = outp[i];
-      }
-      const int crc = lgpu_chain_flat_yuv420p(&pr, &ys, z0->canvas ? &cv : nullptr, yt.data(), n, z0->blend ? amounts.data() : nullptr, S());
-      if (crc == LGPU_OK) { done = true; g_lz_chain_launches++; g_lz_chain_tracks += (unsigned long long)n; g_lz_flat_launches++; g_lz_flat_tracks += (unsigned long long)n; }
-      else if (crc != LGPU_E_BADARG && crc != LGPU_E_UNSUPPORTED) rc = crc;          // a refused shape takes today's two launches below
     }
     if (!rc && !done) {
       // two launches: the group's conversions in one batch (SEAM_STAGED: one call per track), then the RGBA program -- or straight into the planes when the
@@ -806,12 +885,9 @@ int lazy_run_rgba(Lazy *const *zs, int n, uint8_t *const *outp) {
     }
   }
   // every shape: with or without a resize stage, with or without a blend (lgpu_chain_amounts); LGPU_SEAM_STAGED / lgpu_tuning_set("SEAM_STAGED", 1): the fallback walk, for tests
-  if (!rc && !done && n <= LGPU_CHAIN_MAX_TRACKS && !staged) {
-    std::vector<lgpu_chain_track> tr((size_t)n);
-    for (int i = 0; i < n; i++) { tr[(size_t)i].src_d = srcp[(size_t)i]; tr[(size_t)i].layer2_d = (const uint8_t *)zs[i]->l2.d; tr[(size_t)i].dst_d = outp[i]; }
-    const int crc = lgpu_chain_amounts(&pr, z0->canvas ? &cv : nullptr, tr.data(), n, amounts.data(), S());
-    if (crc == LGPU_OK) { done = true; g_lz_chain_launches++; g_lz_chain_tracks += (unsigned long long)n; }
-    else if (crc != LGPU_E_BADARG && crc != LGPU_E_UNSUPPORTED) rc = crc;          // a shape the fused kernel does not take runs stage by stage below
+  if (!rc && !done && one_launch) {
+    const std::vector<lgpu_chain_track> tr = lazy_tracks(zs, n, srcp.data(), outp);
+    done = lazy_route(lgpu_chain_amounts(&pr, cvp, tr.data(), n, amounts.data(), S()), 0, 1, n, &rc);          // a shape the fused kernel does not take runs stage by stage below
   }
   if (!rc && !done)
     for (int i = 0; i < n && !rc; i++) { rc = lazy_run_staged(zs[i], outp[i], srcp[(size_t)i], srow); g_lz_staged++; }
@@ -864,17 +940,7 @@ int lazy_run_group(Lazy *const *zs, const void *const *hs, int n) {
       z->l2h = nullptr;
     }
     for (int p = 0; p < np; p++) { Dev &o = outs[(size_t)i * 3 + p]; if (o.d) { o.stream = S(); pool_give(o); o = Dev(); } }          // (the plane vanished meanwhile: cannot happen under the host's own ordering)
-    Dev src = z->src, yu = z->yu, yv = z->yv;
-    const bool yuv = z->yuv;
-    delete z;
-    if (yuv) {
-      // the three source planes go back with the streams that read them kept (a later taker waits for the writer AND these readers)
-      note_use(src, false); note_use(yu, false); note_use(yv, false);
-      pool_give(src); pool_give(yu); pool_give(yv);
-    } else {
-      src.stream = S(); src.nr = 0;                                                     // its last use is the launch just enqueued
-      pool_give(src);
-    }
+    lazy_free(z, true);
   }
   return LGPU_OK;
 }
@@ -900,109 +966,46 @@ int lazy_run_sink(Lazy *const *zs, int n, Dev (*souts)[3]) {
   // taken, and YUYV with it (the same instantiation); to YUV420P 258.9 us against 243.4 (spread 1.9 us) -- the 4:2:0 form's 98-105 registers hold it to four waves per
   // SIMD -- so 4:2:0 keeps today's two launches.
   const bool transcode_fused = z0->sfmt == 2 || z0->sfmt == 3;
-  if (transcode_fused && !staged && z0->yuv && z0->yfmt == 4 && z0->scale && !z0->canvas && z0->sww == z0->w && z0->shh == z0->h && n <= LGPU_CHAIN_MAX_TRACKS) {
-    // from YUV planes to YUV planes: ONE launch, neither RGBA frame exists.  The source planes are awaited as in lazy_run_rgba; lazy_run_group gives them back with
-    // their reader streams kept.
-    for (int i = 0; i < n; i++) { await(zs[i]->src, false); await(zs[i]->yu, false); await(zs[i]->yv, false); if (zs[i]->blend) await(zs[i]->l2, false); }
-    lgpu_chain_params pr;
-    memset(&pr, 0, sizeof pr);
-    pr.sw = z0->sw; pr.sh = z0->sh; pr.irow = z0->ystr[0]; pr.dw = z0->dw; pr.dh = z0->dh; pr.irow2 = z0->blend ? z0->l2rs : 0; pr.orow = 0;
-    pr.swap_rb = z0->swap ? 1 : 0; pr.interp = z0->interp | LGPU_INTERP_PIXBUF | (z0->blend ? 0 : LGPU_INTERP_NOBLEND); pr.use_lut = z0->lut ? 1 : 0;
-    if (z0->lut) memcpy(pr.lut8, z0->lut8, 256);
-    lgpu_yuv_source ys;
-    memset(&ys, 0, sizeof ys);
-    ys.istrides[0] = z0->ystr[0]; ys.istrides[1] = z0->ystr[1]; ys.istrides[2] = z0->ystr[2]; ys.u_size = z0->usz; ys.v_size = z0->vsz;
-    ys.out_order = z0->order; ys.which_tables = z0->which; ys.pb_quality = z0->quality; ys.flags = 0;
-    lgpu_chain_sink sk;
-    memset(&sk, 0, sizeof sk);
-    sk.out_fmt = z0->sfmt; sk.which_tables = z0->swhich; sk.in_order = z0->sorder;
-    for (int p = 0; p < z0->snp; p++) sk.orow[p] = z0->sors[p];
-    std::vector<lgpu_chain_yuv_sink_track> tr((size_t)n);
-    std::vector<uint8_t> amounts((size_t)n);
-    for (int i = 0; i < n; i++) {
-      memset(&tr[(size_t)i], 0, sizeof tr[0]);
-      tr[(size_t)i].y_d = (const uint8_t *)zs[i]->src.d; tr[(size_t)i].u_d = (const uint8_t *)zs[i]->yu.d; tr[(size_t)i].v_d = (const uint8_t *)zs[i]->yv.d;
-      tr[(size_t)i].layer2_d = (const uint8_t *)zs[i]->l2.d;
-      for (int p = 0; p < z0->snp; p++) tr[(size_t)i].dst_d[p] = (uint8_t *)souts[i][p].d;
-      amounts[(size_t)i] = (uint8_t)zs[i]->bf;
-    }
-    const int crc = lgpu_chain_yuv420p_to_yuv(&pr, &ys, &sk, tr.data(), n, z0->blend ? amounts.data() : nullptr, S());
-    if (crc == LGPU_OK) {
-      const unsigned long long nl = (unsigned long long)((n + LGPU_CHAIN_TRANSCODE_TRACKS - 1) / LGPU_CHAIN_TRANSCODE_TRACKS);      // the call's launches
-      g_lz_chain_launches += nl; g_lz_chain_tracks += (unsigned long long)n; g_lz_yuv_launches += nl; g_lz_yuv_tracks += (unsigned long long)n;
-      g_lz_sink_launches += nl; g_lz_sink_tracks += (unsigned long long)n; g_lz_sink_fused += nl; g_lz_transcode += nl;
-      return LGPU_OK;
-    }
-    if (crc != LGPU_E_BADARG && crc != LGPU_E_UNSUPPORTED) return crc;            // a shape outside the one-launch form takes today's launches below
-  }
   // lives_gpu_set_flat_yuv(1): an UNSCALED group from YUV planes to a YUV sink as ONE lgpu_chain_flat_yuv420p_to_yuv launch, for the sink formats FLAT_SINK_FORMATS
   // names: those for which tools/bench_flat_chain.py shows the launch ahead of today's three (lgpu_yuv420p_to_rgb_batch, lgpu_chain_amounts, lgpu_rgb_to_yuv_batch) by
   // more than the round-to-round spread of the latter.  profiles/r11/flat_chain.md (16 x 1080p, blend + LUT, five interleaved rounds): to UYVY 157.2 us against 274.2
   // (spread 0.4 us), YUYV with it (the same instantiation); to YUV420P 159.7 us against 271.7 (spread 0.7 us) -- all taken.  (RGBA, lazy_run_rgba: 158.0 against 227.3.)
   const bool flat_sink = FLAT_SINK_FORMATS(z0->sfmt);
-  if (flat_sink && g_flat_yuv.load() && !staged && z0->yuv && !z0->scale && !z0->canvas && z0->sww == z0->w && z0->shh == z0->h && n <= LGPU_CHAIN_MAX_TRACKS) {
-    for (int i = 0; i < n; i++) { await(zs[i]->src, false); await(zs[i]->yu, false); await(zs[i]->yv, false); if (zs[i]->blend) await(zs[i]->l2, false); }
-    lgpu_chain_params pr;
-    memset(&pr, 0, sizeof pr);
-    pr.sw = z0->sw; pr.sh = z0->sh; pr.irow = z0->ystr[0]; pr.dw = z0->sw; pr.dh = z0->sh; pr.irow2 = z0->blend ? z0->l2rs : 0; pr.orow = 0;
-    pr.swap_rb = z0->swap ? 1 : 0; pr.interp = LGPU_INTERP_PIXBUF | (z0->blend ? 0 : LGPU_INTERP_NOBLEND); pr.use_lut = z0->lut ? 1 : 0;
-    if (z0->lut) memcpy(pr.lut8, z0->lut8, 256);
-    lgpu_yuv_source ys;
-    memset(&ys, 0, sizeof ys);
-    ys.istrides[0] = z0->ystr[0]; ys.istrides[1] = z0->ystr[1]; ys.istrides[2] = z0->ystr[2]; ys.u_size = z0->usz; ys.v_size = z0->vsz;
-    ys.out_order = z0->order; ys.which_tables = z0->which; ys.pb_quality = z0->quality; ys.flags = 0;
-    lgpu_yuv422_source y4;                    // the same description for a YUV422P / UYVY / YUYV group (lgpu_chain_flat_yuv422)
-    memset(&y4, 0, sizeof y4);
-    y4.in_fmt = z0->yfmt; y4.istrides[0] = z0->ystr[0]; y4.istrides[1] = z0->ystr[1]; y4.istrides[2] = z0->ystr[2]; y4.u_size = z0->usz; y4.v_size = z0->vsz;
-    y4.out_order = z0->order; y4.which_tables = z0->which; y4.pb_quality = z0->quality;
-    lgpu_chain_sink sk;
-    memset(&sk, 0, sizeof sk);
-    sk.out_fmt = z0->sfmt; sk.which_tables = z0->swhich; sk.in_order = z0->sorder;
-    for (int p = 0; p < z0->snp; p++) sk.orow[p] = z0->sors[p];
-    std::vector<lgpu_chain_yuv_sink_track> tr((size_t)n);
-    std::vector<uint8_t> amounts((size_t)n);
-    for (int i = 0; i < n; i++) {
-      memset(&tr[(size_t)i], 0, sizeof tr[0]);
-      tr[(size_t)i].y_d = (const uint8_t *)zs[i]->src.d; tr[(size_t)i].u_d = (const uint8_t *)zs[i]->yu.d; tr[(size_t)i].v_d = (const uint8_t *)zs[i]->yv.d;
-      tr[(size_t)i].layer2_d = (const uint8_t *)zs[i]->l2.d;
-      for (int p = 0; p < z0->snp; p++) tr[(size_t)i].dst_d[p] = (uint8_t *)souts[i][p].d;
-      amounts[(size_t)i] = (uint8_t)zs[i]->bf;
+  // The one-launch routes: the sink takes the whole frame the chain ends at, and at most one of them has the group's shape.
+  //   lgpu_chain_yuv420p_to_yuv                                  4:2:0 planes, scaled, to the formats of transcode_fused
+  //   lgpu_chain_flat_yuv420p_to_yuv / lgpu_chain_flat_yuv422    YUV planes that keep their size, to the formats of flat_sink
+  //   lgpu_chain_to_yuv                                          an RGBA frame, scaled
+  // A shape that the route's entry point refuses takes today's launches below.
+  const bool one_launch = !staged && !z0->canvas && z0->sww == z0->w && z0->shh == z0->h && n <= LGPU_CHAIN_MAX_TRACKS;
+  const bool via_transcode = one_launch && transcode_fused && z0->yuv && z0->yfmt == 4 && z0->scale;
+  const bool via_flat = one_launch && flat_sink && g_flat_yuv.load() && z0->yuv && !z0->scale;
+  const bool via_to_yuv = one_launch && z0->scale && !z0->yuv;
+  if (via_transcode || via_flat || via_to_yuv) {
+    // (the source planes are awaited as in lazy_run_rgba; lazy_run_group gives them back with their reader streams kept)
+    for (int i = 0; i < n; i++) lazy_await(zs[i]);
+    const lgpu_chain_params pr = lazy_params(z0, true);
+    const lgpu_chain_sink sk = lazy_sink(z0);
+    const std::vector<uint8_t> amounts = lazy_amounts(zs, n);
+    const uint8_t *const blend_amounts = z0->blend ? amounts.data() : nullptr;
+    bool done;
+    if (via_to_yuv) {
+      const std::vector<lgpu_chain_sink_track> tr = lazy_sink_tracks(zs, n, souts);
+      done = lazy_route(lgpu_chain_to_yuv(&pr, &sk, tr.data(), n, blend_amounts, S()), RT_SINK, 1, n, &rc);
+    } else {
+      // from YUV planes to YUV planes: neither RGBA frame exists
+      const lgpu_yuv_source ys = lazy_source<lgpu_yuv_source>(z0);
+      const std::vector<lgpu_chain_yuv_sink_track> tr = lazy_yuv_sink_tracks(zs, n, nullptr, souts);
+      if (via_transcode)           // the call's launches: LGPU_CHAIN_TRANSCODE_TRACKS tracks each
+        done = lazy_route(lgpu_chain_yuv420p_to_yuv(&pr, &ys, &sk, tr.data(), n, blend_amounts, S()), RT_YUV | RT_SINK | RT_TRANSCODE,
+                          (n + LGPU_CHAIN_TRANSCODE_TRACKS - 1) / LGPU_CHAIN_TRANSCODE_TRACKS, n, &rc);
+      else if (z0->yfmt == 4)      // the call's launches: 32 tracks each to YUV420P
+        done = lazy_route(lgpu_chain_flat_yuv420p_to_yuv(&pr, &ys, &sk, tr.data(), n, blend_amounts, S()), RT_SINK | RT_FLAT, z0->sfmt == 4 ? (n + 31) / 32 : 1, n, &rc);
+      else {
+        const lgpu_yuv422_source y4 = lazy_source<lgpu_yuv422_source>(z0);
+        done = lazy_route(lgpu_chain_flat_yuv422(&pr, &y4, nullptr, &sk, tr.data(), n, blend_amounts, S()), RT_SINK | RT_FLAT, z0->sfmt == 4 ? (n + 31) / 32 : 1, n, &rc);
+      }
     }
-    const int crc = z0->yfmt == 4 ? lgpu_chain_flat_yuv420p_to_yuv(&pr, &ys, &sk, tr.data(), n, z0->blend ? amounts.data() : nullptr, S())
-                                  : lgpu_chain_flat_yuv422(&pr, &y4, nullptr, &sk, tr.data(), n, z0->blend ? amounts.data() : nullptr, S());
-    if (crc == LGPU_OK) {
-      const unsigned long long nl = z0->sfmt == 4 ? (unsigned long long)((n + 31) / 32) : 1ull;      // the call's launches: 32 tracks each to YUV420P
-      g_lz_chain_launches += nl; g_lz_chain_tracks += (unsigned long long)n; g_lz_sink_launches += nl; g_lz_sink_tracks += (unsigned long long)n; g_lz_sink_fused += nl;
-      g_lz_flat_launches += nl; g_lz_flat_tracks += (unsigned long long)n;
-      return LGPU_OK;
-    }
-    if (crc != LGPU_E_BADARG && crc != LGPU_E_UNSUPPORTED) return crc;            // a refused shape takes today's launches below
-  }
-  if (!staged && z0->scale && !z0->canvas && !z0->yuv && z0->sww == z0->w && z0->shh == z0->h && n <= LGPU_CHAIN_MAX_TRACKS) {
-    for (int i = 0; i < n; i++) { await(zs[i]->src, false); if (zs[i]->blend) await(zs[i]->l2, false); }
-    lgpu_chain_params pr;
-    memset(&pr, 0, sizeof pr);
-    pr.sw = z0->sw; pr.sh = z0->sh; pr.irow = z0->srs; pr.dw = z0->dw; pr.dh = z0->dh; pr.irow2 = z0->blend ? z0->l2rs : 0; pr.orow = 0;
-    pr.swap_rb = z0->swap ? 1 : 0; pr.interp = z0->interp | LGPU_INTERP_PIXBUF | (z0->blend ? 0 : LGPU_INTERP_NOBLEND); pr.use_lut = z0->lut ? 1 : 0;
-    if (z0->lut) memcpy(pr.lut8, z0->lut8, 256);
-    lgpu_chain_sink sk;
-    memset(&sk, 0, sizeof sk);
-    sk.out_fmt = z0->sfmt; sk.which_tables = z0->swhich; sk.in_order = z0->sorder;
-    for (int p = 0; p < z0->snp; p++) sk.orow[p] = z0->sors[p];
-    std::vector<lgpu_chain_sink_track> tr((size_t)n);
-    std::vector<uint8_t> amounts((size_t)n);
-    for (int i = 0; i < n; i++) {
-      memset(&tr[(size_t)i], 0, sizeof tr[0]);
-      tr[(size_t)i].src_d = (const uint8_t *)zs[i]->src.d; tr[(size_t)i].layer2_d = (const uint8_t *)zs[i]->l2.d;
-      for (int p = 0; p < z0->snp; p++) tr[(size_t)i].dst_d[p] = (uint8_t *)souts[i][p].d;
-      amounts[(size_t)i] = (uint8_t)zs[i]->bf;
-    }
-    const int crc = lgpu_chain_to_yuv(&pr, &sk, tr.data(), n, z0->blend ? amounts.data() : nullptr, S());
-    if (crc == LGPU_OK) {
-      g_lz_chain_launches++; g_lz_chain_tracks += (unsigned long long)n; g_lz_sink_launches++; g_lz_sink_tracks += (unsigned long long)n; g_lz_sink_fused++;
-      return LGPU_OK;
-    }
-    if (crc != LGPU_E_BADARG && crc != LGPU_E_UNSUPPORTED) return crc;            // a shape outside the one-launch form takes the two launches below
+    if (done || rc) return rc;
   }
   // the RGBA frames the conversion reads: the programs' results in scratch, or -- a program of the sink stage alone -- the resident frames themselves
   std::vector<const uint8_t *> rgba((size_t)n);
@@ -1016,7 +1019,7 @@ int lazy_run_sink(Lazy *const *zs, int n, Dev (*souts)[3]) {
     rc = lazy_run_rgba(zs, n, outp.data());
     rrow = z0->rs;
   } else
-    for (int i = 0; i < n; i++) { await(zs[i]->src, false); rgba[(size_t)i] = (const uint8_t *)zs[i]->src.d; }
+    for (int i = 0; i < n; i++) { lazy_await(zs[i]); rgba[(size_t)i] = (const uint8_t *)zs[i]->src.d; }
   int ors[4] = {z0->sors[0], z0->sors[1], z0->sors[2], 0};
   for (int i0 = 0; i0 < n && !rc; i0 += (staged ? 1 : LGPU_FX_MAX_FRAMES)) {
     const int m = staged ? 1 : std::min(n - i0, (int)LGPU_FX_MAX_FRAMES);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <initializer_list>
 #include "../../include/lives_gpu.h"
 
 namespace lgpu {
@@ -92,6 +93,24 @@ int tune(Tune t);                                  // the value, or -1 when the 
 static inline bool tune_on(Tune t) { return tune(t) > 0; }
 
 static inline unsigned cdiv(unsigned a, unsigned b) { return (a + b - 1) / b; }
+
+// ---- argument checks of the tick's one-launch forms (pixbuf.hip, flat.hip) ------------------------------
+// What lgpu_chain_yuv420p, lgpu_chain_to_yuv, lgpu_chain_yuv420p_to_yuv and the lgpu_chain_flat_* forms say about a decoded YUV source, a YUV sink, an RGBA
+// destination and a track's pointers is said ONCE, here (defined in pixbuf.hip beside get_sink_tables).  fn: the entry point's name, for set_error.  Each returns
+// LGPU_OK or LGPU_E_BADARG, launches and allocates nothing, and is called before the entry point's own LGPU_E_UNSUPPORTED refusals.
+// A decoded source of pr->sw x pr->sh: sfmt 4 planar 4:2:0, 5 planar 4:2:2, 2 UYVY, 3 YUYV (a packed frame: istrides[0] alone is read)
+int check_yuv_source(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv_source *s, int sfmt);
+// A YUV sink of pr->dw x pr->dh.  chain_order: the byte order of the chain's result where the source states it (src->out_order ^ params->swap_rb), which
+// sink->in_order must repeat; -1 behind an RGBA source, whose order is the caller's word.  l2rgba: layer 2 is an RGBA frame of rowstride pr->irow2
+int check_yuv_sink(const char *fn, const lgpu_chain_params *pr, const lgpu_chain_sink *sk, int chain_order, bool l2rgba);
+// An RGBA destination of rowstride pr->orow: the pr->dw x pr->dh frame itself, or the canvas it is letterboxed onto (cv may be null)
+int check_rgba_dest(const char *fn, const lgpu_chain_params *pr, const lgpu_canvas *cv, bool l2rgba);
+// One track.  src: its source planes, the first nsrc of them required (the others may be null); rgba_src: src[0] is an RGBA frame.  l2: the RGBA layer 2 where one
+// is read (l2rgba).  dst: ndst destination planes, none of them a source plane; rgba_dst: dst[0] is an RGBA frame
+int check_track(const char *fn, const uint8_t *const src[3], int nsrc, bool rgba_src, const uint8_t *l2, bool l2rgba, uint8_t *const *dst, int ndst, bool rgba_dst);
+// The kernels address a plane through 32-bit offsets: LGPU_E_UNSUPPORTED when one of `bytes` (rows x rowstride, or a plane's size) is 2 GiB or more.  instead: what
+// to run then, for the message
+int check_plane_sizes(const char *fn, std::initializer_list<long long> bytes, const char *instead = nullptr);
 
 #if defined(__HIPCC__)
 // ---- device helpers ---------------------------------------------------------------------------------

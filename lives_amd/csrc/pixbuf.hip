@@ -2154,6 +2154,52 @@ static void pb_half_geometry(PbHalfArgs *a, int ntracks, int blur = 0, int opaqu
 
 static unsigned pb_half_grid(const PbHalfArgs &a) { return a.row_major == 2 ? 8u * (unsigned)(a.cgroups * a.ntracks * a.bgroup) * cdiv(cdiv((unsigned)a.bands, (unsigned)a.bgroup), 8u) : 8u * cdiv((unsigned)(a.cgroups * a.bands * a.ntracks), 8u); }
 
+// What every launch of k_pb_half sets up once pb_half_geometry has cut the frame into strips and bands: the work order, the canvas and its bar blocks, the grid.
+// sink420: the 4:2:0 sink's band boundaries lie at odd rows -- the (dh - 2) / 2 inner row pairs are dealt to the bands, row 0 goes with the first band and row
+// dh - 1 with the last (k_pb_half's comment); a.th / a.rem are then not what the kernel walks: only a.bands counts, the rows of a band come from PbSinkDst.pairs,
+// which is what this returns (0 without that sink).
+// order / group: a caller's own choice (pb_chain_half's PBH_ORDER / PBH_GROUP), else decided here from the geometry.  Order: a launch that fits one generation of
+// workgroups (one or two 4K tracks) is a matter of latency, not of streaming order: order 1 there (graph replay, one frame 12.09 us against 12.45 with order 2 and
+// 12.24 with order 0; config 3 12.19 / 12.62 / 12.33; two tracks 20.0 / 21.05 / 20.5); `full` workgroups or more: order 2.  Group: an eighth of the track's bands per
+// XCD when the band count is a multiple of 8 (pb_half_geometry makes it one for full-device launches), else band by band -- what matters is that every XCD gets the
+// SAME number of bands of a track (profiles/r04/group_ab.txt: 216 bands in groups of 1 / 3 / 9 / 27 -- 27 / 9 / 3 / 1 turns per XCD -- 138.2-140.3 us; groups of
+// 2 / 4 / 5 / 13 / 25, which leave some XCDs a turn short, 143 / 143 / 152 / 166 / 194); among the balanced ones the largest group re-reads least: L2 -> fabric reads
+// 769.5 / 698.8 / 675.2 / 667.3 MB per launch against 663.6 MB of source + layer 2.
+static int pb_half_shape(PbHalfArgs *a, int ntracks, const lgpu_canvas *cv, bool sink420, int order = -1, int group = 0, long long full = (long long)device_cus() * 8 + 1) {
+  int pairs = 0;
+  if (sink420) {
+    pairs = (a->dh - 2) / 2;
+    pb_half_bands(a, std::min(a->bands, std::max(1, pairs)));
+  }
+  a->row_major = order >= 0 ? order : ((long long)a->cgroups * a->bands * ntracks >= full) ? 2 : 1;
+  a->bgroup = group > 0 ? group : (a->bands % 8 == 0) ? a->bands / 8 : 1;
+  a->cw = a->ch = a->ox = a->oy = 0; a->bar_blocks = 0;
+  if (cv) { a->cw = cv->nwidth; a->ch = cv->nheight; a->ox = cv->offs_x; a->oy = cv->offs_y; a->bar_blocks = (int)cdiv((unsigned)(a->cw * a->ch - a->dw * a->dh), 1024u); }
+  a->main_blocks = (int)pb_half_grid(*a);
+  a->bar_first = (a->bar_blocks * ntracks + 7) & ~7;
+  return pairs;
+}
+// Workgroups per CU (PBH_OCC): a launch of more than one generation runs FIVE workgroups per CU instead of the eight its registers allow -- unused dynamic LDS is what
+// holds the others back.  Fewer bands in flight = a narrower window of the frames being streamed at any moment (profiles/r04/occupancy_sweep.txt: 8 / 7 / 6 / 5 / 4 / 3
+// per CU 142.3 / 142.2 / 141.4 / 139.2 / 142.3 / 180 us per 16-track launch, 8 tracks 74.1 -> 72.8; with the gaussian 184 -> 187, so that chain keeps its six).
+// Returns the dynamic LDS to ask for.  capped: the launch takes the five at all; static_lds: what the instantiation holds already, so that the count stays what it was
+static size_t pb_half_occ_lds(const PbHalfArgs &a, int ntracks, bool capped, size_t static_lds) {
+  int occ = (capped && (long long)a.cgroups * a.bands * ntracks > (long long)device_cus() * 8) ? 5 : 0;
+  if (tune(TUNE_PBH_OCC) >= 0) occ = tune(TUNE_PBH_OCC);
+  const size_t per_wg = occ > 0 && occ < 16 ? (size_t)(160 * 1024) / (size_t)occ : 0;
+  return per_wg > static_lds ? per_wg - static_lds : 0;
+}
+// a decoded 4:2:0 source / a YUV sink as the kernel takes them (the per-track plane pointers are the caller's)
+template <int NT> static void pb_fill_yuv_src(PbYuvSrcT<NT> *Y, const lgpu_yuv_source *ys) {
+  Y->tables = device_tables()->yuv2rgb[ys->which_tables & 3];
+  Y->us = ys->istrides[1]; Y->vs = ys->istrides[2]; Y->usize = (uint32_t)ys->u_size; Y->vsize = (uint32_t)ys->v_size;
+  Y->clamped = !(ys->which_tables & 1); Y->lowq = ys->pb_quality == 1; Y->fix_edges = (ys->flags & LGPU_YUV_FIX_EDGES) ? 1 : 0;
+}
+template <int NT> static void pb_fill_sink(PbSinkDstT<NT> *S, const lgpu_chain_sink *sk) {
+  const bool planar = sk->out_fmt >= 4;
+  S->urow = planar ? sk->orow[1] : 0; S->vrow = planar ? sk->orow[2] : 0; S->fmt = sk->out_fmt; S->unclamped = sk->which_tables & 1;
+}
+
 // the fused chain on the pixbuf arithmetic (lgpu_chain with LGPU_INTERP_PIXBUF): convert -> gdk-pixbuf 2:1 scale -> chroma blend -> gamma LUT in one launch.
 // LGPU_E_UNSUPPORTED when the geometry is not the exact aligned 2:1 case (the caller then runs the stages one by one).
 int pb_chain_half(const lgpu_chain_params *pr, const lgpu_canvas *cv, const lgpu_chain_track *tracks, int ntracks, hipStream_t st, const uint8_t *amounts = nullptr) {
@@ -2184,33 +2230,18 @@ int pb_chain_half(const lgpu_chain_params *pr, const lgpu_canvas *cv, const lgpu
   // 1: the column groups of a band one after the other -- consecutive workgroups read a band across the whole row: 16 tracks 147.5 -> 142.3 us on one box, 152 -> 146 on another;
   // 2: that, with the bands of a track dealt round robin to the XCDs, so that the whole device sweeps ONE frame at a time like a linear stream does: 151-152 -> 144.2, 8 tracks
   // 76.8 -> 74.3.  With the 5x5 gaussian in the chain neighbouring bands share ten source rows instead of two and want the same L2: 186 us with 1, 189 with 2 -- it keeps 1.
-  a.row_major = tune(TUNE_PBH_ORDER) >= 0 && tune(TUNE_PBH_ORDER) <= 2 ? tune(TUNE_PBH_ORDER) : -1;       // -1: decided below, once the geometry is known
-  // ... in groups of `bgroup` neighbouring bands per XCD turn.  What matters is that every XCD gets the SAME number of bands of a track (profiles/r04/group_ab.txt: 216 bands
-  // in groups of 1 / 3 / 9 / 27 -- 27 / 9 / 3 / 1 turns per XCD -- 138.2-140.3 us; groups of 2 / 4 / 5 / 13 / 25, which leave some XCDs a turn short, 143 / 143 / 152 / 166 / 194);
-  // among the balanced ones the largest group re-reads least: L2 -> fabric reads 769.5 / 698.8 / 675.2 / 667.3 MB per launch against 663.6 MB of source + layer 2.
-  // So: an eighth of the track's bands per XCD when the band count is a multiple of 8 (pb_half_geometry makes it one for full-device launches), else band by band.
-  a.bgroup = tune(TUNE_PBH_GROUP) >= 1 && tune(TUNE_PBH_GROUP) <= 4096 ? tune(TUNE_PBH_GROUP) : 0;
+  const int order = tune(TUNE_PBH_ORDER) >= 0 && tune(TUNE_PBH_ORDER) <= 2 ? tune(TUNE_PBH_ORDER) : -1;       // -1: pb_half_shape decides, once the geometry is known
+  // ... in groups of `bgroup` neighbouring bands per XCD turn (PBH_GROUP; pb_half_shape's default and its measurements)
+  const int group = tune(TUNE_PBH_GROUP) >= 1 && tune(TUNE_PBH_GROUP) <= 4096 ? tune(TUNE_PBH_GROUP) : 0;
   pb_half_geometry(&a, ntracks, pr->do_blur ? 1 : 0, (pr->do_blur && (pr->interp & LGPU_INTERP_OPAQUE)) ? 1 : 0);
-  // a launch that fits one generation of workgroups (one or two 4K tracks) is a matter of latency, not of streaming order: order 1 there (graph replay, one frame 12.09 us
-  // against 12.45 with order 2 and 12.24 with order 0; config 3 12.19 / 12.62 / 12.33; two tracks 20.0 / 21.05 / 20.5)
   // With the gaussian (four resident workgroups per CU, one per CU and track): order 2 from a whole generation on -- 4 tracks 42.3 -> 41.9 us, 8 88.7 -> 86.9, 16 166.5 -> 164.5;
   // one and two tracks keep order 1 (16.9 / 26.4 against 17.1 / 27.2).  Round 4's kernel, with its taller bands, had it the other way round.
-  if (a.row_major < 0) a.row_major = ((long long)a.cgroups * a.bands * ntracks >= (long long)device_cus() * (pr->do_blur ? 4 : 8) + (pr->do_blur ? 0 : 1)) ? 2 : 1;
-  if (a.bgroup <= 0) a.bgroup = (a.bands % 8 == 0) ? a.bands / 8 : 1;
-  a.cw = a.ch = a.ox = a.oy = 0; a.bar_blocks = 0;
-  if (cv) { a.cw = cv->nwidth; a.ch = cv->nheight; a.ox = cv->offs_x; a.oy = cv->offs_y; a.bar_blocks = (int)cdiv((unsigned)(a.cw * a.ch - a.dw * a.dh), 1024u); }
-  a.main_blocks = (int)pb_half_grid(a);
-  a.bar_first = (a.bar_blocks * ntracks + 7) & ~7;
+  pb_half_shape(&a, ntracks, cv, false, order, group, (long long)device_cus() * (pr->do_blur ? 4 : 8) + (pr->do_blur ? 0 : 1));
   PbTracks T;
   for (int i = 0; i < ntracks; i++) { T.src[i] = tracks[i].src_d; T.l2[i] = tracks[i].layer2_d; T.dst[i] = tracks[i].dst_d; T.bf[i] = amounts ? amounts[i] : 0; }
   const Lut8 l = pack_lut(pr->use_lut ? pr->lut8 : nullptr);
   const dim3 grid((unsigned)(a.main_blocks + a.bar_first));
-  // Workgroups per CU (PBH_OCC): a launch of more than one generation runs FIVE workgroups per CU instead of the eight its registers allow -- unused dynamic LDS is what
-  // holds the others back.  Fewer bands in flight = a narrower window of the frames being streamed at any moment (profiles/r04/occupancy_sweep.txt: 8 / 7 / 6 / 5 / 4 / 3
-  // per CU 142.3 / 142.2 / 141.4 / 139.2 / 142.3 / 180 us per 16-track launch, 8 tracks 74.1 -> 72.8; with the gaussian 184 -> 187, so that chain keeps its six).
-  int occ = (!pr->do_blur && (long long)a.cgroups * a.bands * ntracks > (long long)device_cus() * 8) ? 5 : 0;
-  if (tune(TUNE_PBH_OCC) >= 0) occ = tune(TUNE_PBH_OCC);
-  const size_t occ_lds = occ > 0 && occ < 16 ? (size_t)(160 * 1024) / (size_t)occ - 3072 : 0;
+  const size_t occ_lds = pb_half_occ_lds(a, ntracks, !pr->do_blur, 3072);      // (the gaussian chain keeps its six workgroups per CU)
   const bool noblend = (pr->interp & LGPU_INTERP_NOBLEND) != 0;        // (never with the gaussian: pb_chain keeps that pair staged)
 #define PBH_LAUNCH(HY, BL, AL, SW) { if (noblend && !(BL)) hipLaunchKernelGGL((k_pb_half<(BL) ? 1 : 2, HY, BL, AL, SW>), grid, dim3(256), occ_lds, st, a, T, l); \
                                      else hipLaunchKernelGGL((k_pb_half<1, HY, BL, AL, SW>), grid, dim3(256), occ_lds, st, a, T, l); }
@@ -2693,26 +2724,14 @@ extern "C" int lgpu_chain_yuv420p(const lgpu_chain_params *pr, const lgpu_yuv_so
   LGPU_REQUIRE(pr->interp & LGPU_INTERP_PIXBUF, "lgpu_chain_yuv420p serves the gdk-pixbuf arithmetic (LGPU_INTERP_PIXBUF)");
   const bool noblend = (pr->interp & LGPU_INTERP_NOBLEND) != 0;
   LGPU_REQUIRE(amounts || noblend, "null amounts");
-  LGPU_REQUIRE(pr->sw >= 2 && !(pr->sw & 1) && pr->sh >= 1 && pr->dw > 0 && pr->dh > 0, "empty geometry or an odd 4:2:0 width");
-  LGPU_REQUIRE(ys->out_order == 0 || ys->out_order == 1, "out_order is 0 (RGBA) or 1 (BGRA)");
-  LGPU_REQUIRE(ys->which_tables >= 0 && ys->which_tables <= 3, "which_tables is 0..3");
-  LGPU_REQUIRE(ys->pb_quality >= 1 && ys->pb_quality <= 3, "pb_quality is 1 (LOW), 2 (MED) or 3 (HIGH)");
-  LGPU_REQUIRE(!(ys->flags & ~LGPU_YUV_FIX_EDGES), "unknown flags");
-  const int hw = pr->sw >> 1, hh = (pr->sh + 1) >> 1, lys = ys->istrides[0], us = ys->istrides[1], vs = ys->istrides[2];
-  LGPU_REQUIRE(lys >= pr->sw && us >= hw && vs >= hw, "plane rowstride smaller than a row");
-  LGPU_REQUIRE(ys->u_size >= (long)(hh - 1) * us + hw && ys->v_size >= (long)(hh - 1) * vs + hw, "chroma plane smaller than its (sw / 2) x (sh / 2) samples");
-  const int cw = cv ? cv->nwidth : pr->dw, ch = cv ? cv->nheight : pr->dh;
-  if (cv)
-    LGPU_REQUIRE(cv->nwidth >= pr->dw && cv->nheight >= pr->dh && cv->offs_x >= 0 && cv->offs_y >= 0 && cv->offs_x + pr->dw <= cv->nwidth &&
-                 cv->offs_y + pr->dh <= cv->nheight, "the scaled frame must lie inside the canvas");
-  LGPU_REQUIRE(pr->orow >= cw * 4 && (noblend || pr->irow2 >= cw * 4), "rowstride smaller than a row");
-  LGPU_REQUIRE(((pr->orow | (noblend ? 0 : pr->irow2)) & 3) == 0, "rowstrides must be multiples of 4");
+  static const char fn[] = "lgpu_chain_yuv420p";
+  if ((rc = check_yuv_source(fn, pr, ys, 4)) || (rc = check_rgba_dest(fn, pr, cv, !noblend))) return rc;
+  const int ch = cv ? cv->nheight : pr->dh, lys = ys->istrides[0];
   uintptr_t db = (uintptr_t)pr->orow | (uintptr_t)(noblend ? 0 : pr->irow2);
   for (int i = 0; i < ntracks; i++) {
     const lgpu_chain_yuv_track &t = tracks[i];
-    LGPU_REQUIRE(t.y_d && t.u_d && t.v_d && t.dst_d && (noblend || t.layer2_d), "null track pointer");
-    LGPU_REQUIRE((((uintptr_t)t.dst_d | (uintptr_t)(noblend ? nullptr : t.layer2_d)) & 3) == 0, "destination and layer 2 must be 4-byte aligned");
-    LGPU_REQUIRE((const uint8_t *)t.dst_d != t.y_d && (const uint8_t *)t.dst_d != t.u_d && (const uint8_t *)t.dst_d != t.v_d, "the chain cannot run in place");
+    const uint8_t *const planes[3] = {t.y_d, t.u_d, t.v_d};
+    if ((rc = check_track(fn, planes, 3, false, t.layer2_d, !noblend, &t.dst_d, 1, true))) return rc;
     db |= (uintptr_t)t.dst_d | (uintptr_t)(noblend ? nullptr : t.layer2_d);
   }
   // the one-launch form; anything else is refused, never run some other way
@@ -2722,11 +2741,7 @@ extern "C" int lgpu_chain_yuv420p(const lgpu_chain_params *pr, const lgpu_yuv_so
     set_error("lgpu_chain_yuv420p: one launch serves the exact 2:1 reduction (HYPER / BILINEAR, sw %% 4 == 0, sh even, even canvas offs_x, 8-byte aligned destination)");
     return LGPU_E_UNSUPPORTED;
   }
-  const long long lim = 1ll << 31;
-  if ((long long)pr->sh * lys >= lim || ys->u_size >= lim || ys->v_size >= lim || (long long)ch * pr->orow >= lim || (!noblend && (long long)ch * pr->irow2 >= lim)) {
-    set_error("lgpu_chain_yuv420p: planes of 2 GiB or more");
-    return LGPU_E_UNSUPPORTED;
-  }
+  if ((rc = check_plane_sizes(fn, {(long long)pr->sh * lys, ys->u_size, ys->v_size, (long long)ch * pr->orow, noblend ? 0 : (long long)ch * pr->irow2}))) return rc;
   hipStream_t st = (hipStream_t)stream;
   PbPin pin;
   if ((rc = pb_table(interp, pr->sw, pr->sh, pr->dw, pr->dh, st, &pin))) return rc;
@@ -2740,24 +2755,15 @@ extern "C" int lgpu_chain_yuv420p(const lgpu_chain_params *pr, const lgpu_yuv_so
   a.sw = pr->sw; a.sh = pr->sh; a.irow = lys; a.dw = pr->dw; a.dh = pr->dh; a.orow = pr->orow;
   a.swap_rb = (ys->out_order ^ (pr->swap_rb ? 1 : 0)) & 1; a.blend = 1; a.irow2 = noblend ? pr->orow : pr->irow2; a.use_lut = pr->use_lut ? 1 : 0;
   a.bf = 0; a.bf_d = nullptr; a.bf_tracks = 1; a.nt_out = 1;
-  a.row_major = -1;
-  a.bgroup = 0;
   pb_half_geometry(&a, ntracks, 0, 0, 1);
-  a.row_major = ((long long)a.cgroups * a.bands * ntracks >= (long long)device_cus() * 8 + 1) ? 2 : 1;
-  a.bgroup = (a.bands % 8 == 0) ? a.bands / 8 : 1;
-  a.cw = a.ch = a.ox = a.oy = 0; a.bar_blocks = 0;
-  if (cv) { a.cw = cv->nwidth; a.ch = cv->nheight; a.ox = cv->offs_x; a.oy = cv->offs_y; a.bar_blocks = (int)cdiv((unsigned)(a.cw * a.ch - a.dw * a.dh), 1024u); }
-  a.main_blocks = (int)pb_half_grid(a);
-  a.bar_first = (a.bar_blocks * ntracks + 7) & ~7;
+  pb_half_shape(&a, ntracks, cv, false);
   PbTracks T;
   PbYuvSrc Y;
   for (int i = 0; i < ntracks; i++) {
     T.src[i] = tracks[i].y_d; T.l2[i] = noblend ? tracks[i].dst_d : tracks[i].layer2_d; T.dst[i] = tracks[i].dst_d; T.bf[i] = amounts ? amounts[i] : 0;
     Y.u[i] = tracks[i].u_d; Y.v[i] = tracks[i].v_d;
   }
-  Y.tables = device_tables()->yuv2rgb[ys->which_tables & 3];
-  Y.us = us; Y.vs = vs; Y.usize = (uint32_t)ys->u_size; Y.vsize = (uint32_t)ys->v_size;
-  Y.clamped = !(ys->which_tables & 1); Y.lowq = ys->pb_quality == 1; Y.fix_edges = (ys->flags & LGPU_YUV_FIX_EDGES) ? 1 : 0;
+  pb_fill_yuv_src(&Y, ys);
   const Lut8 l = pack_lut(pr->use_lut ? pr->lut8 : nullptr);
   const dim3 grid((unsigned)(a.main_blocks + a.bar_first));
   // No dynamic LDS: pb_chain_half's cap of five workgroups per CU (profiles/r04/occupancy_sweep.txt) was measured for the memory-bound RGBA kernel; this one is
@@ -2808,6 +2814,71 @@ int get_sink_tables(int which_tables, int in_order, const uint2 **out) {      //
   return LGPU_OK;
 }
 
+// ---- the argument checks the one-launch forms share (lgpu_common.h; flat.hip's entry points call them too) ----
+#define CHECK_REQUIRE(cond, msg) do { if (!(cond)) { set_error("%s: %s", fn, msg); return LGPU_E_BADARG; } } while (0)
+int lgpu::check_yuv_source(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv_source *s, int sfmt) {
+  CHECK_REQUIRE(pr->sw >= 2 && !(pr->sw & 1) && pr->sh >= 1 && pr->dw > 0 && pr->dh > 0, "empty geometry or an odd 4:2:0 / 4:2:2 width");
+  CHECK_REQUIRE(s->out_order == 0 || s->out_order == 1, "out_order is 0 (RGBA) or 1 (BGRA)");
+  CHECK_REQUIRE(s->which_tables >= 0 && s->which_tables <= 3, "source which_tables is 0..3");
+  CHECK_REQUIRE(s->pb_quality >= 1 && s->pb_quality <= 3, "pb_quality is 1 (LOW), 2 (MED) or 3 (HIGH)");
+  CHECK_REQUIRE(!(s->flags & ~LGPU_YUV_FIX_EDGES), "unknown flags");
+  if (sfmt == 2 || sfmt == 3) {
+    CHECK_REQUIRE(!(s->which_tables & 2), "UYVY / YUYV are converted with the YCbCr tables only (as lgpu_yuv_to_rgb)");
+    CHECK_REQUIRE(s->istrides[0] >= pr->sw * 2, "plane rowstride smaller than a row");
+    return LGPU_OK;
+  }
+  const int hw = pr->sw >> 1, hh = sfmt == 5 ? pr->sh : (pr->sh + 1) >> 1;
+  CHECK_REQUIRE(s->istrides[0] >= pr->sw && s->istrides[1] >= hw && s->istrides[2] >= hw, "plane rowstride smaller than a row");
+  CHECK_REQUIRE(s->u_size >= (long)(hh - 1) * s->istrides[1] + hw && s->v_size >= (long)(hh - 1) * s->istrides[2] + hw,
+                sfmt == 5 ? "chroma plane smaller than its (sw / 2) x sh samples" : "chroma plane smaller than its (sw / 2) x (sh / 2) samples");
+  return LGPU_OK;
+}
+int lgpu::check_yuv_sink(const char *fn, const lgpu_chain_params *pr, const lgpu_chain_sink *sk, int chain_order, bool l2rgba) {
+  CHECK_REQUIRE(sk->out_fmt >= 2 && sk->out_fmt <= 5, "out_fmt must be 2 (UYVY), 3 (YUYV), 4 (4:2:0 planar) or 5 (4:2:2 planar)");
+  CHECK_REQUIRE(sk->in_order == 0 || sk->in_order == 1, "in_order is 0 (RGBA) or 1 (BGRA)");
+  CHECK_REQUIRE(sk->which_tables >= 0 && sk->which_tables <= 3, "sink which_tables is 0..3");
+  CHECK_REQUIRE(sk->out_fmt >= 4 || !(sk->which_tables & 2), "only the 4:2:0 / 4:2:2 conversions take a BT.709 subspace (as lgpu_rgb_to_yuv)");
+  CHECK_REQUIRE(!(pr->dw & 1), "an odd destination width");
+  CHECK_REQUIRE(pr->sw < 32768 && pr->sh < 32768, "frame sides must stay below 32768 (16.16 positions)");
+  CHECK_REQUIRE(chain_order < 0 || sk->in_order == chain_order, "sink->in_order must state the byte order of the chain's result: src->out_order ^ params->swap_rb");
+  const bool planar = sk->out_fmt >= 4;
+  const int cwid = pr->dw >> 1;
+  CHECK_REQUIRE(!l2rgba || pr->irow2 >= pr->dw * 4, "rowstride smaller than a row");
+  CHECK_REQUIRE(sk->orow[0] >= (planar ? pr->dw : pr->dw * 2) && (!planar || (sk->orow[1] >= cwid && sk->orow[2] >= cwid)), "sink rowstride smaller than a row");
+  CHECK_REQUIRE(!l2rgba || !(pr->irow2 & 3), "rowstrides must be multiples of 4");
+  return LGPU_OK;
+}
+int lgpu::check_rgba_dest(const char *fn, const lgpu_chain_params *pr, const lgpu_canvas *cv, bool l2rgba) {
+  if (cv)
+    CHECK_REQUIRE(cv->nwidth >= pr->dw && cv->nheight >= pr->dh && cv->offs_x >= 0 && cv->offs_y >= 0 && cv->offs_x + pr->dw <= cv->nwidth &&
+                  cv->offs_y + pr->dh <= cv->nheight, "the frame must lie inside the canvas");
+  const int cw = cv ? cv->nwidth : pr->dw;
+  CHECK_REQUIRE(pr->orow >= cw * 4 && (!l2rgba || pr->irow2 >= cw * 4), "rowstride smaller than a row");
+  CHECK_REQUIRE(((pr->orow | (l2rgba ? pr->irow2 : 0)) & 3) == 0, "rowstrides must be multiples of 4");
+  return LGPU_OK;
+}
+int lgpu::check_track(const char *fn, const uint8_t *const src[3], int nsrc, bool rgba_src, const uint8_t *l2, bool l2rgba, uint8_t *const *dst, int ndst, bool rgba_dst) {
+  for (int k = 0; k < nsrc; k++) CHECK_REQUIRE(src[k], "null track pointer");
+  CHECK_REQUIRE(!l2rgba || l2, "null track pointer");
+  CHECK_REQUIRE(!l2rgba || !((uintptr_t)l2 & 3), "layer 2 must be 4-byte aligned");
+  CHECK_REQUIRE(!rgba_src || !((uintptr_t)src[0] & 3), "the source must be 4-byte aligned");
+  for (int k = 0; k < ndst; k++) {
+    CHECK_REQUIRE(dst[k], "null destination plane");
+    CHECK_REQUIRE((const uint8_t *)dst[k] != src[0] && (const uint8_t *)dst[k] != src[1] && (const uint8_t *)dst[k] != src[2], "the chain cannot run in place");
+  }
+  CHECK_REQUIRE(!rgba_dst || !((uintptr_t)dst[0] & 3), "the destination must be 4-byte aligned");
+  return LGPU_OK;
+}
+int lgpu::check_plane_sizes(const char *fn, std::initializer_list<long long> bytes, const char *instead) {
+  for (const long long b : bytes)
+    if (b >= (1ll << 31)) {
+      if (instead) set_error("%s: planes of 2 GiB or more (%s)", fn, instead); else set_error("%s: planes of 2 GiB or more", fn);
+      return LGPU_E_UNSUPPORTED;
+    }
+  return LGPU_OK;
+}
+#undef CHECK_REQUIRE
+
 // lgpu_chain_to_yuv: the 2:1 chain that ENDS at a YUV consumer -- [R <-> B] -> the exact 2:1 scaler [-> chroma blend with layer 2] [-> gamma LUT] -> K4's conversion
 // (lgpu_rgb_to_yuv, every quirk kept) to UYVY / YUYV / YUV420P, one launch for every track; the RGBA result is never written.  Every argument is checked before
 // anything is enqueued.
@@ -2819,23 +2890,17 @@ extern "C" int lgpu_chain_to_yuv(const lgpu_chain_params *pr, const lgpu_chain_s
   LGPU_REQUIRE(pr->interp & LGPU_INTERP_PIXBUF, "lgpu_chain_to_yuv serves the gdk-pixbuf arithmetic (LGPU_INTERP_PIXBUF)");
   const bool noblend = (pr->interp & LGPU_INTERP_NOBLEND) != 0;
   LGPU_REQUIRE(amounts || noblend, "null amounts");
-  LGPU_REQUIRE(sk->out_fmt >= 2 && sk->out_fmt <= 5, "out_fmt must be 2 (UYVY), 3 (YUYV), 4 (4:2:0 planar) or 5 (4:2:2 planar)");
-  LGPU_REQUIRE(sk->in_order == 0 || sk->in_order == 1, "in_order is 0 (RGBA) or 1 (BGRA)");
-  LGPU_REQUIRE(sk->which_tables >= 0 && sk->which_tables <= 3, "which_tables is 0..3");
-  LGPU_REQUIRE(sk->out_fmt >= 4 || !(sk->which_tables & 2), "only the 4:2:0 / 4:2:2 conversions take a BT.709 subspace (as lgpu_rgb_to_yuv)");
-  LGPU_REQUIRE(pr->sw > 0 && pr->sh > 0 && pr->dw > 0 && pr->dh > 0 && !(pr->dw & 1), "empty geometry or an odd destination width");
-  LGPU_REQUIRE(pr->sw < 32768 && pr->sh < 32768, "frame sides must stay below 32768 (16.16 positions)");
+  static const char fn[] = "lgpu_chain_to_yuv";
+  LGPU_REQUIRE(pr->sw > 0 && pr->sh > 0 && pr->dw > 0 && pr->dh > 0, "empty geometry");
+  LGPU_REQUIRE(pr->irow >= pr->sw * 4 && !(pr->irow & 3), "source rowstride smaller than a row or no multiple of 4");
+  if ((rc = check_yuv_sink(fn, pr, sk, -1, !noblend))) return rc;
   const bool planar = sk->out_fmt >= 4;
-  const int nplanes = planar ? 3 : 1, cwid = pr->dw >> 1;
-  LGPU_REQUIRE(pr->irow >= pr->sw * 4 && (noblend || pr->irow2 >= pr->dw * 4), "rowstride smaller than a row");
-  LGPU_REQUIRE(sk->orow[0] >= (planar ? pr->dw : pr->dw * 2) && (!planar || (sk->orow[1] >= cwid && sk->orow[2] >= cwid)), "sink rowstride smaller than a row");
-  LGPU_REQUIRE(((pr->irow | (noblend ? 0 : pr->irow2)) & 3) == 0, "rowstrides must be multiples of 4");
   uintptr_t sb = (uintptr_t)pr->irow, lb = noblend ? 0 : (uintptr_t)pr->irow2, pb = 0;
   for (int i = 0; i < ntracks; i++) {
     const lgpu_chain_sink_track &t = tracks[i];
-    LGPU_REQUIRE(t.src_d && (noblend || t.layer2_d), "null track pointer");
-    for (int k = 0; k < nplanes; k++) { LGPU_REQUIRE(t.dst_d[k], "null destination plane"); LGPU_REQUIRE(t.dst_d[k] != t.src_d, "the chain cannot run in place"); pb |= (uintptr_t)t.dst_d[k]; }
-    LGPU_REQUIRE((((uintptr_t)t.src_d | (uintptr_t)(noblend ? nullptr : t.layer2_d)) & 3) == 0, "frames must be 4-byte aligned");
+    const uint8_t *const planes[3] = {t.src_d, nullptr, nullptr};
+    if ((rc = check_track(fn, planes, 1, true, t.layer2_d, !noblend, t.dst_d, planar ? 3 : 1, false))) return rc;
+    for (int k = 0; k < (planar ? 3 : 1); k++) pb |= (uintptr_t)t.dst_d[k];
     sb |= (uintptr_t)t.src_d; lb |= (uintptr_t)(noblend ? nullptr : t.layer2_d);
   }
   // the one-launch form; anything else is refused, never run some other way
@@ -2848,11 +2913,7 @@ extern "C" int lgpu_chain_to_yuv(const lgpu_chain_params *pr, const lgpu_chain_s
               "8-byte aligned layer-2 rows, luma / packed rowstride %% 8 == 0, chroma rowstrides %% 4 == 0) of an RGBA source; a YUV420P source: lgpu_chain_yuv420p_to_yuv");
     return LGPU_E_UNSUPPORTED;
   }
-  const long long lim = 1ll << 31;
-  if ((long long)pr->sh * pr->irow >= lim || (long long)pr->dh * sk->orow[0] >= lim || (!noblend && (long long)pr->dh * pr->irow2 >= lim)) {
-    set_error("lgpu_chain_to_yuv: planes of 2 GiB or more");
-    return LGPU_E_UNSUPPORTED;
-  }
+  if ((rc = check_plane_sizes(fn, {(long long)pr->sh * pr->irow, (long long)pr->dh * sk->orow[0], noblend ? 0 : (long long)pr->dh * pr->irow2}))) return rc;
   hipStream_t st = (hipStream_t)stream;
   PbPin pin;
   if ((rc = pb_table(interp, pr->sw, pr->sh, pr->dw, pr->dh, st, &pin))) return rc;
@@ -2868,38 +2929,22 @@ extern "C" int lgpu_chain_to_yuv(const lgpu_chain_params *pr, const lgpu_chain_s
   a.sw = pr->sw; a.sh = pr->sh; a.irow = pr->irow; a.dw = pr->dw; a.dh = pr->dh; a.orow = sk->orow[0];
   a.swap_rb = pr->swap_rb ? 1 : 0; a.blend = 1; a.irow2 = noblend ? pr->irow : pr->irow2; a.use_lut = pr->use_lut ? 1 : 0;
   a.bf = 0; a.bf_d = nullptr; a.bf_tracks = amounts ? 1 : 0; a.nt_out = 1;
-  a.row_major = -1; a.bgroup = 0;
   pb_half_geometry(&a, ntracks);
   // Launch-shape switches: PBH_TH and PBH_OCC are honoured; PBH_ALIGNED = 0 is OVERRIDDEN (the sink form exists on strips of 64 quads only: a quad of lanes must
-  // start on an 8-byte luma boundary); PBH_ORDER and PBH_GROUP are NOT consulted -- the work order is pb_chain_half's default for the launch's size.  For the 4:2:0
-  // form a.th / a.rem (pb_half_bands) are not what the kernel walks: only a.bands counts, the rows of a band come from PbSinkDst.pairs.
+  // start on an 8-byte luma boundary); PBH_ORDER and PBH_GROUP are NOT consulted -- the work order is pb_chain_half's default for the launch's size.
   if (!a.aligned) { a.aligned = 1; a.strips = (int)cdiv((unsigned)a.dw, 128u); a.cgroups = (a.strips + 3) / 4; }
-  S.pairs = 0;
-  if (planar) {
-    // band boundaries at odd rows: the (dh - 2) / 2 inner row pairs dealt to the bands, row 0 with the first band, row dh - 1 with the last (k_pb_half's comment)
-    const int pairs = (a.dh - 2) / 2;
-    pb_half_bands(&a, std::min(a.bands, std::max(1, pairs)));
-    S.pairs = pairs;
-  }
-  a.row_major = ((long long)a.cgroups * a.bands * ntracks >= (long long)device_cus() * 8 + 1) ? 2 : 1;      // as pb_chain_half
-  a.bgroup = (a.bands % 8 == 0) ? a.bands / 8 : 1;
-  a.cw = a.ch = a.ox = a.oy = 0; a.bar_blocks = 0;
-  a.main_blocks = (int)pb_half_grid(a);
-  a.bar_first = 0;
+  S.pairs = pb_half_shape(&a, ntracks, nullptr, planar);
   PbTracks T;
   for (int i = 0; i < ntracks; i++) {
     T.src[i] = tracks[i].src_d; T.l2[i] = noblend ? tracks[i].src_d : tracks[i].layer2_d; T.dst[i] = tracks[i].dst_d[0]; T.bf[i] = amounts ? amounts[i] : 0;
     S.u[i] = planar ? tracks[i].dst_d[1] : nullptr; S.v[i] = planar ? tracks[i].dst_d[2] : nullptr;
   }
-  S.urow = planar ? sk->orow[1] : 0; S.vrow = planar ? sk->orow[2] : 0; S.fmt = sk->out_fmt; S.unclamped = sk->which_tables & 1;
+  pb_fill_sink(&S, sk);
   const Lut8 l = pack_lut(pr->use_lut ? pr->lut8 : nullptr);
   const dim3 grid((unsigned)a.main_blocks);
-  // Workgroups per CU: pb_chain_half's five for launches of more than one generation, held by unused DYNAMIC LDS -- less the 12 KB of static LDS the sink's tables
-  // take, so that the count stays what it was (5 x (14.25 KB static + 17 KB dynamic) fits 160 KB, six do not)
-  int occ = ((long long)a.cgroups * a.bands * ntracks > (long long)device_cus() * 8) ? 5 : 0;
-  if (tune(TUNE_PBH_OCC) >= 0) occ = tune(TUNE_PBH_OCC);
-  const size_t per_wg = occ > 0 && occ < 16 ? (size_t)(160 * 1024) / (size_t)occ : 0, held = 3072 + sizeof(PbSinkLds<1>);
-  const size_t occ_lds = per_wg > held ? per_wg - held : 0;
+  // pb_chain_half's five workgroups per CU for launches of more than one generation, less the 12 KB of static LDS the sink's tables take, so that the count stays
+  // what it was (5 x (14.25 KB static + 17 KB dynamic) fits 160 KB, six do not)
+  const size_t occ_lds = pb_half_occ_lds(a, ntracks, true, 3072 + sizeof(PbSinkLds<1>));
 #define PBS_LAUNCH(CH, HY, SW, SK) hipLaunchKernelGGL((k_pb_half<CH, HY, 0, 1, SW, 0, 0, SK>), grid, dim3(256), occ_lds, st, a, T, l, S)
 #define PBS_SWAP(CH, HY, SK) do { if (a.swap_rb) PBS_LAUNCH(CH, HY, 1, SK); else PBS_LAUNCH(CH, HY, 0, SK); } while (0)
 #define PBS_HYPER(CH, SK) do { if (a.hyper) PBS_SWAP(CH, 1, SK); else PBS_SWAP(CH, 0, SK); } while (0)
@@ -2913,8 +2958,8 @@ extern "C" int lgpu_chain_to_yuv(const lgpu_chain_params *pr, const lgpu_chain_s
 }
 
 // lgpu_chain_yuv420p_to_yuv: both ends at once -- K2's conversion in registers -> the exact 2:1 scaler (all-opaque arithmetic) [-> chroma blend with layer 2] [-> gamma
-// LUT] -> K4's conversion in the store.  Neither the 4K nor the 1080p RGBA frame is ever written.  Every check of lgpu_chain_yuv420p and of lgpu_chain_to_yuv on their
-// own arguments is made here before anything is enqueued.
+// LUT] -> K4's conversion in the store.  Neither the 4K nor the 1080p RGBA frame is ever written.  The source is checked as lgpu_chain_yuv420p checks it and the
+// sink as lgpu_chain_to_yuv does -- by the same functions (check_yuv_source, check_yuv_sink) -- before anything is enqueued.
 static_assert(sizeof(PbHalfArgs) + sizeof(PbTracks) + sizeof(Lut8) + sizeof(PbYuvSink) <= 4096, "HIP documents 4 KB of arguments for a __global__ function");
 static_assert(sizeof(PbHalfArgs) + sizeof(PbTracks) + sizeof(Lut8) + sizeof(PbYuvSrc) <= 4096 && sizeof(PbHalfArgs) + sizeof(PbTracks) + sizeof(Lut8) + sizeof(PbSinkDst) <= 4096,
               "HIP documents 4 KB of arguments for a __global__ function");
@@ -2926,39 +2971,16 @@ extern "C" int lgpu_chain_yuv420p_to_yuv(const lgpu_chain_params *pr, const lgpu
   LGPU_REQUIRE(pr->interp & LGPU_INTERP_PIXBUF, "lgpu_chain_yuv420p_to_yuv serves the gdk-pixbuf arithmetic (LGPU_INTERP_PIXBUF)");
   const bool noblend = (pr->interp & LGPU_INTERP_NOBLEND) != 0;
   LGPU_REQUIRE(amounts || noblend, "null amounts");
-  // the source's own (lgpu_chain_yuv420p)
-  LGPU_REQUIRE(pr->sw >= 2 && !(pr->sw & 1) && pr->sh >= 1 && pr->dw > 0 && pr->dh > 0, "empty geometry or an odd 4:2:0 width");
-  LGPU_REQUIRE(ys->out_order == 0 || ys->out_order == 1, "out_order is 0 (RGBA) or 1 (BGRA)");
-  LGPU_REQUIRE(ys->which_tables >= 0 && ys->which_tables <= 3, "source which_tables is 0..3");
-  LGPU_REQUIRE(ys->pb_quality >= 1 && ys->pb_quality <= 3, "pb_quality is 1 (LOW), 2 (MED) or 3 (HIGH)");
-  LGPU_REQUIRE(!(ys->flags & ~LGPU_YUV_FIX_EDGES), "unknown flags");
-  const int hw = pr->sw >> 1, hh = (pr->sh + 1) >> 1, lys = ys->istrides[0], us = ys->istrides[1], vs = ys->istrides[2];
-  LGPU_REQUIRE(lys >= pr->sw && us >= hw && vs >= hw, "plane rowstride smaller than a row");
-  LGPU_REQUIRE(ys->u_size >= (long)(hh - 1) * us + hw && ys->v_size >= (long)(hh - 1) * vs + hw, "chroma plane smaller than its (sw / 2) x (sh / 2) samples");
-  // the sink's own (lgpu_chain_to_yuv)
-  LGPU_REQUIRE(sk->out_fmt >= 2 && sk->out_fmt <= 5, "out_fmt must be 2 (UYVY), 3 (YUYV), 4 (4:2:0 planar) or 5 (4:2:2 planar)");
-  LGPU_REQUIRE(sk->in_order == 0 || sk->in_order == 1, "in_order is 0 (RGBA) or 1 (BGRA)");
-  LGPU_REQUIRE(sk->which_tables >= 0 && sk->which_tables <= 3, "sink which_tables is 0..3");
-  LGPU_REQUIRE(sk->out_fmt >= 4 || !(sk->which_tables & 2), "only the 4:2:0 / 4:2:2 conversions take a BT.709 subspace (as lgpu_rgb_to_yuv)");
-  LGPU_REQUIRE(!(pr->dw & 1), "an odd destination width");
-  LGPU_REQUIRE(pr->sw < 32768 && pr->sh < 32768, "frame sides must stay below 32768 (16.16 positions)");
-  const int chain_order = (ys->out_order ^ (pr->swap_rb ? 1 : 0)) & 1;
-  LGPU_REQUIRE(sk->in_order == chain_order, "sink->in_order must state the byte order of the chain's result: src->out_order ^ params->swap_rb");
+  static const char fn[] = "lgpu_chain_yuv420p_to_yuv";
+  const int chain_order = (ys->out_order ^ (pr->swap_rb ? 1 : 0)) & 1, lys = ys->istrides[0];
+  if ((rc = check_yuv_source(fn, pr, ys, 4)) || (rc = check_yuv_sink(fn, pr, sk, chain_order, !noblend))) return rc;
   const bool planar = sk->out_fmt >= 4;
-  const int nplanes = planar ? 3 : 1, cwid = pr->dw >> 1;
-  LGPU_REQUIRE(noblend || pr->irow2 >= pr->dw * 4, "rowstride smaller than a row");
-  LGPU_REQUIRE(sk->orow[0] >= (planar ? pr->dw : pr->dw * 2) && (!planar || (sk->orow[1] >= cwid && sk->orow[2] >= cwid)), "sink rowstride smaller than a row");
-  LGPU_REQUIRE(noblend || !(pr->irow2 & 3), "rowstrides must be multiples of 4");
   uintptr_t lb = noblend ? 0 : (uintptr_t)pr->irow2, pb = 0;
   for (int i = 0; i < ntracks; i++) {
     const lgpu_chain_yuv_sink_track &t = tracks[i];
-    LGPU_REQUIRE(t.y_d && t.u_d && t.v_d && (noblend || t.layer2_d), "null track pointer");
-    LGPU_REQUIRE(noblend || !((uintptr_t)t.layer2_d & 3), "layer 2 must be 4-byte aligned");
-    for (int k = 0; k < nplanes; k++) {
-      LGPU_REQUIRE(t.dst_d[k], "null destination plane");
-      LGPU_REQUIRE((const uint8_t *)t.dst_d[k] != t.y_d && (const uint8_t *)t.dst_d[k] != t.u_d && (const uint8_t *)t.dst_d[k] != t.v_d, "the chain cannot run in place");
-      pb |= (uintptr_t)t.dst_d[k];
-    }
+    const uint8_t *const planes[3] = {t.y_d, t.u_d, t.v_d};
+    if ((rc = check_track(fn, planes, 3, false, t.layer2_d, !noblend, t.dst_d, planar ? 3 : 1, false))) return rc;
+    for (int k = 0; k < (planar ? 3 : 1); k++) pb |= (uintptr_t)t.dst_d[k];
     lb |= (uintptr_t)(noblend ? nullptr : t.layer2_d);
   }
   // the one-launch form; anything else is refused, never run some other way
@@ -2971,11 +2993,8 @@ extern "C" int lgpu_chain_yuv420p_to_yuv(const lgpu_chain_params *pr, const lgpu
               "8-byte aligned layer-2 rows, luma / packed rowstride %% 8 == 0, chroma rowstrides %% 4 == 0); run lgpu_chain_yuv420p + lgpu_rgb_to_yuv_batch otherwise");
     return LGPU_E_UNSUPPORTED;
   }
-  const long long lim = 1ll << 31;
-  if ((long long)pr->sh * lys >= lim || ys->u_size >= lim || ys->v_size >= lim || (long long)pr->dh * sk->orow[0] >= lim || (!noblend && (long long)pr->dh * pr->irow2 >= lim)) {
-    set_error("lgpu_chain_yuv420p_to_yuv: planes of 2 GiB or more (lgpu_chain_yuv420p + lgpu_rgb_to_yuv_batch)");
-    return LGPU_E_UNSUPPORTED;
-  }
+  if ((rc = check_plane_sizes(fn, {(long long)pr->sh * lys, ys->u_size, ys->v_size, (long long)pr->dh * sk->orow[0], noblend ? 0 : (long long)pr->dh * pr->irow2},
+                              "lgpu_chain_yuv420p + lgpu_rgb_to_yuv_batch"))) return rc;
   hipStream_t st = (hipStream_t)stream;
   PbPin pin;
   if ((rc = pb_table(interp, pr->sw, pr->sh, pr->dw, pr->dh, st, &pin))) return rc;
@@ -2992,27 +3011,15 @@ extern "C" int lgpu_chain_yuv420p_to_yuv(const lgpu_chain_params *pr, const lgpu
   a.sw = pr->sw; a.sh = pr->sh; a.irow = lys; a.dw = pr->dw; a.dh = pr->dh; a.orow = sk->orow[0];
   a.swap_rb = chain_order; a.blend = 1; a.irow2 = noblend ? sk->orow[0] : pr->irow2; a.use_lut = pr->use_lut ? 1 : 0;
   a.bf = 0; a.bf_d = nullptr; a.bf_tracks = 1; a.nt_out = 1;
-  a.cw = a.ch = a.ox = a.oy = 0; a.bar_blocks = 0; a.bar_first = 0;
-  Y.y.tables = device_tables()->yuv2rgb[ys->which_tables & 3];
-  Y.y.us = us; Y.y.vs = vs; Y.y.usize = (uint32_t)ys->u_size; Y.y.vsize = (uint32_t)ys->v_size;
-  Y.y.clamped = !(ys->which_tables & 1); Y.y.lowq = ys->pb_quality == 1; Y.y.fix_edges = (ys->flags & LGPU_YUV_FIX_EDGES) ? 1 : 0;
-  Y.s.urow = planar ? sk->orow[1] : 0; Y.s.vrow = planar ? sk->orow[2] : 0; Y.s.fmt = sk->out_fmt; Y.s.unclamped = sk->which_tables & 1;
+  pb_fill_yuv_src(&Y.y, ys);
+  pb_fill_sink(&Y.s, sk);
   const Lut8 l = pack_lut(pr->use_lut ? pr->lut8 : nullptr);
   // kPbTranscodeTracks tracks per launch (the kernel arguments, PbYuvSink's comment): a longer tick goes as two launches on the stream
   for (int t0 = 0; t0 < ntracks; t0 += kPbTranscodeTracks) {
     const int n = std::min(kPbTranscodeTracks, ntracks - t0);
-    a.row_major = -1; a.bgroup = 0;
     // the 4:2:0 sink walks strips of 60 storing lanes (whole quads of k per wave, k_pb_half's comment); the packed sinks keep the source form's 62
     pb_half_geometry(&a, n, 0, 0, 1, planar ? 120 : 0);
-    Y.s.pairs = 0;
-    if (planar) {      // band boundaries at odd rows, as lgpu_chain_to_yuv deals them
-      const int pairs = (a.dh - 2) / 2;
-      pb_half_bands(&a, std::min(a.bands, std::max(1, pairs)));
-      Y.s.pairs = pairs;
-    }
-    a.row_major = ((long long)a.cgroups * a.bands * n >= (long long)device_cus() * 8 + 1) ? 2 : 1;
-    a.bgroup = (a.bands % 8 == 0) ? a.bands / 8 : 1;
-    a.main_blocks = (int)pb_half_grid(a);
+    Y.s.pairs = pb_half_shape(&a, n, nullptr, planar);
     PbTracks T;
     for (int i = 0; i < n; i++) {
       const lgpu_chain_yuv_sink_track &t = tracks[t0 + i];
