@@ -238,6 +238,34 @@ typedef struct {
   int vec, xoff;                 /* the separable kernels' 16-byte window loads; LGPU_PATH_HALF8S: the aligned-window form */
 } lgpu_resize_plan;
 int lgpu_debug_resize_plan(const lgpu_resize_plan_query *q, lgpu_resize_plan *out);
+/* test hook, the same contract for the gdk-pixbuf scaler below: which kernel lgpu_pixbuf_scale / lgpu_pixbuf_scale_batch (LGPU_PB_PLAN_SCALE) or the fused chain's
+   scale with the chain's last stages in its store (LGPU_PB_PLAN_CHAIN: lgpu_chain_amounts and its kin at every ratio but the aligned 2:1) would launch, decided by
+   the very function the launch switches on (pixbuf.hip: pb_plan, on a host-built weight table); host only -- no HIP call, nothing launched, works without a device.
+   interp: 0 / 2 / 3, LGPU_INTERP_OPAQUE included where the call carries it.  src_bits / dst_bits: the OR of the low four address bits of every source resp.
+   destination frame.  LGPU_TUNE "PB_NO_PAIRS", "PB_UP_RB" (and "PBH_ALIGNED" for k_pb_half's form) are read as the launch reads them.  Returns LGPU_OK with
+   out->path one of LGPU_PB_PATH_*: LGPU_PB_PATH_REFUSED (out->rc = what the call returns) and LGPU_PB_PATH_NOT_FUSED (the chain runs its stages one after the
+   other; rc LGPU_OK) included; LGPU_E_BADARG for a query that is no call at all (what the entry points answer with LGPU_E_BADARG). */
+enum { LGPU_PB_PLAN_SCALE = 0, LGPU_PB_PLAN_CHAIN = 1 };
+/* lgpu_copy_rows; k_pb_nearest<ch>; k_pb_double<0>; k_pb_half3<hyper>; k_pb_half<0, hyper, 0, aligned>; k_pb_up<np, ny, opq, epi>; k_pb_gather<np, epi, opq>;
+   k_pb_pairs<ch, np, ny, pre, opq, epi>; k_pb_window<ch, uniform>; k_pb_direct<ch>; nothing (PB_NOT_FUSED to the chain); nothing */
+enum { LGPU_PB_PATH_COPY = 1, LGPU_PB_PATH_NEAREST, LGPU_PB_PATH_DOUBLE, LGPU_PB_PATH_HALF3, LGPU_PB_PATH_HALF, LGPU_PB_PATH_UP, LGPU_PB_PATH_GATHER,
+       LGPU_PB_PATH_PAIRS, LGPU_PB_PATH_WINDOW, LGPU_PB_PATH_DIRECT, LGPU_PB_PATH_NOT_FUSED, LGPU_PB_PATH_REFUSED };
+typedef struct { int sw, sh, dw, dh, channels, interp, irow, orow; unsigned src_bits, dst_bits; int nframes, mode; } lgpu_pixbuf_plan_query;
+typedef struct {
+  int path, rc;                       /* LGPU_PB_PATH_*; rc: LGPU_OK, or the error of a refused call */
+  int ch, np, ny, pre, opq, epi;      /* the template arguments instantiated (0 where the family has none of that name); epi: the PbEpi form */
+  int hyper, aligned, uniform;        /* k_pb_half3 / k_pb_half: HYPER, ALIGNED; k_pb_window: UNIFORM_X */
+  int tile_h, win_h, win_w, lds;      /* rows per tile or band; window rows; window columns (k_pb_pairs: pixel pairs); dynamic LDS bytes */
+  int gx, gy, gz;                     /* the grid (k_pb_half: not reported, it depends on the device's CU count) */
+  int tiles_x, tiles_y, per_xcd;      /* k_pb_pairs: tiles per row and column; per_xcd > 0: the one-dimensional grid, a contiguous run of tiles per XCD */
+  int strips, cgroups, bands;         /* k_pb_double, k_pb_half3 */
+  int rb;                             /* k_pb_up: rows per band */
+  int x_step, y_step;                 /* 16.16 source steps */
+  int tx0, tx1, ty0, ty1, n_x, n_y;   /* the table's taps and the box of the non-zero ones among the phases this geometry takes */
+  int nq;                             /* k_pb_pairs: groups of four pairs per tap row */
+  unsigned rnd;
+} lgpu_pixbuf_plan;
+int lgpu_debug_pixbuf_plan(const lgpu_pixbuf_plan_query *q, lgpu_pixbuf_plan *out);
 /* ---- K7, pixbuf arithmetic: the reference's OTHER resize body -- resize_layer_full without swscale scales through
    lives_pixbuf_scale_simple == gdk_pixbuf_scale_simple (src/colourspace.c:15262-15322, call :15295), and the compositor scales its layers with the
    same call (lives-plugins/weed-plugins/gdk/compositor.c:263-265).  PINNED: bit-exact to gdk-pixbuf 2.42.8's output (tests/golden/pixbuf_scale.npz,

@@ -1845,6 +1845,7 @@ static void pb_fix_sum(int *w, int count, int total) {
 
 struct PbTable { int n_x, n_y, xoff, yoff, uniform_x; int *table_d; std::vector<int> host;
                  int tx0 = 0, tx1 = 0, ty0 = 0, ty1 = 0, nq = 0; uint32_t *pairs_d = nullptr; uint32_t *gpairs_d = nullptr;      // pairs_d: the k_pb_pairs form of the table (nullptr: a weight needs 17 bits)
+                 bool has_pairs = false, has_gather = false;       // host: the pair form / the k_pb_gather form of this table exists -- set by every build, uploaded or not (what pb_plan asks)
                  // cache bookkeeping (under g_pb_mu): the streams that have launched with this table, calls between lookup and launch, age
                  std::vector<hipStream_t> users; int pins = 0; unsigned long long stamp = 0; };
 // The tables of a geometry are cached per (device, interp, sw, sh, dw, dh) -- but BOUNDED: a compositor that animates its layers' scale or an interactive zoom asks
@@ -1942,8 +1943,10 @@ static int pb_build(int interp, int sw, int sh, int dw, int dh, PbTable *t, bool
             }
       }
     t->tx0 = tx0; t->tx1 = tx1; t->ty0 = ty0; t->ty1 = ty1;
-    if (upload && wmax < 65536 && tx1 > tx0) {
-      const int n_eff = tx1 - tx0, ny_eff = ty1 - ty0, np = (n_eff + 2) / 2, nq = (np + 3) / 4, rowlen = 4 * nq;
+    t->has_pairs = wmax < 65536 && tx1 > tx0;
+    if (t->has_pairs) { t->nq = ((tx1 - tx0 + 2) / 2 + 3) / 4; t->has_gather = (tx1 - tx0 + 1) / 2 <= 4; }
+    if (upload && t->has_pairs) {
+      const int n_eff = tx1 - tx0, ny_eff = ty1 - ty0, np = (n_eff + 2) / 2, nq = t->nq, rowlen = 4 * nq;
       std::vector<uint32_t> pr((size_t)16 * 16 * 2 * ny_eff * rowlen, 0u);
       for (int y = 0; y < 16; y++)
         for (int x = 0; x < 16; x++)
@@ -1959,10 +1962,9 @@ static int pb_build(int interp, int sw, int sh, int dw, int dh, PbTable *t, bool
           }
       if ((rc = pb_upload(pr.data(), pr.size() * sizeof(uint32_t), st, (void **)&t->pairs_d))) { pb_free_device(t, st); return rc; }
       (void)hipStreamSynchronize(st);          // pr is a local: its bytes must have left before it goes
-      t->nq = nq;
       // the same weights as pairs aligned on the first used tap (k_pb_gather: one form, no parity), rows of 2 or 4 dwords
       const int gnp = (n_eff + 1) / 2;
-      if (gnp <= 4) {
+      if (t->has_gather) {
         const int rl = gnp <= 2 ? 2 : 4;
         std::vector<uint32_t> gp((size_t)256 * ny_eff * rl, 0u);
         for (int ph = 0; ph < 256; ph++) {
@@ -2051,24 +2053,6 @@ extern "C" int lgpu_debug_pixbuf_cache_entries(void) {
 }
 
 
-// zero taps are common (the 5th row / column of an integer-ratio HYPER table, the far taps of most phases): only the phases this call's destination pixels
-// take are looked at, and the tap loops run over the bounding box of their non-zero weights
-static void pb_used_taps(const PbTable *t, int x_step, int y_step, int dw, int dh, PbArgs *a) {
-  bool xp[16] = {false}, yp[16] = {false};
-  for (int j = 0; j < dw; j++) xp[(((long long)j * x_step + t->xoff) >> 12) & 15] = true;
-  for (int i = 0; i < dh; i++) yp[(((long long)i * y_step + t->yoff) >> 12) & 15] = true;
-  int tx0 = t->n_x, tx1 = 0, ty0 = t->n_y, ty1 = 0;
-  for (int y = 0; y < 16; y++)
-    for (int x = 0; x < 16; x++) {
-      if (!xp[x] || !yp[y]) continue;
-      const int *w = t->host.data() + (size_t)(y * 16 + x) * t->n_x * t->n_y;
-      for (int ty = 0; ty < t->n_y; ty++)
-        for (int tx = 0; tx < t->n_x; tx++)
-          if (w[ty * t->n_x + tx]) { tx0 = tx < tx0 ? tx : tx0; tx1 = tx + 1 > tx1 ? tx + 1 : tx1; ty0 = ty < ty0 ? ty : ty0; ty1 = ty + 1 > ty1 ? ty + 1 : ty1; }
-    }
-  a->tx0 = tx0; a->tx1 = tx1; a->ty0 = ty0; a->ty1 = ty1;
-}
-
 // the exact-2:1 fast path: geometry, alignment, and the table really being the outer product the kernel evaluates
 static bool pb_half_ok(const PbTable *t, int interp, int sw, int sh, int dw, int dh, uintptr_t src_bits, uintptr_t dst_bits, int *hyper, int *ashift) {
   if (sw != 2 * dw || sh != 2 * dh || (sw & 3) || (src_bits & 15) || (dst_bits & 7)) return false;
@@ -2113,14 +2097,19 @@ static void pb_half_bands(PbHalfArgs *a, int bands) {
   a->bands = bands; a->th = a->dh / bands; a->rem = a->dh - a->th * bands;
 }
 
+// k_pb_half<.., ALIGNED>: the strips of 64 storing lanes (pb_half_geometry's comment), or the strips with feeder lanes
+static int pb_half_aligned(int blur, int yuv) {
+  if (blur || yuv) return 0;                    // (the 4:2:0 source: the all-opaque arithmetic exists for the strips with feeder lanes)
+  return tune(TUNE_PBH_ALIGNED) >= 0 ? (tune(TUNE_PBH_ALIGNED) ? 1 : 0) : 1;
+}
+
 static void pb_half_geometry(PbHalfArgs *a, int ntracks, int blur = 0, int opaque = 0, int yuv = 0, int strip_cols = 0) {      // strip_cols: output columns per strip, when the form has its own
   // strips of 64 storing lanes on 128-byte lines (k_pb_half<.., ALIGNED>; the two outer taps of a strip from one extra 4-byte load per source row, which lanes 0 and 63
   // keep as the raw pixel the lane exchange leaves in a lane without a source lane -- hrow_raw in the kernel).  Round 3 measured them 3 % lighter on traffic and 13 %
   // heavier on arithmetic: a draw.  With round 4's arithmetic (buffer addressing, five-operation reciprocal) they win clearly: 16 tracks 166.5 -> 155.0 us, 8 tracks
   // 85.7 -> 81.1, one frame equal (profiles/r04/al_ab1.txt, interleaved; measured on the exchange of premultiplied pairs that the kernel had then).  The exchange of raw
   // pixels and its instruction budget: profiles/r10/.  LGPU_PBH_ALIGNED=0 keeps the feeder-lane strips.
-  a->aligned = (blur || yuv) ? 0 : 1;           // (the 4:2:0 source: the all-opaque arithmetic exists for the strips with feeder lanes)
-  if (!blur && !yuv && tune(TUNE_PBH_ALIGNED) >= 0) a->aligned = tune(TUNE_PBH_ALIGNED) ? 1 : 0;
+  a->aligned = pb_half_aligned(blur, yuv);
   a->strips = (int)cdiv((unsigned)a->dw, strip_cols ? strip_cols : blur ? 120 : a->aligned ? 128 : 124);
   a->cgroups = (a->strips + 3) / 4;
   a->ntracks = ntracks;
@@ -2426,6 +2415,146 @@ extern "C" int lgpu_pixbuf_weights(int interp, int sw, int sh, int dw, int dh, i
   return LGPU_OK;
 }
 
+// ---- which kernel a scale takes: the ONE decision pb_scale_n launches from and lgpu_debug_pixbuf_plan reports ------------------------------------------
+struct PbCall {
+  int sw, sh, dw, dh, channels, interp;        // interp: 0, 2 or 3 (the flag bits taken off)
+  bool opaque, epi;                            // LGPU_INTERP_OPAQUE; the chain's call (PbEpi in the store)
+  int irow, orow;
+  uintptr_t sbits, dbits;                      // OR of the frames' addresses
+  int n;
+};
+// Pure host: geometry, pitches, address bits, frame count and the weight table in, the plan out.  `table` hands over the table of the geometry when the decision
+// gets that far (the launch: the cached, uploaded one; the query: a host-only build -- has_pairs / has_gather and the tap box are the same in both) and returns what
+// building it returned.  Nothing here looks at a device pointer or at the device.  k_pb_half's sweep order and band grouping depend on the CU count and are the
+// launch's; the plan names the instantiation only.
+template <class Table>
+static void pb_plan(const PbCall &c, Table &&table, lgpu_pixbuf_plan *p) {
+  *p = lgpu_pixbuf_plan{};
+  const int sw = c.sw, sh = c.sh, dw = c.dw, dh = c.dh, channels = c.channels, interp = c.interp, n = c.n;
+  p->path = LGPU_PB_PATH_REFUSED; p->rc = LGPU_OK;
+  if (c.epi && (channels != 4 || interp == 0 || (dw == sw && dh == sh))) { p->path = LGPU_PB_PATH_NOT_FUSED; return; }
+  if (dw == sw && dh == sh) { p->path = LGPU_PB_PATH_COPY; return; }       // gdk_pixbuf_scale_simple: a plain copy
+  const double scale_x = (double)dw / sw, scale_y = (double)dh / sh;
+  const int x_step = (int)(65536 / scale_x), y_step = (int)(65536 / scale_y);
+  p->x_step = x_step; p->y_step = y_step;
+  if (x_step == 0 || y_step == 0) { p->rc = LGPU_E_UNSUPPORTED; return; }
+  p->gx = (int)cdiv((unsigned)dw, 64); p->gy = (int)cdiv((unsigned)dh, 4); p->gz = n;       // the grid of the kernels without tiles of their own
+  if (interp == 0) { p->path = LGPU_PB_PATH_NEAREST; p->ch = channels; return; }
+  const PbTable *t = nullptr;
+  const int trc = table(&t);
+  if (t) { p->n_x = t->n_x; p->n_y = t->n_y; }
+  if (trc) { p->rc = trc; return; }
+  p->tx0 = t->tx0; p->tx1 = t->tx1; p->ty0 = t->ty0; p->ty1 = t->ty1;
+  p->rnd = (t->n_x == 2 && t->n_y == 2 && channels == 3) ? 0x8000u : 0xffffu;
+  const uintptr_t sbits = c.sbits, dbits = c.dbits;
+  const int irow = c.irow, orow = c.orow;
+  if (!c.epi && channels == 4 && dw == 2 * sw && dh == 2 * sh && (sw & 1) == 0 && ((sbits | (unsigned)irow) & 7) == 0 && ((dbits | (unsigned)orow) & 15) == 0 &&
+      pb_double_ok(t, x_step, y_step)) {
+    p->path = LGPU_PB_PATH_DOUBLE;
+    p->strips = (int)cdiv((unsigned)sw, 124); p->cgroups = (p->strips + 3) / 4;
+    p->tile_h = 3;                 // measured (1080p -> 4K): 16.5 us at 2-3 source rows per band, 18.2 us at 4, 22.8 at 8, 33.4 at 16, 52.7 at 32 -- per-wave latency, as in k_pb_half
+    p->bands = (int)cdiv((unsigned)sh, (unsigned)p->tile_h);
+    p->gx = (int)(8u * cdiv((unsigned)(p->cgroups * p->bands), 8u)); p->gy = 1;
+    return;
+  }
+  if (channels == 3 && sw == 2 * dw && sh == 2 * dh && (sw & 7) == 0 && ((sbits | dbits | (unsigned)irow | (unsigned)orow) & 3) == 0) {
+    int hyper, ashift;
+    // the same table check as the 4-byte kernel (alignment arguments that always pass: this kernel's own are checked above)
+    if (pb_half_ok(t, interp, sw, sh, dw, dh, 0, 0, &hyper, &ashift)) {
+      p->path = LGPU_PB_PATH_HALF3; p->hyper = hyper;
+      p->strips = (int)cdiv((unsigned)dw, 120); p->cgroups = (p->strips + 3) / 4; p->tile_h = 6; p->bands = (int)cdiv((unsigned)dh, 6u);
+      p->gx = (int)(8u * cdiv((unsigned)(p->cgroups * p->bands), 8u)); p->gy = 1;
+      return;
+    }
+  }
+  if (channels == 4 && !c.epi) {
+    int hyper, ashift;
+    if ((long long)sh * irow < (1ll << 31) && (long long)dh * orow < (1ll << 31) &&        // 32-bit buffer offsets in k_pb_half (see pb_chain_half)
+        pb_half_ok(t, interp, sw, sh, dw, dh, sbits | (uintptr_t)irow, dbits | (uintptr_t)orow, &hyper, &ashift)) {
+      p->path = LGPU_PB_PATH_HALF; p->hyper = hyper; p->aligned = pb_half_aligned(0, 0);
+      p->gx = p->gy = p->gz = 0;
+      return;
+    }
+  }
+  const bool no_pairs = tune_on(TUNE_PB_NO_PAIRS);        // tests: the one-tap-per-operation kernels at any ratio
+  const int n_eff = t->tx1 - t->tx0, ny_eff = t->ty1 - t->ty0;
+  // both sides enlarged: the register-window walk
+  if (channels == 4 && t->has_gather && !no_pairs && x_step <= 65536 && y_step <= 65536) {
+    // One filter serves both axes, and enlarging (or keeping) a side BILINEAR has two taps (pb_dimension: n = 2), HYPER four of which at least three are
+    // non-zero over the phases of a frame (phase 0, which pixel 0 takes, weights taps 0 and 1; the last pixel's phase weights tap 2; a kept side has the one
+    // phase [1 6 1] / 8): one tap pair goes with one or two tap rows, two pairs with three or four.  The other four <NP, NY> cannot be asked for and do not exist.
+    const int unp = (n_eff + 1) / 2, uny = ny_eff;
+    if ((unp == 1 && uny >= 1 && uny <= 2) || (unp == 2 && uny >= 3 && uny <= 4)) {
+      p->path = LGPU_PB_PATH_UP; p->np = unp; p->ny = uny; p->opq = c.opaque; p->epi = c.epi;
+      p->rb = (long long)dw * dh >= 6000000 ? 8 : 6;      // per-wave time rules (profiles/r03/pb_up_ab.txt: 720p -> 1080p 11.6 us at 6 rows per band, 15.3 at 16, 38 at 64)
+      { const int v = tune(TUNE_PB_UP_RB); if (v >= 1 && v <= 4096) p->rb = v; }      // tuning probe
+      p->tile_h = p->rb;
+      p->gx = (int)cdiv(cdiv((unsigned)dw, 64), 4); p->gy = (int)cdiv((unsigned)dh, (unsigned)p->rb);
+      return;
+    }
+  }
+  // integer reductions (one phase for the whole frame): the barrier-free kernel with scalar weights; every other ratio keeps the LDS window
+  if (channels == 4 && t->has_gather && !no_pairs && (x_step & 0xFFFF) == 0 && (y_step & 0xFFFF) == 0) {
+    p->path = LGPU_PB_PATH_GATHER; p->np = (n_eff + 1) / 2; p->opq = c.opaque; p->epi = c.epi; p->tile_h = 4;
+    return;
+  }
+  if (t->has_pairs && !no_pairs) {
+    // pairs per window row: the span of 64 destination pixels' first taps, the taps of the last one (padded to whole groups of four pairs), one pair of alignment slack
+    const int wpairs = ((int)((((63LL * x_step + 65535) >> 16) + 1) / 2) + 4 * t->nq + 3 + 3) & ~3;       // whole quads of pairs, and wx0 is rounded down to a multiple of 4 in the kernel
+    const size_t lds_cap = 24 * 1024;     // 6 workgroups per CU: the per-lane weight loads want occupancy more than the window wants rows (profiles/r03/pb_pairs_lds_sweep.txt)
+    for (int th = 16; th >= 1; th >>= 1) {
+      const int wh = (int)(((long long)(th - 1) * y_step + 65535) >> 16) + ny_eff + 1;
+      if ((size_t)wpairs * wh * 16 <= lds_cap) { p->tile_h = th; p->win_h = wh; break; }
+    }
+    if (p->tile_h) {
+      p->path = LGPU_PB_PATH_PAIRS; p->ch = channels; p->opq = channels == 4 && c.opaque; p->epi = c.epi;
+      p->win_w = wpairs; p->nq = t->nq; p->lds = (int)((size_t)wpairs * p->win_h * 16);
+      p->tiles_x = (int)cdiv((unsigned)dw, 64); p->tiles_y = (int)cdiv((unsigned)dh, (unsigned)p->tile_h);
+      p->gx = p->tiles_x; p->gy = p->tiles_y;
+      // Tile order.  Counters on 4K -> 1706x960 (profiles/r06/fetch_size_calibration.md: FETCH_SIZE reports HALF of what is read for this kernel's 640-byte window
+      // segments exactly as for a full-wave stream -- 128-byte requests) put its L2 -> fabric reads at 2.0 x the source: with the tiles of a row dealt round robin to
+      // the XCDs, the window rows that vertically neighbouring tiles share (5 of 14) are fetched by another XCD's L2 again.  So every XCD takes a
+      // contiguous run of the row-major tile sequence.
+      if ((unsigned)p->tiles_x * (unsigned)p->tiles_y >= 64) { p->per_xcd = (int)cdiv((unsigned)p->tiles_x * (unsigned)p->tiles_y, 8u); p->gx = 8 * p->per_xcd; p->gy = 1; }
+      // the instantiation: pairs per tap row at compile time up to four (0: any count); the short filters also with their tap rows at compile time, and those
+      // again for tiles of at most four rows (PRE: one destination row per wave)
+      const int np = (n_eff + 2) / 2, ny = ny_eff;
+      const bool fixed = (np == 2 && ny == 2) || (np == 2 && ny == 3) || (np == 3 && ny == 3) || (np == 3 && ny == 4) || (np == 3 && ny == 5) || (np == 4 && ny == 6);
+      p->np = np <= 4 ? np : 0; p->ny = fixed ? ny : 0; p->pre = fixed && p->tile_h <= 4;
+      return;
+    }
+  }
+  if (c.epi) { p->path = LGPU_PB_PATH_NOT_FUSED; return; }
+  p->win_w = (int)((63LL * x_step + 65535) >> 16) + t->n_x;
+  for (int th = 16; th >= 1; th >>= 1) {
+    const int wh = (int)(((long long)(th - 1) * y_step + 65535) >> 16) + t->n_y;
+    if ((size_t)p->win_w * wh * 4 <= 48 * 1024) { p->tile_h = th; p->win_h = wh; break; }
+  }
+  p->ch = channels;
+  if (p->tile_h) {
+    p->path = LGPU_PB_PATH_WINDOW; p->uniform = (x_step & 0xFFFF) == 0;
+    p->gy = (int)cdiv((unsigned)dh, (unsigned)p->tile_h); p->lds = (int)((size_t)p->win_w * p->win_h * 4);
+  } else p->path = LGPU_PB_PATH_DIRECT;
+}
+
+// what a scale demands of its numbers (the frames themselves are pb_scale_n's to look at): pb_scale_n's and lgpu_debug_pixbuf_plan's LGPU_E_BADARG
+static int pb_check_call(int irow, int sw, int sh, int orow, int dw, int dh, int channels, int interp, uintptr_t sbits, uintptr_t dbits) {
+  LGPU_REQUIRE(sw > 0 && sh > 0 && dw > 0 && dh > 0, "empty geometry");
+  LGPU_REQUIRE(channels == 3 || channels == 4, "channels must be 3 (no alpha) or 4 (alpha)");
+  interp &= ~LGPU_INTERP_OPAQUE;
+  LGPU_REQUIRE(interp == 0 || interp == 2 || interp == 3, "interp must be 0 (NEAREST), 2 (BILINEAR) or 3 (HYPER)");
+  LGPU_REQUIRE(irow >= sw * channels && orow >= dw * channels, "rowstride smaller than a row");
+  LGPU_REQUIRE(sw < 32768 && sh < 32768 && dw < 32768 && dh < 32768, "frame sides must stay below 32768 (16.16 positions)");
+  if (channels == 4) LGPU_REQUIRE(((sbits | dbits | (unsigned)irow | (unsigned)orow) & 3) == 0, "4-byte pixels must be 4-byte aligned");
+  return LGPU_OK;
+}
+
+// a plan the launch has no kernel for is an error, never another kernel
+static int pb_no_kernel(const char *what, const lgpu_pixbuf_plan &p) {
+  set_error("%s: the plan (path %d, ch %d, np %d, ny %d, pre %d) names no instantiation", what, p.path, p.ch, p.np, p.ny, p.pre);
+  return LGPU_E_HIP;
+}
+
 // n frames of one geometry in one launch of whichever kernel the geometry selects (n == 1: lgpu_pixbuf_scale)
 // epi: the chain's last stages in the store (PbEpi) -- served by the pair, gather and enlargement kernels; PB_NOT_FUSED (nothing launched) where another kernel has the ratio
 static int pb_scale_n(const uint8_t *const *srcs, uint8_t *const *dsts, int n, int irow, int sw, int sh, int orow, int dw, int dh, int channels, int interp, void *stream,
@@ -2433,7 +2562,6 @@ static int pb_scale_n(const uint8_t *const *srcs, uint8_t *const *dsts, int n, i
   int rc = ensure_init();
   if (rc) return rc;
   LGPU_REQUIRE(srcs && dsts && n >= 1 && n <= LGPU_CHAIN_MAX_TRACKS, "1..64 frames");
-  LGPU_REQUIRE(sw > 0 && sh > 0 && dw > 0 && dh > 0, "empty geometry");
   PbFrames F;
   uintptr_t sbits = 0, dbits = 0;                       // alignment of the launch = of its least aligned frame
   for (int i = 0; i < n; i++) {
@@ -2444,192 +2572,150 @@ static int pb_scale_n(const uint8_t *const *srcs, uint8_t *const *dsts, int n, i
   }
   const uint8_t *const src_d = srcs[0];
   uint8_t *const dst_d = dsts[0];
-  LGPU_REQUIRE(channels == 3 || channels == 4, "channels must be 3 (no alpha) or 4 (alpha)");
+  if ((rc = pb_check_call(irow, sw, sh, orow, dw, dh, channels, interp, sbits, dbits))) return rc;
   const bool opaque = (interp & LGPU_INTERP_OPAQUE) != 0;          // the caller's word that every source pixel has alpha 255: the pair kernel's lighter form (k_pb_pairs<.., OPQ>)
   interp &= ~LGPU_INTERP_OPAQUE;
-  LGPU_REQUIRE(interp == 0 || interp == 2 || interp == 3, "interp must be 0 (NEAREST), 2 (BILINEAR) or 3 (HYPER)");
-  LGPU_REQUIRE(irow >= sw * channels && orow >= dw * channels, "rowstride smaller than a row");
-  LGPU_REQUIRE(sw < 32768 && sh < 32768 && dw < 32768 && dh < 32768, "frame sides must stay below 32768 (16.16 positions)");
-  if (channels == 4) LGPU_REQUIRE(((sbits | dbits | (unsigned)irow | (unsigned)orow) & 3) == 0, "4-byte pixels must be 4-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  if (epi && (channels != 4 || interp == 0 || (dw == sw && dh == sh))) return PB_NOT_FUSED;
-  if (dw == sw && dh == sh) {                           // gdk_pixbuf_scale_simple: a plain copy
+  PbPin pin;
+  const PbCall call = {sw, sh, dw, dh, channels, interp, opaque, epi != nullptr, irow, orow, sbits, dbits, n};
+  lgpu_pixbuf_plan p;
+  pb_plan(call, [&](const PbTable **t) { const int trc = pb_table(interp, sw, sh, dw, dh, st, &pin); *t = pin.t; return trc; }, &p);
+  const PbTable *t = pin.t;
+  const int x_step = p.x_step, y_step = p.y_step;
+  const dim3 grid((unsigned)p.gx, (unsigned)p.gy, (unsigned)p.gz), block(256);
+  switch (p.path) {
+  case LGPU_PB_PATH_NOT_FUSED: return PB_NOT_FUSED;
+  case LGPU_PB_PATH_REFUSED:
+    if (x_step == 0 || y_step == 0) set_error("lgpu_pixbuf_scale: enlargement beyond 65536x");
+    else if (p.rc == LGPU_E_UNSUPPORTED) set_error("lgpu_pixbuf_scale: %dx%d -> %dx%d needs %d x %d taps; the library's two-step scaler is not covered", sw, sh, dw, dh, p.n_x, p.n_y);
+    return p.rc;
+  case LGPU_PB_PATH_COPY:
     for (int i = 0; i < n && !rc; i++) rc = lgpu_copy_rows(dsts[i], orow, srcs[i], irow, sw * channels, sh, stream);
     return rc;
-  }
-  const double scale_x = (double)dw / sw, scale_y = (double)dh / sh;
-  const int x_step = (int)(65536 / scale_x), y_step = (int)(65536 / scale_y);
-  if (x_step == 0 || y_step == 0) { set_error("lgpu_pixbuf_scale: enlargement beyond 65536x"); return LGPU_E_UNSUPPORTED; }
-  const dim3 grid(cdiv((unsigned)dw, 64), cdiv((unsigned)dh, 4), (unsigned)n), block(256);
-  if (interp == 0) {
-    if (channels == 4) hipLaunchKernelGGL(k_pb_nearest<4>, grid, block, 0, st, F, irow, sw, sh, orow, dw, dh, x_step, y_step);
+  case LGPU_PB_PATH_NEAREST:
+    if (p.ch == 4) hipLaunchKernelGGL(k_pb_nearest<4>, grid, block, 0, st, F, irow, sw, sh, orow, dw, dh, x_step, y_step);
     else hipLaunchKernelGGL(k_pb_nearest<3>, grid, block, 0, st, F, irow, sw, sh, orow, dw, dh, x_step, y_step);
-    LGPU_CHECK_LAUNCH();
-    return LGPU_OK;
-  }
-  PbPin pin;
-  rc = pb_table(interp, sw, sh, dw, dh, st, &pin);
-  const PbTable *t = pin.t;
-  if (rc) {
-    if (rc == LGPU_E_UNSUPPORTED) set_error("lgpu_pixbuf_scale: %dx%d -> %dx%d needs %d x %d taps; the library's two-step scaler is not covered", sw, sh, dw, dh, t->n_x, t->n_y);
-    return rc;
-  }
-  if (!epi && channels == 4 && dw == 2 * sw && dh == 2 * sh && (sw & 1) == 0 && ((sbits | (unsigned)irow) & 7) == 0 && ((dbits | (unsigned)orow) & 15) == 0 &&
-      pb_double_ok(t, x_step, y_step)) {
+    break;
+  case LGPU_PB_PATH_DOUBLE: {
     PbHalfArgs h;
     h.sw = sw; h.sh = sh; h.irow = irow; h.dw = dw; h.dh = dh; h.orow = orow;
-    h.strips = (int)cdiv((unsigned)sw, 124); h.cgroups = (h.strips + 3) / 4;
-    h.th = 3;                      // measured (1080p -> 4K): 16.5 us at 2-3 source rows per band, 18.2 us at 4, 22.8 at 8, 33.4 at 16, 52.7 at 32 -- per-wave latency, as in k_pb_half
-    h.bands = (int)cdiv((unsigned)sh, (unsigned)h.th); h.ntracks = 1;
-    hipLaunchKernelGGL(k_pb_double<0>, dim3(8u * cdiv((unsigned)(h.cgroups * h.bands), 8u), 1, (unsigned)n), dim3(256), 0, st, h, F);
-    LGPU_CHECK_LAUNCH();
-    return LGPU_OK;
+    h.strips = p.strips; h.cgroups = p.cgroups; h.th = p.tile_h; h.bands = p.bands; h.ntracks = 1;
+    hipLaunchKernelGGL(k_pb_double<0>, grid, block, 0, st, h, F);
+    break;
   }
-  if (channels == 3 && sw == 2 * dw && sh == 2 * dh && (sw & 7) == 0 && ((sbits | dbits | (unsigned)irow | (unsigned)orow) & 3) == 0) {
+  case LGPU_PB_PATH_HALF3: {
     PbHalfArgs h;
-    // the same table check as the 4-byte kernel (alignment arguments that always pass: this kernel's own are checked above)
-    if (pb_half_ok(t, interp, sw, sh, dw, dh, 0, 0, &h.hyper, &h.ashift)) {
-      h.sw = sw; h.sh = sh; h.irow = irow; h.dw = dw; h.dh = dh; h.orow = orow;
-      h.strips = (int)cdiv((unsigned)dw, 120); h.cgroups = (h.strips + 3) / 4; h.th = 6; h.bands = (int)cdiv((unsigned)dh, 6u); h.ntracks = 1;
-      const dim3 g3(8u * cdiv((unsigned)(h.cgroups * h.bands), 8u), 1, (unsigned)n);
-      if (h.hyper) hipLaunchKernelGGL(k_pb_half3<1>, g3, dim3(256), 0, st, h, F);
-      else hipLaunchKernelGGL(k_pb_half3<0>, g3, dim3(256), 0, st, h, F);
-      LGPU_CHECK_LAUNCH();
-      return LGPU_OK;
-    }
+    h.hyper = p.hyper; h.ashift = p.hyper ? 8 : 2;
+    h.sw = sw; h.sh = sh; h.irow = irow; h.dw = dw; h.dh = dh; h.orow = orow;
+    h.strips = p.strips; h.cgroups = p.cgroups; h.th = p.tile_h; h.bands = p.bands; h.ntracks = 1;
+    if (p.hyper) hipLaunchKernelGGL(k_pb_half3<1>, grid, block, 0, st, h, F);
+    else hipLaunchKernelGGL(k_pb_half3<0>, grid, block, 0, st, h, F);
+    break;
   }
-  if (channels == 4 && !epi) {
+  case LGPU_PB_PATH_HALF: {
     PbHalfArgs h;
-    if ((long long)sh * irow < (1ll << 31) && (long long)dh * orow < (1ll << 31) &&        // 32-bit buffer offsets in k_pb_half (see pb_chain_half)
-        pb_half_ok(t, interp, sw, sh, dw, dh, sbits | (uintptr_t)irow, dbits | (uintptr_t)orow, &h.hyper, &h.ashift)) {
-      h.sw = sw; h.sh = sh; h.irow = irow; h.dw = dw; h.dh = dh; h.orow = orow;
-      h.swap_rb = 0; h.blend = 0; h.irow2 = 0; h.use_lut = 0; h.bf = 0; h.bf_d = nullptr; h.nt_out = 0; h.row_major = tune(TUNE_PBH_ORDER) >= 0 && tune(TUNE_PBH_ORDER) <= 2 ? tune(TUNE_PBH_ORDER) : 1; h.bgroup = tune(TUNE_PBH_GROUP) >= 1 && tune(TUNE_PBH_GROUP) <= 4096 ? tune(TUNE_PBH_GROUP) : 0;
-      pb_half_geometry(&h, n);
-      if (tune(TUNE_PBH_ORDER) < 0 && (long long)h.cgroups * h.bands * n > (long long)device_cus() * 8) h.row_major = 2;      // more than one generation: the chain's sweep order (pb_chain_half)
-      if (h.bgroup <= 0) h.bgroup = (h.bands % 8 == 0) ? h.bands / 8 : 1;
-      PbTracks T;
-      for (int i = 0; i < n; i++) { T.src[i] = srcs[i]; T.l2[i] = nullptr; T.dst[i] = dsts[i]; }
-      h.kscale = nullptr; h.cw = h.ch = h.ox = h.oy = 0; h.bar_blocks = 0; h.bar_first = 0; h.main_blocks = (int)pb_half_grid(h);
-      if (h.aligned) {
-        if (h.hyper) hipLaunchKernelGGL((k_pb_half<0, 1, 0, 1>), dim3(pb_half_grid(h)), dim3(256), 0, st, h, T, pack_lut(nullptr));
-        else hipLaunchKernelGGL((k_pb_half<0, 0, 0, 1>), dim3(pb_half_grid(h)), dim3(256), 0, st, h, T, pack_lut(nullptr));
-      } else if (h.hyper) hipLaunchKernelGGL((k_pb_half<0, 1, 0>), dim3(pb_half_grid(h)), dim3(256), 0, st, h, T, pack_lut(nullptr));
-      else hipLaunchKernelGGL((k_pb_half<0, 0, 0>), dim3(pb_half_grid(h)), dim3(256), 0, st, h, T, pack_lut(nullptr));
-      LGPU_CHECK_LAUNCH();
-      return LGPU_OK;
-    }
+    h.hyper = p.hyper; h.ashift = p.hyper ? 8 : 2;
+    h.sw = sw; h.sh = sh; h.irow = irow; h.dw = dw; h.dh = dh; h.orow = orow;
+    h.swap_rb = 0; h.blend = 0; h.irow2 = 0; h.use_lut = 0; h.bf = 0; h.bf_d = nullptr; h.nt_out = 0; h.row_major = tune(TUNE_PBH_ORDER) >= 0 && tune(TUNE_PBH_ORDER) <= 2 ? tune(TUNE_PBH_ORDER) : 1; h.bgroup = tune(TUNE_PBH_GROUP) >= 1 && tune(TUNE_PBH_GROUP) <= 4096 ? tune(TUNE_PBH_GROUP) : 0;
+    pb_half_geometry(&h, n);             // h.aligned: pb_half_aligned(0, 0), as the plan has it
+    if (tune(TUNE_PBH_ORDER) < 0 && (long long)h.cgroups * h.bands * n > (long long)device_cus() * 8) h.row_major = 2;      // more than one generation: the chain's sweep order (pb_chain_half)
+    if (h.bgroup <= 0) h.bgroup = (h.bands % 8 == 0) ? h.bands / 8 : 1;
+    PbTracks T;
+    for (int i = 0; i < n; i++) { T.src[i] = srcs[i]; T.l2[i] = nullptr; T.dst[i] = dsts[i]; }
+    h.kscale = nullptr; h.cw = h.ch = h.ox = h.oy = 0; h.bar_blocks = 0; h.bar_first = 0; h.main_blocks = (int)pb_half_grid(h);
+    if (h.aligned != p.aligned) { set_error("lgpu_pixbuf_scale: k_pb_half's strip form differs from the plan's"); return LGPU_E_HIP; }
+    if (p.aligned) {
+      if (p.hyper) hipLaunchKernelGGL((k_pb_half<0, 1, 0, 1>), dim3(pb_half_grid(h)), dim3(256), 0, st, h, T, pack_lut(nullptr));
+      else hipLaunchKernelGGL((k_pb_half<0, 0, 0, 1>), dim3(pb_half_grid(h)), dim3(256), 0, st, h, T, pack_lut(nullptr));
+    } else if (p.hyper) hipLaunchKernelGGL((k_pb_half<0, 1, 0>), dim3(pb_half_grid(h)), dim3(256), 0, st, h, T, pack_lut(nullptr));
+    else hipLaunchKernelGGL((k_pb_half<0, 0, 0>), dim3(pb_half_grid(h)), dim3(256), 0, st, h, T, pack_lut(nullptr));
+    break;
   }
-  const bool no_pairs = tune_on(TUNE_PB_NO_PAIRS);        // tests: the one-tap-per-operation kernels at any ratio
-  // both sides enlarged: the register-window walk
-  if (channels == 4 && t->gpairs_d && !no_pairs && x_step <= 65536 && y_step <= 65536) {
-    const int unp = (t->tx1 - t->tx0 + 1) / 2, uny = t->ty1 - t->ty0;
-    if (unp >= 1 && unp <= 2 && uny >= 1 && uny <= 4) {
-      PbUpArgs ua;
-      ua.src = src_d; ua.dst = dst_d; ua.irow = irow; ua.orow = orow; ua.sw = sw; ua.sh = sh; ua.dw = dw; ua.dh = dh;
-      ua.x_step = x_step; ua.y_step = y_step; ua.xoff = t->xoff; ua.yoff = t->yoff; ua.tx0 = t->tx0; ua.ty0 = t->ty0;
-      ua.rb = (long long)dw * dh >= 6000000 ? 8 : 6;      // per-wave time rules (profiles/r03/pb_up_ab.txt: 720p -> 1080p 11.6 us at 6 rows per band, 15.3 at 16, 38 at 64)
-      { const int v = tune(TUNE_PB_UP_RB); if (v >= 1 && v <= 4096) ua.rb = v; }      // tuning probe
-      const dim3 gu(cdiv(cdiv((unsigned)dw, 64), 4), cdiv((unsigned)dh, (unsigned)ua.rb), (unsigned)n);
-      const uint32_t *gp = t->gpairs_d;
-      if (opaque && (rc = pb_opaque_check())) return rc;
-#define PB_UP(NP_, NY_) { if (epi) { if (opaque) hipLaunchKernelGGL((k_pb_up<NP_, NY_, 1, PbEpi>), gu, block, 0, st, ua, gp, F, *epi); else hipLaunchKernelGGL((k_pb_up<NP_, NY_, 0, PbEpi>), gu, block, 0, st, ua, gp, F, *epi); } \
-                          else if (opaque) hipLaunchKernelGGL((k_pb_up<NP_, NY_, 1, PbNoEpi>), gu, block, 0, st, ua, gp, F, PbNoEpi{}); else hipLaunchKernelGGL((k_pb_up<NP_, NY_, 0, PbNoEpi>), gu, block, 0, st, ua, gp, F, PbNoEpi{}); }
-      if (unp == 1) { if (uny == 1) PB_UP(1, 1) else if (uny == 2) PB_UP(1, 2) else if (uny == 3) PB_UP(1, 3) else PB_UP(1, 4) }
-      else { if (uny == 1) PB_UP(2, 1) else if (uny == 2) PB_UP(2, 2) else if (uny == 3) PB_UP(2, 3) else PB_UP(2, 4) }
+  case LGPU_PB_PATH_UP: {
+    PbUpArgs ua;
+    ua.src = src_d; ua.dst = dst_d; ua.irow = irow; ua.orow = orow; ua.sw = sw; ua.sh = sh; ua.dw = dw; ua.dh = dh;
+    ua.x_step = x_step; ua.y_step = y_step; ua.xoff = t->xoff; ua.yoff = t->yoff; ua.tx0 = p.tx0; ua.ty0 = p.ty0;
+    ua.rb = p.rb;
+    const uint32_t *gp = t->gpairs_d;
+    if (p.opq && (rc = pb_opaque_check())) return rc;
+#define PB_UP(NP_, NY_) { if (p.epi) { if (p.opq) hipLaunchKernelGGL((k_pb_up<NP_, NY_, 1, PbEpi>), grid, block, 0, st, ua, gp, F, *epi); else hipLaunchKernelGGL((k_pb_up<NP_, NY_, 0, PbEpi>), grid, block, 0, st, ua, gp, F, *epi); } \
+                          else if (p.opq) hipLaunchKernelGGL((k_pb_up<NP_, NY_, 1, PbNoEpi>), grid, block, 0, st, ua, gp, F, PbNoEpi{}); else hipLaunchKernelGGL((k_pb_up<NP_, NY_, 0, PbNoEpi>), grid, block, 0, st, ua, gp, F, PbNoEpi{}); }
+    const int form = p.np * 16 + p.ny;
+    if (form == 0x11) PB_UP(1, 1) else if (form == 0x12) PB_UP(1, 2) else if (form == 0x23) PB_UP(2, 3) else if (form == 0x24) PB_UP(2, 4)
+    else return pb_no_kernel("k_pb_up", p);
 #undef PB_UP
-      LGPU_CHECK_LAUNCH();
-      return LGPU_OK;
-    }
+    break;
   }
-  // integer reductions (one phase for the whole frame): the barrier-free kernel with scalar weights; every other ratio keeps the LDS window
-  if (channels == 4 && t->gpairs_d && !no_pairs && (x_step & 0xFFFF) == 0 && (y_step & 0xFFFF) == 0) {
+  case LGPU_PB_PATH_GATHER: {
     PbGatherArgs ga;
     ga.src = src_d; ga.dst = dst_d; ga.irow = irow; ga.orow = orow; ga.sw = sw; ga.sh = sh; ga.dw = dw; ga.dh = dh;
-    ga.x_step = x_step; ga.y_step = y_step; ga.xoff = t->xoff; ga.yoff = t->yoff; ga.tx0 = t->tx0; ga.ty0 = t->ty0; ga.ny_eff = t->ty1 - t->ty0;
-    const int gnp = (t->tx1 - t->tx0 + 1) / 2;
+    ga.x_step = x_step; ga.y_step = y_step; ga.xoff = t->xoff; ga.yoff = t->yoff; ga.tx0 = p.tx0; ga.ty0 = p.ty0; ga.ny_eff = p.ty1 - p.ty0;
     const uint32_t *gp = t->gpairs_d;
-    if (opaque && (rc = pb_opaque_check())) return rc;
-#define PB_GATHER(NP_) { if (epi) { if (opaque) hipLaunchKernelGGL((k_pb_gather<NP_, PbEpi, 1>), grid, block, 0, st, ga, gp, F, *epi); else hipLaunchKernelGGL((k_pb_gather<NP_, PbEpi, 0>), grid, block, 0, st, ga, gp, F, *epi); } \
-                         else if (opaque) hipLaunchKernelGGL((k_pb_gather<NP_, PbNoEpi, 1>), grid, block, 0, st, ga, gp, F, PbNoEpi{}); else hipLaunchKernelGGL((k_pb_gather<NP_, PbNoEpi, 0>), grid, block, 0, st, ga, gp, F, PbNoEpi{}); }
-    if (gnp == 1) PB_GATHER(1) else if (gnp == 2) PB_GATHER(2) else if (gnp == 3) PB_GATHER(3) else PB_GATHER(4)
+    if (p.opq && (rc = pb_opaque_check())) return rc;
+#define PB_GATHER(NP_) { if (p.epi) { if (p.opq) hipLaunchKernelGGL((k_pb_gather<NP_, PbEpi, 1>), grid, block, 0, st, ga, gp, F, *epi); else hipLaunchKernelGGL((k_pb_gather<NP_, PbEpi, 0>), grid, block, 0, st, ga, gp, F, *epi); } \
+                         else if (p.opq) hipLaunchKernelGGL((k_pb_gather<NP_, PbNoEpi, 1>), grid, block, 0, st, ga, gp, F, PbNoEpi{}); else hipLaunchKernelGGL((k_pb_gather<NP_, PbNoEpi, 0>), grid, block, 0, st, ga, gp, F, PbNoEpi{}); }
+    if (p.np == 1) PB_GATHER(1) else if (p.np == 2) PB_GATHER(2) else if (p.np == 3) PB_GATHER(3) else if (p.np == 4) PB_GATHER(4)
+    else return pb_no_kernel("k_pb_gather", p);
 #undef PB_GATHER
-    LGPU_CHECK_LAUNCH();
-    return LGPU_OK;
+    break;
   }
-  if (t->pairs_d && !no_pairs) {
+  case LGPU_PB_PATH_PAIRS: {
     PbPairArgs pa;
     pa.src = src_d; pa.dst = dst_d; pa.irow = irow; pa.orow = orow; pa.sw = sw; pa.sh = sh; pa.dw = dw; pa.dh = dh;
-    pa.x_step = x_step; pa.y_step = y_step; pa.xoff = t->xoff; pa.yoff = t->yoff; pa.n_x = t->n_x; pa.tx0 = t->tx0; pa.ty0 = t->ty0; pa.ny_eff = t->ty1 - t->ty0; pa.nq = t->nq;
+    pa.x_step = x_step; pa.y_step = y_step; pa.xoff = t->xoff; pa.yoff = t->yoff; pa.n_x = p.n_x; pa.tx0 = p.tx0; pa.ty0 = p.ty0; pa.ny_eff = p.ty1 - p.ty0; pa.nq = p.nq;
     pa.pairs = t->pairs_d;
-    pa.rnd = (t->n_x == 2 && t->n_y == 2 && channels == 3) ? 0x8000u : 0xffffu;
-    // pairs per window row: the span of 64 destination pixels' first taps, the taps of the last one (padded to whole groups of four pairs), one pair of alignment slack
-    pa.wpairs = ((int)((((63LL * x_step + 65535) >> 16) + 1) / 2) + 4 * t->nq + 3 + 3) & ~3;       // whole quads of pairs, and wx0 is rounded down to a multiple of 4 below
-
-    pa.tile_h = 0;
-    const size_t lds_cap = 24 * 1024;     // 6 workgroups per CU: the per-lane weight loads want occupancy more than the window wants rows (profiles/r03/pb_pairs_lds_sweep.txt)
-    for (int th = 16; th >= 1; th >>= 1) {
-      const int wh = (int)(((long long)(th - 1) * y_step + 65535) >> 16) + pa.ny_eff + 1;
-      if ((size_t)pa.wpairs * wh * 16 <= lds_cap) { pa.tile_h = th; pa.win_h = wh; break; }
-    }
-    if (pa.tile_h) {
-      dim3 g(cdiv((unsigned)dw, 64), cdiv((unsigned)dh, (unsigned)pa.tile_h), (unsigned)n);
-      pa.gx = (int)g.x; pa.gy = (int)g.y; pa.per_xcd = 0;
-      // Tile order.  Counters on 4K -> 1706x960 (profiles/r06/fetch_size_calibration.md: FETCH_SIZE reports HALF of what is read for this kernel's 640-byte window
-      // segments exactly as for a full-wave stream -- 128-byte requests) put its L2 -> fabric reads at 2.0 x the source: with the tiles of a row dealt round robin to
-      // the XCDs, the window rows that vertically neighbouring tiles share (5 of 14) are fetched by another XCD's L2 again.  So every XCD takes a
-      // contiguous run of the row-major tile sequence.
-      if (g.x * g.y >= 64) { pa.per_xcd = (int)cdiv(g.x * g.y, 8u); g = dim3(8u * (unsigned)pa.per_xcd, 1, (unsigned)n); }
-      const size_t lds = (size_t)pa.wpairs * pa.win_h * 16;
-      const int np = (t->tx1 - t->tx0 + 2) / 2;
-#define PB_PRE(CHN, NP_, NY_, OQ, EAT, EAV) { if (pa.tile_h <= 4) hipLaunchKernelGGL((k_pb_pairs<CHN, NP_, NY_, 1, OQ, EAT>), g, block, lds, st, pa, F, EAV); else hipLaunchKernelGGL((k_pb_pairs<CHN, NP_, NY_, 0, OQ, EAT>), g, block, lds, st, pa, F, EAV); }
-#define PB_PAIRS(CHN, OQ, EAT, EAV)                                                                                       \
-      { const int ny = t->ty1 - t->ty0;                                                                                   \
-        if (np == 2 && ny == 2) PB_PRE(CHN, 2, 2, OQ, EAT, EAV)                                                              \
-        else if (np == 2 && ny == 3) PB_PRE(CHN, 2, 3, OQ, EAT, EAV)                                                         \
-        else if (np == 3 && ny == 3) PB_PRE(CHN, 3, 3, OQ, EAT, EAV)                                                         \
-        else if (np == 3 && ny == 4) PB_PRE(CHN, 3, 4, OQ, EAT, EAV)                                                         \
-        else if (np == 3 && ny == 5) PB_PRE(CHN, 3, 5, OQ, EAT, EAV)                                                         \
-        else if (np == 4 && ny == 6) PB_PRE(CHN, 4, 6, OQ, EAT, EAV)                                                         \
-        else if (np == 1) hipLaunchKernelGGL((k_pb_pairs<CHN, 1, 0, 0, OQ, EAT>), g, block, lds, st, pa, F, EAV);            \
-        else if (np == 2) hipLaunchKernelGGL((k_pb_pairs<CHN, 2, 0, 0, OQ, EAT>), g, block, lds, st, pa, F, EAV);            \
-        else if (np == 3) hipLaunchKernelGGL((k_pb_pairs<CHN, 3, 0, 0, OQ, EAT>), g, block, lds, st, pa, F, EAV);            \
-        else if (np == 4) hipLaunchKernelGGL((k_pb_pairs<CHN, 4, 0, 0, OQ, EAT>), g, block, lds, st, pa, F, EAV);            \
-        else hipLaunchKernelGGL((k_pb_pairs<CHN, 0, 0, 0, OQ, EAT>), g, block, lds, st, pa, F, EAV); }
-      if (channels == 4 && opaque && (rc = pb_opaque_check())) return rc;
-      if (epi) { if (opaque) { PB_PAIRS(4, 1, PbEpi, *epi) } else { PB_PAIRS(4, 0, PbEpi, *epi) } }
-      else if (channels == 4 && opaque) { PB_PAIRS(4, 1, PbNoEpi, PbNoEpi{}) } else if (channels == 4) { PB_PAIRS(4, 0, PbNoEpi, PbNoEpi{}) } else { PB_PAIRS(3, 0, PbNoEpi, PbNoEpi{}) }
+    pa.rnd = p.rnd;
+    pa.wpairs = p.win_w; pa.tile_h = p.tile_h; pa.win_h = p.win_h;
+    pa.gx = p.tiles_x; pa.gy = p.tiles_y; pa.per_xcd = p.per_xcd;
+    const size_t lds = (size_t)p.lds;
+#define PB_PRE(CHN, NP_, NY_, OQ, EAT, EAV) { if (p.pre) hipLaunchKernelGGL((k_pb_pairs<CHN, NP_, NY_, 1, OQ, EAT>), grid, block, lds, st, pa, F, EAV); else hipLaunchKernelGGL((k_pb_pairs<CHN, NP_, NY_, 0, OQ, EAT>), grid, block, lds, st, pa, F, EAV); }
+#define PB_PAIRS(CHN, OQ, EAT, EAV)                                                                                        \
+      { const int form = p.np * 16 + p.ny;                                                                                 \
+        if (form == 0x22) PB_PRE(CHN, 2, 2, OQ, EAT, EAV)                                                                  \
+        else if (form == 0x23) PB_PRE(CHN, 2, 3, OQ, EAT, EAV)                                                             \
+        else if (form == 0x33) PB_PRE(CHN, 3, 3, OQ, EAT, EAV)                                                             \
+        else if (form == 0x34) PB_PRE(CHN, 3, 4, OQ, EAT, EAV)                                                             \
+        else if (form == 0x35) PB_PRE(CHN, 3, 5, OQ, EAT, EAV)                                                             \
+        else if (form == 0x46) PB_PRE(CHN, 4, 6, OQ, EAT, EAV)                                                             \
+        else if (p.pre) return pb_no_kernel("k_pb_pairs", p);                                                              \
+        else if (form == 0x10) hipLaunchKernelGGL((k_pb_pairs<CHN, 1, 0, 0, OQ, EAT>), grid, block, lds, st, pa, F, EAV);  \
+        else if (form == 0x20) hipLaunchKernelGGL((k_pb_pairs<CHN, 2, 0, 0, OQ, EAT>), grid, block, lds, st, pa, F, EAV);  \
+        else if (form == 0x30) hipLaunchKernelGGL((k_pb_pairs<CHN, 3, 0, 0, OQ, EAT>), grid, block, lds, st, pa, F, EAV);  \
+        else if (form == 0x40) hipLaunchKernelGGL((k_pb_pairs<CHN, 4, 0, 0, OQ, EAT>), grid, block, lds, st, pa, F, EAV);  \
+        else if (form == 0x00) hipLaunchKernelGGL((k_pb_pairs<CHN, 0, 0, 0, OQ, EAT>), grid, block, lds, st, pa, F, EAV);  \
+        else return pb_no_kernel("k_pb_pairs", p); }
+    if (p.opq && (rc = pb_opaque_check())) return rc;
+    if (p.epi) { if (p.opq) { PB_PAIRS(4, 1, PbEpi, *epi) } else { PB_PAIRS(4, 0, PbEpi, *epi) } }
+    else if (p.ch == 4 && p.opq) { PB_PAIRS(4, 1, PbNoEpi, PbNoEpi{}) } else if (p.ch == 4) { PB_PAIRS(4, 0, PbNoEpi, PbNoEpi{}) } else { PB_PAIRS(3, 0, PbNoEpi, PbNoEpi{}) }
 #undef PB_PAIRS
 #undef PB_PRE
-      LGPU_CHECK_LAUNCH();
-      return LGPU_OK;
-    }
+    break;
   }
-  if (epi) return PB_NOT_FUSED;
-  PbArgs a;
-  a.src = src_d; a.dst = dst_d; a.irow = irow; a.orow = orow; a.sw = sw; a.sh = sh; a.dw = dw; a.dh = dh;
-  a.x_step = x_step; a.y_step = y_step; a.xoff = t->xoff; a.yoff = t->yoff; a.n_x = t->n_x; a.n_y = t->n_y; a.table = t->table_d;
-  a.rnd = (t->n_x == 2 && t->n_y == 2 && channels == 3) ? 0x8000u : 0xffffu;
-  pb_used_taps(t, x_step, y_step, dw, dh, &a);
-  a.win_w = (int)((63LL * x_step + 65535) >> 16) + t->n_x;
-  a.tile_h = 0;
-  for (int th = 16; th >= 1; th >>= 1) {
-    const int wh = (int)(((long long)(th - 1) * y_step + 65535) >> 16) + t->n_y;
-    if ((size_t)a.win_w * wh * 4 <= 48 * 1024) { a.tile_h = th; a.win_h = wh; break; }
-  }
-  const bool uniform = (x_step & 0xFFFF) == 0;
-  if (a.tile_h) {
-    const dim3 g(cdiv((unsigned)dw, 64), cdiv((unsigned)dh, (unsigned)a.tile_h), (unsigned)n);
-    const size_t lds = (size_t)a.win_w * a.win_h * 4;
-    if (channels == 4) {
-      if (uniform) hipLaunchKernelGGL((k_pb_window<4, 1>), g, block, lds, st, a, F);
-      else hipLaunchKernelGGL((k_pb_window<4, 0>), g, block, lds, st, a, F);
+  case LGPU_PB_PATH_WINDOW:
+  case LGPU_PB_PATH_DIRECT: {
+    PbArgs a;
+    a.src = src_d; a.dst = dst_d; a.irow = irow; a.orow = orow; a.sw = sw; a.sh = sh; a.dw = dw; a.dh = dh;
+    a.x_step = x_step; a.y_step = y_step; a.xoff = t->xoff; a.yoff = t->yoff; a.n_x = p.n_x; a.n_y = p.n_y; a.table = t->table_d;
+    a.rnd = p.rnd;
+    a.tx0 = p.tx0; a.tx1 = p.tx1; a.ty0 = p.ty0; a.ty1 = p.ty1;
+    a.win_w = p.win_w; a.tile_h = p.tile_h; a.win_h = p.win_h;
+    const size_t lds = (size_t)p.lds;
+    if (p.path == LGPU_PB_PATH_WINDOW) {
+      if (p.ch == 4) {
+        if (p.uniform) hipLaunchKernelGGL((k_pb_window<4, 1>), grid, block, lds, st, a, F);
+        else hipLaunchKernelGGL((k_pb_window<4, 0>), grid, block, lds, st, a, F);
+      } else {
+        if (p.uniform) hipLaunchKernelGGL((k_pb_window<3, 1>), grid, block, lds, st, a, F);
+        else hipLaunchKernelGGL((k_pb_window<3, 0>), grid, block, lds, st, a, F);
+      }
     } else {
-      if (uniform) hipLaunchKernelGGL((k_pb_window<3, 1>), g, block, lds, st, a, F);
-      else hipLaunchKernelGGL((k_pb_window<3, 0>), g, block, lds, st, a, F);
+      if (p.ch == 4) hipLaunchKernelGGL(k_pb_direct<4>, grid, block, 0, st, a, F);
+      else hipLaunchKernelGGL(k_pb_direct<3>, grid, block, 0, st, a, F);
     }
-  } else {
-    if (channels == 4) hipLaunchKernelGGL(k_pb_direct<4>, grid, block, 0, st, a, F);
-    else hipLaunchKernelGGL(k_pb_direct<3>, grid, block, 0, st, a, F);
+    break;
+  }
+  default:
+    return pb_no_kernel("lgpu_pixbuf_scale", p);
   }
   LGPU_CHECK_LAUNCH();
   return LGPU_OK;
@@ -2666,6 +2752,22 @@ extern "C" int lgpu_pixbuf_scale(const uint8_t *src_d, int irow, int sw, int sh,
 extern "C" int lgpu_pixbuf_scale_batch(const uint8_t *const *src_d, uint8_t *const *dst_d, int nframes, int irow, int sw, int sh, int orow, int dw, int dh, int channels,
                                        int interp, void *stream) {
   return pb_scale_n(src_d, dst_d, nframes, irow, sw, sh, orow, dw, dh, channels, interp, stream);
+}
+
+// the plan of a call on a host-built table: the same pb_plan as the launch
+extern "C" int lgpu_debug_pixbuf_plan(const lgpu_pixbuf_plan_query *q, lgpu_pixbuf_plan *out) {
+  LGPU_REQUIRE(q && out, "null query");
+  LGPU_REQUIRE(q->mode == LGPU_PB_PLAN_SCALE || q->mode == LGPU_PB_PLAN_CHAIN, "mode must be LGPU_PB_PLAN_*");
+  LGPU_REQUIRE(q->nframes >= 1 && q->nframes <= LGPU_CHAIN_MAX_TRACKS, "1..64 frames");
+  const int rc = pb_check_call(q->irow, q->sw, q->sh, q->orow, q->dw, q->dh, q->channels, q->interp, q->src_bits, q->dst_bits);
+  if (rc) return rc;
+  const bool opaque = (q->interp & LGPU_INTERP_OPAQUE) != 0;
+  const int interp = q->interp & ~LGPU_INTERP_OPAQUE;
+  LGPU_REQUIRE(q->mode == LGPU_PB_PLAN_SCALE || (q->channels == 4 && !(q->sw == q->dw && q->sh == q->dh)), "the chain scales 4-byte pixels and needs a resize stage");
+  const PbCall call = {q->sw, q->sh, q->dw, q->dh, q->channels, interp, opaque, q->mode == LGPU_PB_PLAN_CHAIN, q->irow, q->orow, q->src_bits, q->dst_bits, q->nframes};
+  PbTable t;
+  pb_plan(call, [&](const PbTable **tp) { *tp = &t; return pb_build(interp, q->sw, q->sh, q->dw, q->dh, &t, false); }, out);
+  return LGPU_OK;
 }
 
 // resize -> letterbox -> blend (-> gamma) as one call: BASELINE config 3's chain.  letterbox_layer (src/colourspace.c:15343-15567) centres the scaled frame on an

@@ -105,6 +105,24 @@ PLAN_RESIZE, PLAN_CHAIN, PLAN_CHAIN_BLUR = range(3)
 PLAN_PATHS = {1: "HALF8S", 2: "SEP2", 3: "SEP2P", 4: "SEP2P_MFMA", 5: "SEPARABLE", 6: "GENERIC", 7: "REFUSED"}      # LGPU_PATH_*
 
 
+class PixbufPlanQuery(ctypes.Structure):
+    """lgpu_pixbuf_plan_query"""
+    _fields_ = [("sw", ci), ("sh", ci), ("dw", ci), ("dh", ci), ("channels", ci), ("interp", ci), ("irow", ci), ("orow", ci),
+                ("src_bits", ctypes.c_uint), ("dst_bits", ctypes.c_uint), ("nframes", ci), ("mode", ci)]
+
+
+class PixbufPlan(ctypes.Structure):
+    """lgpu_pixbuf_plan"""
+    _fields_ = [(n, ci) for n in ("path", "rc", "ch", "np", "ny", "pre", "opq", "epi", "hyper", "aligned", "uniform", "tile_h", "win_h", "win_w", "lds",
+                                  "gx", "gy", "gz", "tiles_x", "tiles_y", "per_xcd", "strips", "cgroups", "bands", "rb", "x_step", "y_step",
+                                  "tx0", "tx1", "ty0", "ty1", "n_x", "n_y", "nq")] + [("rnd", ctypes.c_uint)]
+
+
+PB_PLAN_SCALE, PB_PLAN_CHAIN = range(2)
+PB_PLAN_PATHS = {1: "COPY", 2: "NEAREST", 3: "DOUBLE", 4: "HALF3", 5: "HALF", 6: "UP", 7: "GATHER", 8: "PAIRS", 9: "WINDOW", 10: "DIRECT",
+                 11: "NOT_FUSED", 12: "REFUSED"}      # LGPU_PB_PATH_*
+
+
 class FxFrame(ctypes.Structure):
     _fields_ = [("in0", vp * 4), ("in1", vp * 4), ("out", vp * 4)]
 
@@ -183,6 +201,7 @@ PROTOTYPES = {
     "lgpu_letterbox_bars": [vp, ci, ci, ci, ci, vp, ci, ci, ci, ci, vp],
     "lgpu_resize": [vp, ci, ci, ci, vp, ci, ci, ci, ci, ci, vp, vp],
     "lgpu_debug_resize_plan": [ctypes.POINTER(ResizePlanQuery), ctypes.POINTER(ResizePlan)],
+    "lgpu_debug_pixbuf_plan": [ctypes.POINTER(PixbufPlanQuery), ctypes.POINTER(PixbufPlan)],
     "lgpu_pixbuf_scale": [vp, ci, ci, ci, vp, ci, ci, ci, ci, ci, vp],
     "lgpu_swizzle_batch": [ci, ci, vp, ci, vp, ci, ci, ci, vp, ci, vp],
     "lgpu_gamma_apply_batch": [vp, ci, ci, ci, ci, ci, ci, ci, vp, ci, vp],

@@ -138,6 +138,20 @@ def pixbuf_scale(src, dst, sw, sh, dw, dh, channels=4, interp=3):
     lib.call("lgpu_pixbuf_scale", dptr(src), src.stride(0), sw, sh, dptr(dst), dst.stride(0), dw, dh, channels, interp, stream_ptr())
 
 
+def pixbuf_plan(sw, sh, dw, dh, channels=4, interp=3, irow=None, orow=None, src_bits=0, dst_bits=0, nframes=1, mode=lib.PB_PLAN_SCALE):
+    """lgpu_debug_pixbuf_plan: the kernel a gdk-pixbuf scale (or the fused chain's scale, mode PB_PLAN_CHAIN) of this geometry would launch, as a dict (path by
+    name); host only, no device needed.  irow / orow default to compact rows rounded up to 16 bytes; src_bits / dst_bits: the OR of the frames' addresses (only
+    the low four bits count); interp may carry LGPU_INTERP_OPAQUE"""
+    al = lambda n: (n + 15) // 16 * 16
+    q = lib.PixbufPlanQuery(sw, sh, dw, dh, channels, interp, al(sw * channels) if irow is None else irow, al(dw * channels) if orow is None else orow,
+                            src_bits & 15, dst_bits & 15, nframes, mode)
+    out = lib.PixbufPlan()
+    lib.call("lgpu_debug_pixbuf_plan", ctypes.byref(q), ctypes.byref(out))
+    d = {n: getattr(out, n) for n, _ in lib.PixbufPlan._fields_}
+    d["path"] = lib.PB_PLAN_PATHS[out.path]
+    return d
+
+
 def ptr_array(tensors):
     """host array of device pointers (what the *_batch entry points take)"""
     return (ctypes.c_void_p * len(tensors))(*[dptr(t) for t in tensors])

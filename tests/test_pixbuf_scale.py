@@ -190,10 +190,13 @@ def test_gpu_equals_the_oracle_on_random_geometry(gpu, orc):
 
 @gpu_mark
 def test_gpu_one_tap_kernels_at_every_ratio(gpu, orc, tune):
-    """k_pb_window / k_pb_direct (what ratios with a 17-bit weight and windows too large for LDS take) forced onto the ratios k_pb_pairs normally serves"""
+    """k_pb_window / k_pb_direct (what ratios with a 17-bit weight and windows too large for LDS take) forced onto the ratios k_pb_pairs normally serves.  By
+    lgpu_debug_pixbuf_plan the first five reach k_pb_window<3 | 4, 0> only; the last three add k_pb_window<3 | 4, 1> (a whole x step) and k_pb_direct<3>
+    (tests/test_pixbuf_plans.py holds every instantiation to a row of its own)"""
     tune("PB_NO_PAIRS", 1)
     rng = np.random.default_rng(0x9DBE)
-    for (sw, sh, dw, dh, ch, interp) in [(384, 216, 171, 96, 4, 3), (200, 120, 300, 180, 4, 3), (200, 120, 133, 80, 3, 2), (64, 36, 200, 100, 3, 3), (320, 180, 96, 54, 4, 2)]:
+    for (sw, sh, dw, dh, ch, interp) in [(384, 216, 171, 96, 4, 3), (200, 120, 300, 180, 4, 3), (200, 120, 133, 80, 3, 2), (64, 36, 200, 100, 3, 3), (320, 180, 96, 54, 4, 2),
+                                         (520, 11, 65, 9, 4, 3), (520, 11, 65, 9, 3, 3), (1820, 32, 65, 9, 3, 3)]:
         src = rng.integers(0, 256, (sh, align(sw * ch, 4)), dtype=np.uint8)
         want = np.zeros((dh, dw * ch), np.uint8)
         assert orc.orc_pixbuf_scale(P(src), src.strides[0], sw, sh, P(want), dw * ch, dw, dh, ch, interp) == 0
@@ -223,11 +226,14 @@ def test_gpu_integer_reductions(gpu, orc):
 
 @gpu_mark
 def test_gpu_enlargements(gpu, orc, tune):
-    """k_pb_up (4-byte pixels, both sides enlarged: register tap window walked down a band of destination rows, pair table in LDS): both filters, ratios from 1.01 to 9,
-    one side kept (step exactly 1), frames narrower than a tap row, widths that end inside a wave, heights that end inside a band, band heights 1 and 5, three alpha mixes"""
+    """Enlargements of 4-byte pixels: both filters, ratios from 1.01 to 9, one side kept (step exactly 1), frames narrower than a tap row, widths that end inside a
+    wave, heights that end inside a band, band heights 1 and 5, three alpha mixes.  By lgpu_debug_pixbuf_plan: HYPER takes k_pb_up<2, 3> / <2, 4> (register tap window
+    walked down a band of destination rows, pair table in LDS); BILINEAR takes k_pb_up<1, 2> only where no destination pixel falls on phase (0, 0) -- most BILINEAR
+    enlargements (100x60 -> 101x61, 64x36 -> 200x100, 96x54 -> 200x54, 3x2 -> 100x70 here) carry that phase's 65536 weight, which the pair tables cannot hold, and go
+    to the one-tap k_pb_window<4, 0>; the exact 1:2 cases go to k_pb_double.  The last case (one side kept, BILINEAR) is the list's k_pb_up<1, 1>"""
     rng = np.random.default_rng(0x9DB8)
     cases = [(128, 72, 192, 108), (100, 60, 101, 61), (64, 36, 200, 100), (30, 20, 270, 180), (96, 54, 96, 108), (96, 54, 200, 54), (3, 2, 100, 70), (1, 1, 9, 9),
-             (640, 360, 1280, 720), (642, 361, 1284, 722), (200, 120, 300, 180), (500, 9, 1000, 10)]
+             (640, 360, 1280, 720), (642, 361, 1284, 722), (200, 120, 300, 180), (500, 9, 1000, 10), (26, 9, 65, 9)]
     for rb in (None, "1", "5"):
         if rb:
             tune("PB_UP_RB", int(rb))
@@ -247,10 +253,11 @@ def test_gpu_enlargements(gpu, orc, tune):
 
 @gpu_mark
 def test_gpu_strong_reductions(gpu, orc):
-    """windows too large for LDS take the direct kernel; ratios past the library's one-step range are refused, the frame untouched"""
+    """windows too large for LDS take the direct kernel (by lgpu_debug_pixbuf_plan the first and third case, k_pb_direct<4>, and the last, k_pb_direct<3>; the
+    second is k_pb_window<3, 1>, the fourth k_pb_window<3, 0>); ratios past the library's one-step range are refused, the frame untouched"""
     from lives_amd import lib
     rng = np.random.default_rng(0x9DB2)
-    for (sw, sh, dw, dh, ch, interp) in [(3000, 64, 100, 8, 4, 3), (64, 1500, 16, 50, 3, 2), (2048, 512, 70, 18, 4, 2), (1200, 900, 41, 300, 3, 3)]:
+    for (sw, sh, dw, dh, ch, interp) in [(3000, 64, 100, 8, 4, 3), (64, 1500, 16, 50, 3, 2), (2048, 512, 70, 18, 4, 2), (1200, 900, 41, 300, 3, 3), (1820, 32, 65, 9, 3, 3)]:
         src = rng.integers(0, 256, (sh, sw * ch), dtype=np.uint8)
         want = np.zeros((dh, dw * ch), np.uint8)
         assert orc.orc_pixbuf_scale(P(src), sw * ch, sw, sh, P(want), dw * ch, dw, dh, ch, interp) == 0

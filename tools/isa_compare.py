@@ -7,7 +7,7 @@ flags (lives_amd/csrc/build.sh) on the parent's and on the changed source file:
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -mllvm -amdgpu-mfma-vgpr-form --cuda-device-only -S pixbuf.hip -o NEW.s
 
 Functions are matched by their leading integer template arguments: a NEW instantiation whose argument list is OLD's followed by zeros (the new parameters at their
-defaults) is OLD's twin.  Compared: every instruction and label of the function body, comments and assembler directives dropped, basic-block labels renumbered
+defaults) is OLD's twin; an instantiation with a type among its arguments is matched by its whole mangled name.  Compared: every instruction and label of the function body, comments and assembler directives dropped, basic-block labels renumbered
 (their numbers carry the function's index in the file).  Exit status 1 when a twin is missing or differs."""
 import argparse
 import re
@@ -53,11 +53,14 @@ def main():
     exact = re.compile(r"\d+%sI" % re.escape(a.kernel))
     old = {k: v for k, v in bodies(a.old, a.kernel).items() if exact.search(k)}
     new = {k: v for k, v in bodies(a.new, a.kernel).items() if exact.search(k)}
-    by_args = {targs(k, a.kernel): k for k in new}
+    by_args = {targs(k, a.kernel): k for k in new if targs(k, a.kernel) is not None}
     same = bad = 0
     for name, body in sorted(old.items()):
         t = targs(name, a.kernel)
-        twin = next((by_args[u] for u in by_args if u[:len(t)] == t and not any(u[len(t):])), None)
+        if t is None:                 # a type among the template arguments (k_pb_pairs<.., PbEpi>): the same mangled name or nothing
+            twin, t = (name if name in new else None), (name,)
+        else:
+            twin = next((by_args[u] for u in by_args if u[:len(t)] == t and not any(u[len(t):])), None)
         if twin is None:
             print("MISSING in new: <%s>" % ", ".join(map(str, t)))
             bad += 1
