@@ -132,9 +132,14 @@ def src_frame(rng, w, h, ps, stride):
     return frame(rng, w, h, ps, stride=stride, extra_rows=GUARD)
 
 
+def guards_kept(want, before, h, what):
+    """the oracle left everything past the frame's h rows as it was (needs no device: the runners assert it before they look at `gpu`)"""
+    assert (want[h:] == before[h:]).all(), what + ": the oracle wrote past the frame"
+
+
 def same_whole(got, want, before, h, what):
     """the whole buffer -- image, row padding and guard rows -- equals the oracle's, and the oracle itself left everything past the frame as it was"""
-    assert (want[h:] == before[h:]).all(), what + ": the oracle wrote past the frame"
+    guards_kept(want, before, h, what)
     bad = np.argwhere(got != want)
     assert len(bad) == 0, "%s: %d bytes differ, first at row %d byte %d (of %d rows + %d guard rows): got %d want %d" % (
         what, len(bad), bad[0][0], bad[0][1], h, got.shape[0] - h, got[tuple(bad[0])], want[tuple(bad[0])])
@@ -518,6 +523,9 @@ def run_rgb_to_yuv(orc, gpu, order, ia, w, fmt, h, nframes=1):
         wp, ws = po.planes_args(wt)
         assert orc.orc_rgb_to_yuv(P(s), s.strides[0], w, h, order, ia, ctypes.addressof(wp), ctypes.addressof(ws), fmt, oa, which) == 0
         wants.append(wt)
+    for f, wt in enumerate(wants):
+        for i, (a, b) in enumerate(dims):
+            guards_kept(wt[i], before[i], b, "rgb_to_yuv fmt=%d %dx%d frame %d plane %d" % (fmt, w, h, f, i))
     if gpu is None:
         return
     got = [[dev(b) for b in before] for _ in range(nframes)]
@@ -563,6 +571,7 @@ def run_yuv_to_rgb(orc, gpu, fmt, ia, order, oa, w, h):
     want = before.copy()
     sp, ss = po.planes_args(planes)
     assert orc.orc_yuv_to_rgb(ctypes.addressof(sp), ctypes.addressof(ss), w, h, fmt, ia, P(want), want.strides[0], order, oa, which) == 0
+    guards_kept(want, before, h, "yuv_to_rgb fmt=%d %dx%d" % (fmt, w, h))
     if gpu is None:
         return
     d = dev(before)
@@ -588,6 +597,7 @@ def run_rgb_to_yuv411(orc, gpu, order, ia, w, h):
     before = blank(h, (w >> 2) * 6)
     want = before.copy()
     assert orc.orc_rgb_to_yuv411(P(src), src.strides[0], w, h, order, ia, P(want), flag(h)) == 0
+    guards_kept(want, before, h, "rgb_to_yuv411 %dx%d" % (w, h))
     if gpu is None:
         return
     d = dev(before)
@@ -610,6 +620,8 @@ def run_repack(orc, gpu, ip, op, w, h, pad, unc, sampling, what):
     sp, ss = po.planes_args(src)
     wp, ws = po.planes_args(want)
     assert orc.orc_yuv_repack(ip, op, ctypes.addressof(sp), ctypes.addressof(ss), ctypes.addressof(wp), ctypes.addressof(ws), w, h, unc, sampling) == 0, what
+    for i, (nb, rows) in enumerate(po.YUV_PLANE_DIMS[op](w, h)):
+        guards_kept(want[i], before[i], rows, "%s %d->%d %dx%d plane %d" % (what, ip, op, w, h, i))
     if gpu is None:
         return
     dst = [dev(b) for b in before]
@@ -1144,6 +1156,8 @@ def run_rgbdelay(orc, gpu, pal, w, inplace, h):
             a = want if inplace else src
             assert orc.orc_rgbdelay_process(s, P(a), a.strides[0], P(want), want.strides[0], w, h, pal, 1, maxcache, on.ctypes.data, st.ctypes.data) == 0
             steps.append((src, before, want, maxcache, on, st))
+    for f, (src, before, want, maxcache, on, st) in enumerate(steps):
+        guards_kept(want, before, h, "rgbdelay pal=%d %dx%d frame %d" % (pal, w, h, f))
     orc.orc_rgbdelay_free(s)
     if gpu is None:
         return

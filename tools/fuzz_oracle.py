@@ -152,15 +152,33 @@ def gcopy(a):
     return b
 
 
+# what one drawn unit of FUZZ_OPS_RANGES is in pixels and rows, where it is not a pixel and a row: "w, h = 2 * int(..), .." draws pixel pairs
+GEOMETRY_UNITS = {"k2": (2, 1), "repack": (2, 2), "repack411": (4, 1), "yuv411": (4, 1), "softlight": (2, 2)}
+
+
 class Draw:
-    def __init__(self, rng):
-        self.rng = rng
+    """fixed: an optional (width, height) in pixels and rows that every geometry draw of a case returns in place of a random one (everything else is still drawn):
+    the comparison at one given size, e.g. the widths beyond the ranges above that tests/test_wide_frames.py runs"""
+
+    def __init__(self, rng, fixed=None):
+        self.rng, self.fixed = rng, fixed
 
     def i(self, lo, hi):
         return int(self.rng.integers(lo, hi))
 
     def wh(self, kind):
         a, b, c, d = FUZZ_OPS_RANGES[kind][1]
+        if self.fixed is not None:
+            ux, uy = GEOMETRY_UNITS.get(kind, (1, 1))
+            assert self.fixed[0] % ux == 0 and self.fixed[1] % uy == 0 and self.fixed[0] >= a * ux and self.fixed[1] >= c * uy, "%s draws no %dx%d" % (kind, self.fixed[0], self.fixed[1])
+            return self.fixed[0] // ux, self.fixed[1] // uy
+        return self.i(a, b), self.i(c, d)
+
+    def geometry(self, a, b, c, d):
+        """the families that draw their own ranges: width in [a, b), height in [c, d)"""
+        if self.fixed is not None:
+            assert self.fixed[0] >= a and self.fixed[1] >= c, "no %dx%d below %dx%d" % (self.fixed[0], self.fixed[1], a, c)
+            return self.fixed
         return self.i(a, b), self.i(c, d)
 
     def stride(self, w, ps, extra=None):
@@ -598,8 +616,8 @@ def same(got, want, what, mask=None):
 class Ctx:
     """what a family function gets: the random stream, the reference, the subject and the mask ledger"""
 
-    def __init__(self, rng, ref, subj):
-        self.rng, self.ref, self.S, self.d = rng, ref, subj, Draw(rng)
+    def __init__(self, rng, ref, subj, geometry=None):
+        self.rng, self.ref, self.S, self.d = rng, ref, subj, Draw(rng, geometry)
         self.masked_bytes = 0
         self.overmasked = 0
         self.redrawn = 0
@@ -1071,7 +1089,7 @@ def fam_edge(x):
     pal, mode = d.i(1, 6), d.i(0, 3)
     ps = 3 if pal <= 2 else 4
     w, h = d.wh("edge")
-    if x.rng.random() < 0.5:        # whole quads, as fuzz_ops.py draws them (capped at 300 x 120)
+    if x.rng.random() < 0.5 and d.fixed is None:        # whole quads, as fuzz_ops.py draws them (capped at 300 x 120)
         w, h = 4 * d.i(2, 76), d.i(4, 121)
     inplace = d.i(0, 2)
     sfr = d.fr(w, h, ps)
@@ -1103,7 +1121,8 @@ def fam_dissolve(x):
     d = x.d
     ps = int(x.rng.choice([3, 4]))
     w, h = d.wh("transition")
-    w, h = max(1, w - 1), max(1, h - 1)           # tests/test_gpu_parity.py::test_dissolve runs 1x1 too
+    if d.fixed is None:
+        w, h = max(1, w - 1), max(1, h - 1)       # tests/test_gpu_parity.py::test_dissolve runs 1x1 too
     amt = float(x.rng.choice([0., 1., float(x.rng.random())]))
     seed = int(x.rng.integers(1, 2 ** 62))
     inplace = d.i(0, 2)
@@ -1188,7 +1207,7 @@ def fam_compositor(x):
     """compositor.c's paint loop (libcompref.so: compref_paint_layer) with the background and the z order laid out as oracle/ref/gen_golden_comp.py does (:171-189)"""
     d = x.d
     ps, is_bgr, revz = int(x.rng.choice([3, 4])), d.i(0, 2), d.i(0, 2)
-    ow, oh, n = d.i(1, 301), d.i(1, 121), d.i(0, 6)
+    (ow, oh), n = d.geometry(1, 301, 1, 121), d.i(0, 6)
     bg = [int(v) for v in x.rng.integers(0, 256, 3)]
     layers = []
     for z in range(n):
@@ -1238,7 +1257,7 @@ def fam_get_resizable(x):
 def fam_blurzoom(x):
     d = x.d
     pal, mode, pattern = d.i(3, 5), d.i(0, 4), d.i(0, 4)
-    w, h, n = d.i(32, 301), d.i(8, 41), d.i(5, 13)          # blurzoom.c:262-263 takes 32 pixels and up
+    (w, h), n = d.geometry(32, 301, 8, 41), d.i(5, 13)          # blurzoom.c:262-263 takes 32 pixels and up
     stride = po.align(w * 4) if mode in (0, 3) else w * 4          # strobe modes: compact rows (blurzoom.c:391-396)
     srcs = []
     for f in range(n):
@@ -1262,7 +1281,7 @@ def fam_rgbdelay(x):
     yuv = x.rng.random() < 0.3
     fn, pal = ("YUVdelay", 588) if yuv else ("RGBdelay", d.i(1, 3))
     clamp = d.i(0, 2) if yuv else -1
-    w, h, n = d.i(1, 133), d.i(1, 25), d.i(5, 13)
+    (w, h), n = d.geometry(1, 133, 1, 25), d.i(5, 13)
     maxcache, inplace = d.i(1, 21), d.i(0, 2)
     on, st = np.zeros(51 * 3, np.int32), np.ones(51, np.float64)
     for j in set([0] + [d.i(0, min(maxcache + 2, 51)) for _ in range(d.i(0, 4))]):
@@ -1302,10 +1321,10 @@ STATEFUL = ("blurzoom", "rgbdelay")
 EXHAUSTIVE = {"clamp_tables": 1024, "premult_tables": 1024, "get_resizable": 1020 + 225}
 
 
-def run(cases, seed, kinds=None, subject="oracle", sequences=None, verbose=True, max_reports=5, per_family=None):
+def run(cases, seed, kinds=None, subject="oracle", sequences=None, verbose=True, max_reports=5, per_family=None, geometry=None):
     """-> {family: dict(drawn, redrawn, compared, skipped, mismatching, masked_bytes, overmasked, first)}; redrawn: draws thrown away because a `never`
     entry of EXCEPTIONS held (they are not part of drawn); skipped: draws neither compared nor mismatching (none today); subject: "oracle", "gpu" or a subject object to use again;
-    per_family overrides the case count of single families"""
+    per_family overrides the case count of single families; geometry: a (width, height) every case takes in place of a drawn one (Draw.fixed)"""
     assert po.have_ref(), "oracle/_ref is not built (oracle/ref/build_ref.sh)"
     subj = GpuSubject() if subject == "gpu" else OracleSubject() if subject == "oracle" else subject
     ref = Ref()
@@ -1318,7 +1337,7 @@ def run(cases, seed, kinds=None, subject="oracle", sequences=None, verbose=True,
             n = (per_family or {}).get(name, n)
             if name in EXHAUSTIVE:
                 n = -(-max(n, 1) // EXHAUSTIVE[name]) * EXHAUSTIVE[name]
-            x = Ctx(np.random.default_rng([seed, k]), ref, subj)
+            x = Ctx(np.random.default_rng([seed, k]), ref, subj, geometry)
             st = dict(drawn=0, redrawn=0, compared=0, skipped=0, mismatching=0, masked_bytes=0, overmasked=0, first=None)
             for _ in range(n):
                 st["drawn"] += 1
