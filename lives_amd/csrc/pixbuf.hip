@@ -30,9 +30,12 @@
 #include <tuple>
 #include <vector>
 
+int get_sink_tables(int which_tables, int in_order, const uint2 **out);      // below: the YUV sink's tables (flat.hip's sinks take them too)
+
 namespace lgpu {
 
 int get_kscale(const uint2 **out);      // resize.hip: the chroma blend's alpha scalers as a device table
+int cavg_forms_checked();               // palette.hip: cavg_arith against the table form, all 65,536 pairs, once per device
 
 struct PbArgs {
   const uint8_t *src;
@@ -225,6 +228,21 @@ struct PbTracks {
   uint8_t *dst[LGPU_CHAIN_MAX_TRACKS];
   uint8_t bf[LGPU_CHAIN_MAX_TRACKS];       // PbHalfArgs.bf_tracks: a blend amount per track (lgpu_chain_amounts: the tracks of a tick need not share one)
 };
+// k_pb_half's eight template arguments as a value (the kernel's comments say what each one does).  pb_half_form_exists is the record of the instantiations the
+// library holds, one clause per caller: pb_half_launch instantiates exactly these, tests/test_pbh_forms.py reads the same set out of the built code object.
+struct PbHalfForm { int chain, hyper, blur, aligned, swap, opaque, yuv, sink; };
+constexpr bool pb_half_form_exists(const PbHalfForm f) {
+  if ((unsigned)f.chain > 2u || (unsigned)f.sink > 2u || (unsigned)(f.hyper | f.blur | f.aligned | f.swap | f.opaque | f.yuv) > 1u) return false;
+  if (!f.chain) return !f.blur && !f.swap && !f.opaque && !f.yuv && !f.sink;             // pb_scale_n: the scaler alone
+  if (f.blur) return f.chain == 1 && !f.aligned && !f.yuv && !f.sink;                     // pb_chain_half with the gaussian: strips with feeder lanes, OPAQUE free
+  if (f.yuv) return f.opaque && !f.aligned;                                               // lgpu_chain_yuv420p, and with SINK 1 or 2 lgpu_chain_yuv420p_to_yuv
+  if (f.sink) return f.aligned && !f.opaque;                                              // lgpu_chain_to_yuv: the sink behind an RGBA source
+  return !f.opaque;                                                                       // pb_chain_half
+}
+// the lanes at each end of a wave's strip that only feed their neighbours, and the output columns a strip yields (two per storing lane): the kernel's addressing
+// and pb_half_geometry's strip count both come from here
+constexpr int pb_half_halo(const PbHalfForm f) { return f.blur ? 2 : f.aligned ? 0 : 1; }
+constexpr int pb_half_strip_cols(const PbHalfForm f) { return (f.yuv && f.sink == 2) ? 120 : 2 * (64 - 2 * pb_half_halo(f)); }
 typedef unsigned short pb_us2 __attribute__((ext_vector_type(2)));
 typedef unsigned pb_u4 __attribute__((ext_vector_type(4)));
 typedef unsigned pb_u2 __attribute__((ext_vector_type(2)));
@@ -480,7 +498,9 @@ template <> struct PbSinkLds<0> {};
 
 template <int CHAIN, int HYPER, int BLUR, int ALIGNED = 0, int SWAP = 0, int OPAQUE = 0, int YUV = 0, int SINK = 0>
 __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTracks T, const Lut8 lut, const typename PbExtraArg<YUV, SINK>::type Y = typename PbExtraArg<YUV, SINK>::type()) {
-  static_assert(!SINK || (CHAIN && !BLUR && (YUV ? OPAQUE && !ALIGNED : !OPAQUE && ALIGNED)),
+  constexpr PbHalfForm kForm = {CHAIN, HYPER, BLUR, ALIGNED, SWAP, OPAQUE, YUV, SINK};
+  static_assert(pb_half_form_exists(kForm), "a form that no caller launches: it gets a clause in pb_half_form_exists first");
+  static_assert(!SINK || pb_half_form_exists(kForm),
                 "the YUV sink: the chain on strips of 64 quads (a quad of lanes = 8 luma bytes on an 8-byte boundary), or behind the 4:2:0 source on its strips with feeder lanes");
   const auto &YS = pb_ysrc(Y);
   const auto &SK = pb_sink(Y);
@@ -492,7 +512,7 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
   // strip come from one extra 4-byte load per source row in lanes 0 and 63
   // YUV with the 4:2:0 sink: 60 storing lanes (1 .. 60; lane 61 feeds, 62 and 63 idle), so that a strip starts at a multiple of four quads and every wave owns whole
   // luma octets / chroma quads -- see sink_row
-  constexpr int kHalo = BLUR ? 2 : ALIGNED ? 0 : 1, kCols = (YUV && SINK == 2) ? 60 : 64 - 2 * kHalo;      // lanes that only feed their neighbours on each side / lanes that store
+  constexpr int kHalo = pb_half_halo(kForm), kCols = pb_half_strip_cols(kForm) / 2;      // lanes that only feed their neighbours on each side / lanes that store
   __shared__ PbSinkLds<SINK> s_sink;
   if constexpr (SINK) {           // the sink's tables: the whole workgroup, before a wave without work leaves (the only workgroup barrier of this form; no letterbox bars in it)
 #pragma unroll
@@ -747,7 +767,7 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
     }
   };
   if constexpr (YUV) {
-    static_assert(CHAIN && OPAQUE && !BLUR && !ALIGNED, "the 4:2:0 source: the chain's all-opaque form, no gaussian, strips with feeder lanes");
+    static_assert(pb_half_form_exists(kForm), "the 4:2:0 source: the chain's all-opaque form, no gaussian, strips with feeder lanes");
     // K2's tables, paired as in k_yuv420p_to_rgb_s: RGB_Y, {R_Cr, G_Cr}[v], {G_Cb, B_Cb}[u] with CLAMP16_240 / the 0..255 clamp folded into the chroma index
     __shared__ uint32_t s_ty[256];
     __shared__ pb_u2 s_rg[256], s_gb[256];
@@ -958,13 +978,8 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
 #pragma unroll
   for (int i = 0; i < 8; i++) if (!OPAQUE || (i & 3) != 3) carry[i] = (HYPER && OPAQUE) ? pb_mad7(hs[i], hr[i]) : HYPER ? __umul24(hs[i], 7u) + hr[i] : hs[i];
 
-  // one scaled row from its last two source rows (the first two are in `carry`): colours apart in cc, alpha in place (<< 24) in al
-  auto scale_row = [&](const pb_u4 &ra, const pb_u4 &rb, uint32_t xa, uint32_t xb, uint32_t cc[2][3], uint32_t al[2]) __attribute__((always_inline)) {
-    if constexpr (HYPER && ALIGNED) { hrow_raw(ra, xa, hr); hrow_raw(rb, xb, hs); }
-    else {
-    pb_half_hrow<HYPER, ALIGNED, SWAP, OPAQUE>(fix(ra), hr);
-    pb_half_hrow<HYPER, ALIGNED, SWAP, OPAQUE>(fix(rb), hs);
-    }
+  // the vertical taps over `carry` and the two new H rows in hr / hs, then the un-premultiply: one scaled row, colours apart in cc, alpha in place (<< 24) in al
+  auto vcombine = [&](uint32_t cc[2][3], uint32_t al[2]) __attribute__((always_inline)) {
     uint32_t v[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) {
@@ -980,6 +995,15 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
       pb_half_colours(v[4 * j], v[4 * j + 1], v[4 * j + 2], va ? va : 1u, cc[j]);       // V_alpha == 0 makes every V_c 0 too: 0 * fl(1 / 1) = 0, the library's all-zero pixel
       al[j] = (va >> A.ashift) << 24;
     }
+  };
+  // one scaled row from its last two source rows (the first two are in `carry`): colours apart in cc, alpha in place (<< 24) in al
+  auto scale_row = [&](const pb_u4 &ra, const pb_u4 &rb, uint32_t xa, uint32_t xb, uint32_t cc[2][3], uint32_t al[2]) __attribute__((always_inline)) {
+    if constexpr (HYPER && ALIGNED) { hrow_raw(ra, xa, hr); hrow_raw(rb, xb, hs); }
+    else {
+    pb_half_hrow<HYPER, ALIGNED, SWAP, OPAQUE>(fix(ra), hr);
+    pb_half_hrow<HYPER, ALIGNED, SWAP, OPAQUE>(fix(rb), hs);
+    }
+    vcombine(cc, al);
   };
 
   if (!BLUR) {
@@ -1065,21 +1089,7 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
       if (more) qa = load_row(S0 + d * (2 * s + 4));
       pb_half_hrow<HYPER, ALIGNED, SWAP, OPAQUE>(qb, hs);
       if (more) qb = load_row(S0 + d * (2 * s + 5));
-      uint32_t v[8];
-#pragma unroll
-      for (int i = 0; i < 8; i++) {
-        if (OPAQUE && (i & 3) == 3) { v[i] = 0u; continue; }
-        if (HYPER && OPAQUE) { v[i] = pb_mad7(hr[i], carry[i] + hs[i]); carry[i] = pb_mad7(hs[i], hr[i]); continue; }
-        if (HYPER) { v[i] = carry[i] + __umul24(hr[i], 7u) + hs[i]; carry[i] = __umul24(hs[i], 7u) + hr[i]; }
-        else { v[i] = carry[i] + hr[i]; carry[i] = hs[i]; }
-      }
-#pragma unroll
-      for (int j = 0; j < 2; j++) {
-        if (OPAQUE) { cc[j][0] = v[4 * j] >> (HYPER ? 8 : 2); cc[j][1] = v[4 * j + 1] >> (HYPER ? 8 : 2); cc[j][2] = v[4 * j + 2] >> (HYPER ? 8 : 2); al[j] = 0xFF000000u; continue; }
-        const uint32_t va = v[4 * j + 3];
-        pb_half_colours(v[4 * j], v[4 * j + 1], v[4 * j + 2], va ? va : 1u, cc[j]);
-        al[j] = (va >> A.ashift) << 24;
-      }
+      vcombine(cc, al);
     };
 #pragma unroll
     for (int s = 0; s < 4; s++) {            // the four rows above (below) the band's first output row: no output yet (nsteps >= 5: a next step exists)
@@ -2103,14 +2113,17 @@ static int pb_half_aligned(int blur, int yuv) {
   return tune(TUNE_PBH_ALIGNED) >= 0 ? (tune(TUNE_PBH_ALIGNED) ? 1 : 0) : 1;
 }
 
-static void pb_half_geometry(PbHalfArgs *a, int ntracks, int blur = 0, int opaque = 0, int yuv = 0, int strip_cols = 0) {      // strip_cols: output columns per strip, when the form has its own
+// cuts the frame into strips and bands for the form's strip width, and decides the one argument of the form that is a matter of geometry: f->aligned
+static void pb_half_geometry(PbHalfArgs *a, int ntracks, PbHalfForm *f) {
+  const int blur = f->blur, opaque = f->opaque;
   // strips of 64 storing lanes on 128-byte lines (k_pb_half<.., ALIGNED>; the two outer taps of a strip from one extra 4-byte load per source row, which lanes 0 and 63
   // keep as the raw pixel the lane exchange leaves in a lane without a source lane -- hrow_raw in the kernel).  Round 3 measured them 3 % lighter on traffic and 13 %
   // heavier on arithmetic: a draw.  With round 4's arithmetic (buffer addressing, five-operation reciprocal) they win clearly: 16 tracks 166.5 -> 155.0 us, 8 tracks
   // 85.7 -> 81.1, one frame equal (profiles/r04/al_ab1.txt, interleaved; measured on the exchange of premultiplied pairs that the kernel had then).  The exchange of raw
   // pixels and its instruction budget: profiles/r10/.  LGPU_PBH_ALIGNED=0 keeps the feeder-lane strips.
-  a->aligned = pb_half_aligned(blur, yuv);
-  a->strips = (int)cdiv((unsigned)a->dw, strip_cols ? strip_cols : blur ? 120 : a->aligned ? 128 : 124);
+  // The sink behind an RGBA source exists on strips of 64 quads only (a quad of lanes must start on an 8-byte luma boundary): PBH_ALIGNED = 0 is OVERRIDDEN there.
+  a->aligned = f->aligned = (f->sink && !f->yuv) ? 1 : pb_half_aligned(blur, f->yuv);
+  a->strips = (int)cdiv((unsigned)a->dw, (unsigned)pb_half_strip_cols(*f));
   a->cgroups = (a->strips + 3) / 4;
   a->ntracks = ntracks;
   // Band height.  Short bands win (profiles/r03/pbh_sweep*.txt, r04/al_ab1.txt: 4-6 rows within 1 %, 8 rows 5 % behind, 12 rows further).  One frame: 6 rows.  A launch of
@@ -2189,76 +2202,122 @@ template <int NT> static void pb_fill_sink(PbSinkDstT<NT> *S, const lgpu_chain_s
   S->urow = planar ? sk->orow[1] : 0; S->vrow = planar ? sk->orow[2] : 0; S->fmt = sk->out_fmt; S->unclamped = sk->which_tables & 1;
 }
 
+// PbHalfArgs as every launch starts it: the frame, the scaler's weights and the chain's stages; the strips, bands and work order are pb_half_geometry's and
+// pb_half_shape's to add.  Everything else is 0.  The blend amount has three sources: bf_tracks (PbTracks.bf, a byte per track), else the device word bf_d, else bf.
+static PbHalfArgs pb_half_args(int chain, int sw, int sh, int irow, int dw, int dh, int orow, int hyper, int swap_rb = 0, int irow2 = 0, int use_lut = 0,
+                               const uint2 *kscale = nullptr, int bf_tracks = 0, uint32_t bf = 0, const int32_t *bf_d = nullptr) {
+  PbHalfArgs a{};
+  a.sw = sw; a.sh = sh; a.irow = irow; a.dw = dw; a.dh = dh; a.orow = orow;
+  a.hyper = hyper; a.ashift = hyper ? 8 : 2; a.kscale = kscale;
+  a.swap_rb = swap_rb; a.blend = a.nt_out = chain ? 1 : 0; a.irow2 = irow2; a.use_lut = use_lut;
+  a.bf = bf; a.bf_d = bf_d; a.bf_tracks = bf_tracks;
+  return a;
+}
+
+// The one place that names k_pb_half<...>: the run-time form becomes the template arguments one at a time, and only the forms of pb_half_form_exists (with the
+// extra argument of their YUV / SINK: PbNoYuv, PbYuvSrc, PbSinkDst, PbYuvSink) end at a launch; every other one returns false and is an error, as pb_no_kernel.
+template <class X, int... F>
+static bool pb_half_launch_as(const int *v, dim3 grid, size_t lds, hipStream_t st, const PbHalfArgs &a, const PbTracks &T, const Lut8 &lut, const X &x) {
+  constexpr int n = (int)sizeof...(F);
+  if constexpr (n == 8) {
+    constexpr PbHalfForm f = {F...};
+    if constexpr (pb_half_form_exists(f) && std::is_same<X, typename PbExtraArg<f.yuv, f.sink>::type>::value) {
+      hipLaunchKernelGGL((k_pb_half<F...>), grid, dim3(256), lds, st, a, T, lut, x);
+      return true;
+    }
+  } else {
+    if (v[n] == 0) return pb_half_launch_as<X, F..., 0>(v, grid, lds, st, a, T, lut, x);
+    if (v[n] == 1) return pb_half_launch_as<X, F..., 1>(v, grid, lds, st, a, T, lut, x);
+    if constexpr (n == 0 || n == 7) if (v[n] == 2) return pb_half_launch_as<X, F..., 2>(v, grid, lds, st, a, T, lut, x);      // CHAIN and SINK count to 2
+  }
+  return false;
+}
+template <class X>
+static int pb_half_launch(const PbHalfForm &f, dim3 grid, size_t lds, hipStream_t st, const PbHalfArgs &a, const PbTracks &T, const Lut8 &lut, const X &extra) {
+  const int v[8] = {f.chain, f.hyper, f.blur, f.aligned, f.swap, f.opaque, f.yuv, f.sink};
+  if (!pb_half_launch_as<X>(v, grid, lds, st, a, T, lut, extra)) {
+    set_error("k_pb_half: the form (%d, %d, %d, %d, %d, %d, %d, %d) names no instantiation", v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
+    return LGPU_E_HIP;
+  }
+  LGPU_CHECK_LAUNCH();
+  return LGPU_OK;
+}
+
+// a caller's own work order and band group for pb_half_shape (PBH_ORDER / PBH_GROUP); -1 / 0: pb_half_shape decides, once the geometry is known
+static void pb_half_order_switches(int *order, int *group) {
+  *order = tune(TUNE_PBH_ORDER) >= 0 && tune(TUNE_PBH_ORDER) <= 2 ? tune(TUNE_PBH_ORDER) : -1;
+  *group = tune(TUNE_PBH_GROUP) >= 1 && tune(TUNE_PBH_GROUP) <= 4096 ? tune(TUNE_PBH_GROUP) : 0;
+}
+
+// What pb_chain_half and the three YUV entry points settle before they fill PbHalfArgs: HYPER or BILINEAR, the scaler's table pinned and verified to be the exact
+// 2:1 outer product on frames of the caller's address bits (f->hyper), then what the form asks for -- the all-opaque arithmetic checked against the library's
+// (OPAQUE), the table-free chroma average against the table form (the 4:2:0 sink), the sink's tables -- and the blend's alpha scalers.
+// fn: the entry point's name and `tail` the end of its LGPU_E_UNSUPPORTED text; nullptr: pb_chain_half, which says nothing (pb_chain then runs the stages one by one).
+static int pb_half_tables(const char *fn, const char *tail, const lgpu_chain_params *pr, uintptr_t src_bits, uintptr_t dst_bits, const lgpu_chain_sink *sk, hipStream_t st,
+                          PbHalfForm *f, PbPin *pin, const uint2 **kscale, const uint2 **sink_tab = nullptr) {
+  const int interp = pr->interp & 0xFF;
+  int rc, ashift;
+  if (interp != 2 && interp != 3) return LGPU_E_UNSUPPORTED;        // (the entry points have said so in their own words before they come here)
+  if ((rc = pb_table(interp, pr->sw, pr->sh, pr->dw, pr->dh, st, pin))) return rc;
+  if (!pb_half_ok(pin->t, interp, pr->sw, pr->sh, pr->dw, pr->dh, src_bits, dst_bits, &f->hyper, &ashift)) {
+    if (fn) set_error("%s: the scaler's table is not the exact 2:1 outer product%s", fn, tail);
+    return LGPU_E_UNSUPPORTED;
+  }
+  if (f->opaque && (rc = pb_opaque_check())) return rc;
+  if (f->sink == 2 && (rc = cavg_forms_checked())) return rc;
+  if (f->sink && (rc = get_sink_tables(sk->which_tables, sk->in_order, sink_tab))) return rc;
+  return get_kscale(kscale);
+}
+
 // the fused chain on the pixbuf arithmetic (lgpu_chain with LGPU_INTERP_PIXBUF): convert -> gdk-pixbuf 2:1 scale -> chroma blend -> gamma LUT in one launch.
 // LGPU_E_UNSUPPORTED when the geometry is not the exact aligned 2:1 case (the caller then runs the stages one by one).
 int pb_chain_half(const lgpu_chain_params *pr, const lgpu_canvas *cv, const lgpu_chain_track *tracks, int ntracks, hipStream_t st, const uint8_t *amounts = nullptr) {
-  const int interp = pr->interp & 0xFF;
-  if (interp != 2 && interp != 3) return LGPU_E_UNSUPPORTED;
-  PbPin pin;
-  int rc = pb_table(interp, pr->sw, pr->sh, pr->dw, pr->dh, st, &pin);
-  if (rc) return rc;
-  const PbTable *t = pin.t;
-  uintptr_t sb = (uintptr_t)pr->irow, db = (uintptr_t)pr->orow | (uintptr_t)pr->irow2;
-  for (int i = 0; i < ntracks; i++) { sb |= (uintptr_t)tracks[i].src_d; db |= (uintptr_t)tracks[i].dst_d | (uintptr_t)tracks[i].layer2_d; }
-  PbHalfArgs a;
   if (cv && (cv->offs_x & 1)) return LGPU_E_UNSUPPORTED;        // 8-byte stores: the frame must start on an even canvas column
-  if (!pb_half_ok(t, interp, pr->sw, pr->sh, pr->dw, pr->dh, sb, db, &a.hyper, &a.ashift)) return LGPU_E_UNSUPPORTED;
   {
     // k_pb_half addresses its frames through 32-bit buffer offsets (row * rowstride as a scalar offset): a plane of 2 GiB or more -- a sub-rectangle of a huge atlas
     // with its rowstride -- keeps the general kernels and their 64-bit row addresses
     const long long out_rows = cv ? cv->nheight : pr->dh, lim = 1ll << 31;
     if ((long long)pr->sh * pr->irow >= lim || out_rows * pr->orow >= lim || out_rows * pr->irow2 >= lim) return LGPU_E_UNSUPPORTED;
   }
-  if ((rc = get_kscale(&a.kscale))) return rc;
-  a.sw = pr->sw; a.sh = pr->sh; a.irow = pr->irow; a.dw = pr->dw; a.dh = pr->dh; a.orow = pr->orow;
-  a.swap_rb = pr->swap_rb ? 1 : 0; a.blend = 1; a.irow2 = pr->irow2; a.use_lut = pr->use_lut ? 1 : 0; a.bf = (uint32_t)pr->bf & 0xFF; a.bf_d = pr->param_block_d;
-  a.bf_tracks = amounts ? 1 : 0;
-  a.nt_out = 1;
+  const bool blur = pr->do_blur != 0, noblend = (pr->interp & LGPU_INTERP_NOBLEND) != 0;        // (never both: pb_chain keeps that pair staged)
+  // OPAQUE, the caller's word that every source pixel is opaque: the vector-bound gaussian chain sheds a quarter of its instructions (pb_half_hrow)
+  PbHalfForm f = {noblend && !blur ? 2 : 1, 0, blur, 0, pr->swap_rb ? 1 : 0, blur && (pr->interp & LGPU_INTERP_OPAQUE), 0, 0};
+  uintptr_t sb = (uintptr_t)pr->irow, db = (uintptr_t)pr->orow | (uintptr_t)pr->irow2;
+  for (int i = 0; i < ntracks; i++) { sb |= (uintptr_t)tracks[i].src_d; db |= (uintptr_t)tracks[i].dst_d | (uintptr_t)tracks[i].layer2_d; }
+  PbPin pin;
+  const uint2 *kscale;
+  int rc = pb_half_tables(nullptr, "", pr, sb, db, nullptr, st, &f, &pin, &kscale);
+  if (rc) return rc;
+  PbHalfArgs a = pb_half_args(f.chain, pr->sw, pr->sh, pr->irow, pr->dw, pr->dh, pr->orow, f.hyper, f.swap, pr->irow2, pr->use_lut ? 1 : 0, kscale, amounts ? 1 : 0,
+                              (uint32_t)pr->bf & 0xFF, pr->param_block_d);
   // (non-temporal loads for a band's inner source rows were measured and dropped: a gain only on buffers the memory-side cache still holds, profiles/r04/nt_cold_ab.txt)
   // Work order (PBH_ORDER; profiles/r04/order_ab.txt, interleaved on cold buffers).  0: a column group's bands one after the other, an XCD owning a contiguous run (rounds 3 / 4);
   // 1: the column groups of a band one after the other -- consecutive workgroups read a band across the whole row: 16 tracks 147.5 -> 142.3 us on one box, 152 -> 146 on another;
   // 2: that, with the bands of a track dealt round robin to the XCDs, so that the whole device sweeps ONE frame at a time like a linear stream does: 151-152 -> 144.2, 8 tracks
   // 76.8 -> 74.3.  With the 5x5 gaussian in the chain neighbouring bands share ten source rows instead of two and want the same L2: 186 us with 1, 189 with 2 -- it keeps 1.
-  const int order = tune(TUNE_PBH_ORDER) >= 0 && tune(TUNE_PBH_ORDER) <= 2 ? tune(TUNE_PBH_ORDER) : -1;       // -1: pb_half_shape decides, once the geometry is known
   // ... in groups of `bgroup` neighbouring bands per XCD turn (PBH_GROUP; pb_half_shape's default and its measurements)
-  const int group = tune(TUNE_PBH_GROUP) >= 1 && tune(TUNE_PBH_GROUP) <= 4096 ? tune(TUNE_PBH_GROUP) : 0;
-  pb_half_geometry(&a, ntracks, pr->do_blur ? 1 : 0, (pr->do_blur && (pr->interp & LGPU_INTERP_OPAQUE)) ? 1 : 0);
+  int order, group;
+  pb_half_order_switches(&order, &group);
+  pb_half_geometry(&a, ntracks, &f);
   // With the gaussian (four resident workgroups per CU, one per CU and track): order 2 from a whole generation on -- 4 tracks 42.3 -> 41.9 us, 8 88.7 -> 86.9, 16 166.5 -> 164.5;
   // one and two tracks keep order 1 (16.9 / 26.4 against 17.1 / 27.2).  Round 4's kernel, with its taller bands, had it the other way round.
-  pb_half_shape(&a, ntracks, cv, false, order, group, (long long)device_cus() * (pr->do_blur ? 4 : 8) + (pr->do_blur ? 0 : 1));
+  pb_half_shape(&a, ntracks, cv, false, order, group, (long long)device_cus() * (blur ? 4 : 8) + (blur ? 0 : 1));
   PbTracks T;
   for (int i = 0; i < ntracks; i++) { T.src[i] = tracks[i].src_d; T.l2[i] = tracks[i].layer2_d; T.dst[i] = tracks[i].dst_d; T.bf[i] = amounts ? amounts[i] : 0; }
-  const Lut8 l = pack_lut(pr->use_lut ? pr->lut8 : nullptr);
-  const dim3 grid((unsigned)(a.main_blocks + a.bar_first));
-  const size_t occ_lds = pb_half_occ_lds(a, ntracks, !pr->do_blur, 3072);      // (the gaussian chain keeps its six workgroups per CU)
-  const bool noblend = (pr->interp & LGPU_INTERP_NOBLEND) != 0;        // (never with the gaussian: pb_chain keeps that pair staged)
-#define PBH_LAUNCH(HY, BL, AL, SW) { if (noblend && !(BL)) hipLaunchKernelGGL((k_pb_half<(BL) ? 1 : 2, HY, BL, AL, SW>), grid, dim3(256), occ_lds, st, a, T, l); \
-                                     else hipLaunchKernelGGL((k_pb_half<1, HY, BL, AL, SW>), grid, dim3(256), occ_lds, st, a, T, l); }
-#define PBH_SWAP(HY, BL, AL) do { if (a.swap_rb) PBH_LAUNCH(HY, BL, AL, 1) else PBH_LAUNCH(HY, BL, AL, 0) } while (0)
-#define PBH_OPAQUE(HY, SW) hipLaunchKernelGGL((k_pb_half<1, HY, 1, 0, SW, 1>), grid, dim3(256), occ_lds, st, a, T, l)
-  if (pr->do_blur && (pr->interp & LGPU_INTERP_OPAQUE)) {
-    // the caller's word that every source pixel is opaque: the vector-bound gaussian chain sheds a quarter of its instructions (pb_half_hrow)
-    if ((rc = pb_opaque_check())) return rc;
-    if (a.hyper) { if (a.swap_rb) PBH_OPAQUE(1, 1); else PBH_OPAQUE(1, 0); }
-    else { if (a.swap_rb) PBH_OPAQUE(0, 1); else PBH_OPAQUE(0, 0); }
-  } else if (pr->do_blur) {
-    if (a.hyper) PBH_SWAP(1, 1, 0); else PBH_SWAP(0, 1, 0);
-  } else if (a.aligned) {
-    if (a.hyper) PBH_SWAP(1, 0, 1); else PBH_SWAP(0, 0, 1);
-  } else {
-    if (a.hyper) PBH_SWAP(1, 0, 0); else PBH_SWAP(0, 0, 0);
-  }
-#undef PBH_OPAQUE
-#undef PBH_SWAP
-#undef PBH_LAUNCH
-  LGPU_CHECK_LAUNCH();
-  return LGPU_OK;
+  const size_t occ_lds = pb_half_occ_lds(a, ntracks, !blur, 3072);      // (the gaussian chain keeps its six workgroups per CU)
+  return pb_half_launch(f, dim3((unsigned)(a.main_blocks + a.bar_first)), occ_lds, st, a, T, pack_lut(pr->use_lut ? pr->lut8 : nullptr), PbNoYuv{});
 }
 
 // lgpu_chain / lgpu_chain_canvas.  One fused launch for the exact aligned 2:1 case on the pixbuf arithmetic (blur stage and letterbox canvas included); otherwise the
 // stages run one after the other through stream-ordered scratch frames: [bars] -> scale (into the canvas) -> [5x5 gaussian] -> [R <-> B] + chroma blend + gamma LUT.
 // The channel swap commutes with the scalers and the gaussian (all treat the three colour bytes alike), so it rides in the last kernel.
 int pb_scale_fused(const uint8_t *const *srcs, uint8_t *const *dsts, int n, int irow, int sw, int sh, int orow, int dw, int dh, int interp, hipStream_t st, const PbEpi *epi);
+// the chain's last stages as a scaler's store takes them (PbEpi); l2_off: where the scaled frame's first layer-2 pixel lies in a track's layer 2 (a letterbox canvas)
+static void pb_fill_epi(PbEpi *e, const lgpu_chain_params *pr, const lgpu_chain_track *tracks, int ntracks, const uint8_t *amounts, size_t l2_off) {
+  for (int i = 0; i < ntracks; i++) { e->l2[i] = tracks[i].layer2_d + l2_off; e->bf[i] = amounts ? amounts[i] : 0; }
+  e->bf_d = amounts ? nullptr : pr->param_block_d; e->bf0 = (uint32_t)pr->bf & 0xFF; e->irow2 = pr->irow2; e->swap_rb = pr->swap_rb ? 1 : 0; e->use_lut = pr->use_lut ? 1 : 0;
+  e->bf_tracks = amounts ? 1 : 0; e->blend = (pr->interp & LGPU_INTERP_NOBLEND) ? 0 : 1; e->lut = pack_lut(pr->use_lut ? pr->lut8 : nullptr);
+}
 int pb_chain(const lgpu_chain_params *pr, const lgpu_canvas *cv, const lgpu_chain_track *tracks, int ntracks, hipStream_t st, const uint8_t *amounts) {
   int rc;
   const bool pixbuf = (pr->interp & LGPU_INTERP_PIXBUF) != 0, noblend = (pr->interp & LGPU_INTERP_NOBLEND) != 0;
@@ -2266,9 +2325,8 @@ int pb_chain(const lgpu_chain_params *pr, const lgpu_canvas *cv, const lgpu_chai
     if (pr->do_blur) { set_error("lgpu_chain_amounts: the gaussian needs the resize stage"); return LGPU_E_UNSUPPORTED; }
     PbEpi e;
     PbTracks T;
-    for (int i = 0; i < ntracks; i++) { T.src[i] = tracks[i].src_d; T.l2[i] = tracks[i].layer2_d; T.dst[i] = tracks[i].dst_d; T.bf[i] = e.bf[i] = amounts ? amounts[i] : 0; e.l2[i] = tracks[i].layer2_d; }
-    e.bf_d = amounts ? nullptr : pr->param_block_d; e.bf0 = (uint32_t)pr->bf & 0xFF; e.irow2 = pr->irow2; e.swap_rb = pr->swap_rb ? 1 : 0; e.use_lut = pr->use_lut ? 1 : 0;
-    e.bf_tracks = amounts ? 1 : 0; e.blend = noblend ? 0 : 1; e.lut = pack_lut(pr->use_lut ? pr->lut8 : nullptr);
+    pb_fill_epi(&e, pr, tracks, ntracks, amounts, 0);
+    for (int i = 0; i < ntracks; i++) { T.src[i] = tracks[i].src_d; T.l2[i] = tracks[i].layer2_d; T.dst[i] = tracks[i].dst_d; T.bf[i] = e.bf[i]; }
     const int cw = cv ? cv->nwidth : pr->dw, ch = cv ? cv->nheight : pr->dh;
     hipLaunchKernelGGL(k_pb_flat_n, dim3(cdiv((unsigned)cw, 64), cdiv((unsigned)ch, 4), (unsigned)ntracks), dim3(256), 0, st, T, e, pr->irow, pr->orow, cw, ch,
                        cv ? cv->offs_x : 0, cv ? cv->offs_y : 0, pr->dw, pr->dh);
@@ -2287,12 +2345,11 @@ int pb_chain(const lgpu_chain_params *pr, const lgpu_canvas *cv, const lgpu_chai
     const uint8_t *srcs[LGPU_CHAIN_MAX_TRACKS];
     uint8_t *dsts[LGPU_CHAIN_MAX_TRACKS];
     const size_t doff = cv ? (size_t)cv->offs_y * pr->orow + 4 * (size_t)cv->offs_x : 0, loff = cv ? (size_t)cv->offs_y * pr->irow2 + 4 * (size_t)cv->offs_x : 0;
+    pb_fill_epi(&e, pr, tracks, ntracks, amounts, loff);
     for (int i = 0; i < ntracks; i++) {
-      srcs[i] = tracks[i].src_d; dsts[i] = tracks[i].dst_d + doff; e.l2[i] = tracks[i].layer2_d + loff; e.bf[i] = amounts ? amounts[i] : 0;
+      srcs[i] = tracks[i].src_d; dsts[i] = tracks[i].dst_d + doff;
       T.src[i] = nullptr; T.l2[i] = tracks[i].layer2_d; T.dst[i] = tracks[i].dst_d; T.bf[i] = e.bf[i];
     }
-    e.bf_d = amounts ? nullptr : pr->param_block_d; e.bf0 = (uint32_t)pr->bf & 0xFF; e.irow2 = pr->irow2; e.swap_rb = pr->swap_rb ? 1 : 0; e.use_lut = pr->use_lut ? 1 : 0;
-    e.bf_tracks = amounts ? 1 : 0; e.blend = noblend ? 0 : 1; e.lut = pack_lut(pr->use_lut ? pr->lut8 : nullptr);
     rc = pb_scale_fused(srcs, dsts, ntracks, pr->irow, pr->sw, pr->sh, pr->orow, pr->dw, pr->dh, (pr->interp & 0xFF) | (pr->interp & LGPU_INTERP_OPAQUE), st, &e);
     if (rc == LGPU_OK && cv && (cv->nwidth != pr->dw || cv->nheight != pr->dh)) {
       for (int i = 0; i < ntracks; i++) e.l2[i] = tracks[i].layer2_d;      // the bars read layer 2 at canvas coordinates
@@ -2597,39 +2654,29 @@ static int pb_scale_n(const uint8_t *const *srcs, uint8_t *const *dsts, int n, i
     else hipLaunchKernelGGL(k_pb_nearest<3>, grid, block, 0, st, F, irow, sw, sh, orow, dw, dh, x_step, y_step);
     break;
   case LGPU_PB_PATH_DOUBLE: {
-    PbHalfArgs h;
-    h.sw = sw; h.sh = sh; h.irow = irow; h.dw = dw; h.dh = dh; h.orow = orow;
+    PbHalfArgs h = pb_half_args(0, sw, sh, irow, dw, dh, orow, 0);
     h.strips = p.strips; h.cgroups = p.cgroups; h.th = p.tile_h; h.bands = p.bands; h.ntracks = 1;
     hipLaunchKernelGGL(k_pb_double<0>, grid, block, 0, st, h, F);
     break;
   }
   case LGPU_PB_PATH_HALF3: {
-    PbHalfArgs h;
-    h.hyper = p.hyper; h.ashift = p.hyper ? 8 : 2;
-    h.sw = sw; h.sh = sh; h.irow = irow; h.dw = dw; h.dh = dh; h.orow = orow;
+    PbHalfArgs h = pb_half_args(0, sw, sh, irow, dw, dh, orow, p.hyper);
     h.strips = p.strips; h.cgroups = p.cgroups; h.th = p.tile_h; h.bands = p.bands; h.ntracks = 1;
     if (p.hyper) hipLaunchKernelGGL(k_pb_half3<1>, grid, block, 0, st, h, F);
     else hipLaunchKernelGGL(k_pb_half3<0>, grid, block, 0, st, h, F);
     break;
   }
   case LGPU_PB_PATH_HALF: {
-    PbHalfArgs h;
-    h.hyper = p.hyper; h.ashift = p.hyper ? 8 : 2;
-    h.sw = sw; h.sh = sh; h.irow = irow; h.dw = dw; h.dh = dh; h.orow = orow;
-    h.swap_rb = 0; h.blend = 0; h.irow2 = 0; h.use_lut = 0; h.bf = 0; h.bf_d = nullptr; h.nt_out = 0; h.row_major = tune(TUNE_PBH_ORDER) >= 0 && tune(TUNE_PBH_ORDER) <= 2 ? tune(TUNE_PBH_ORDER) : 1; h.bgroup = tune(TUNE_PBH_GROUP) >= 1 && tune(TUNE_PBH_GROUP) <= 4096 ? tune(TUNE_PBH_GROUP) : 0;
-    pb_half_geometry(&h, n);             // h.aligned: pb_half_aligned(0, 0), as the plan has it
-    if (tune(TUNE_PBH_ORDER) < 0 && (long long)h.cgroups * h.bands * n > (long long)device_cus() * 8) h.row_major = 2;      // more than one generation: the chain's sweep order (pb_chain_half)
-    if (h.bgroup <= 0) h.bgroup = (h.bands % 8 == 0) ? h.bands / 8 : 1;
+    PbHalfForm f = {0, p.hyper, 0, 0, 0, 0, 0, 0};
+    PbHalfArgs h = pb_half_args(0, sw, sh, irow, dw, dh, orow, p.hyper);
+    int order, group;
+    pb_half_order_switches(&order, &group);
+    pb_half_geometry(&h, n, &f);             // f.aligned: pb_half_aligned(0, 0), as the plan has it
+    pb_half_shape(&h, n, nullptr, false, order, group);      // more than one generation: the chain's sweep order (pb_chain_half)
+    if (f.aligned != p.aligned) { set_error("lgpu_pixbuf_scale: k_pb_half's strip form differs from the plan's"); return LGPU_E_HIP; }
     PbTracks T;
     for (int i = 0; i < n; i++) { T.src[i] = srcs[i]; T.l2[i] = nullptr; T.dst[i] = dsts[i]; }
-    h.kscale = nullptr; h.cw = h.ch = h.ox = h.oy = 0; h.bar_blocks = 0; h.bar_first = 0; h.main_blocks = (int)pb_half_grid(h);
-    if (h.aligned != p.aligned) { set_error("lgpu_pixbuf_scale: k_pb_half's strip form differs from the plan's"); return LGPU_E_HIP; }
-    if (p.aligned) {
-      if (p.hyper) hipLaunchKernelGGL((k_pb_half<0, 1, 0, 1>), dim3(pb_half_grid(h)), dim3(256), 0, st, h, T, pack_lut(nullptr));
-      else hipLaunchKernelGGL((k_pb_half<0, 0, 0, 1>), dim3(pb_half_grid(h)), dim3(256), 0, st, h, T, pack_lut(nullptr));
-    } else if (p.hyper) hipLaunchKernelGGL((k_pb_half<0, 1, 0>), dim3(pb_half_grid(h)), dim3(256), 0, st, h, T, pack_lut(nullptr));
-    else hipLaunchKernelGGL((k_pb_half<0, 0, 0>), dim3(pb_half_grid(h)), dim3(256), 0, st, h, T, pack_lut(nullptr));
-    break;
+    return pb_half_launch(f, dim3((unsigned)h.main_blocks), 0, st, h, T, pack_lut(nullptr), PbNoYuv{});
   }
   case LGPU_PB_PATH_UP: {
     PbUpArgs ua;
@@ -2845,19 +2892,12 @@ extern "C" int lgpu_chain_yuv420p(const lgpu_chain_params *pr, const lgpu_yuv_so
   }
   if ((rc = check_plane_sizes(fn, {(long long)pr->sh * lys, ys->u_size, ys->v_size, (long long)ch * pr->orow, noblend ? 0 : (long long)ch * pr->irow2}))) return rc;
   hipStream_t st = (hipStream_t)stream;
+  PbHalfForm f = {noblend ? 2 : 1, 0, 0, 0, (ys->out_order ^ (pr->swap_rb ? 1 : 0)) & 1, 1, 1, 0};
   PbPin pin;
-  if ((rc = pb_table(interp, pr->sw, pr->sh, pr->dw, pr->dh, st, &pin))) return rc;
-  PbHalfArgs a;
-  if (!pb_half_ok(pin.t, interp, pr->sw, pr->sh, pr->dw, pr->dh, 0, db, &a.hyper, &a.ashift)) {
-    set_error("lgpu_chain_yuv420p: the scaler's table is not the exact 2:1 outer product");
-    return LGPU_E_UNSUPPORTED;
-  }
-  if ((rc = pb_opaque_check())) return rc;
-  if ((rc = get_kscale(&a.kscale))) return rc;
-  a.sw = pr->sw; a.sh = pr->sh; a.irow = lys; a.dw = pr->dw; a.dh = pr->dh; a.orow = pr->orow;
-  a.swap_rb = (ys->out_order ^ (pr->swap_rb ? 1 : 0)) & 1; a.blend = 1; a.irow2 = noblend ? pr->orow : pr->irow2; a.use_lut = pr->use_lut ? 1 : 0;
-  a.bf = 0; a.bf_d = nullptr; a.bf_tracks = 1; a.nt_out = 1;
-  pb_half_geometry(&a, ntracks, 0, 0, 1);
+  const uint2 *kscale;
+  if ((rc = pb_half_tables(fn, "", pr, 0, db, nullptr, st, &f, &pin, &kscale))) return rc;
+  PbHalfArgs a = pb_half_args(f.chain, pr->sw, pr->sh, lys, pr->dw, pr->dh, pr->orow, f.hyper, f.swap, noblend ? pr->orow : pr->irow2, pr->use_lut ? 1 : 0, kscale, 1);
+  pb_half_geometry(&a, ntracks, &f);
   pb_half_shape(&a, ntracks, cv, false);
   PbTracks T;
   PbYuvSrc Y;
@@ -2866,28 +2906,15 @@ extern "C" int lgpu_chain_yuv420p(const lgpu_chain_params *pr, const lgpu_yuv_so
     Y.u[i] = tracks[i].u_d; Y.v[i] = tracks[i].v_d;
   }
   pb_fill_yuv_src(&Y, ys);
-  const Lut8 l = pack_lut(pr->use_lut ? pr->lut8 : nullptr);
-  const dim3 grid((unsigned)(a.main_blocks + a.bar_first));
   // No dynamic LDS: pb_chain_half's cap of five workgroups per CU (profiles/r04/occupancy_sweep.txt) was measured for the memory-bound RGBA kernel; this one is
   // bound by its arithmetic and its 85-93 registers already hold it to five waves per SIMD.  The cap has not been measured for it.
-#define PBY_LAUNCH(CH, HY, SW) hipLaunchKernelGGL((k_pb_half<CH, HY, 0, 0, SW, 1, 1>), grid, dim3(256), 0, st, a, T, l, Y)
-  if (noblend) {
-    if (a.hyper) { if (a.swap_rb) PBY_LAUNCH(2, 1, 1); else PBY_LAUNCH(2, 1, 0); }
-    else { if (a.swap_rb) PBY_LAUNCH(2, 0, 1); else PBY_LAUNCH(2, 0, 0); }
-  } else {
-    if (a.hyper) { if (a.swap_rb) PBY_LAUNCH(1, 1, 1); else PBY_LAUNCH(1, 1, 0); }
-    else { if (a.swap_rb) PBY_LAUNCH(1, 0, 1); else PBY_LAUNCH(1, 0, 0); }
-  }
-#undef PBY_LAUNCH
-  LGPU_CHECK_LAUNCH();
-  return LGPU_OK;
+  return pb_half_launch(f, dim3((unsigned)(a.main_blocks + a.bar_first)), 0, st, a, T, pack_lut(pr->use_lut ? pr->lut8 : nullptr), Y);
 }
 
 // the sink's tables (k_pb_half<.., SINK>): rgb2yuv[which_tables] as {Y, U} and {Y, V} contributions per byte POSITION of the chain's result -- in_order 1 (BGRA): byte 0
 // is blue -- one device table per (device, which_tables, in_order).  Like the file's other lazily built tables (get_kscale, pb_table) the FIRST use of a pair does a
 // blocking hipMalloc + hipMemcpy outside `stream` (a stream capture must have met the pair before it begins), and the eight 12 KB tables live until the process ends.
-namespace lgpu { int cavg_forms_checked(); }      // palette.hip: cavg_arith against the table form, all 65,536 pairs, once per device
-int get_sink_tables(int which_tables, int in_order, const uint2 **out) {      // (not static: flat.hip's sinks take the same tables)
+int get_sink_tables(int which_tables, int in_order, const uint2 **out) {     // (not static: flat.hip's sinks take the same tables)
   static std::mutex mu;
   static std::map<std::tuple<int, int, int>, uint2 *> tabs;
   int dev = 0;
@@ -3017,24 +3044,16 @@ extern "C" int lgpu_chain_to_yuv(const lgpu_chain_params *pr, const lgpu_chain_s
   }
   if ((rc = check_plane_sizes(fn, {(long long)pr->sh * pr->irow, (long long)pr->dh * sk->orow[0], noblend ? 0 : (long long)pr->dh * pr->irow2}))) return rc;
   hipStream_t st = (hipStream_t)stream;
+  PbHalfForm f = {noblend ? 2 : 1, 0, 0, 0, pr->swap_rb ? 1 : 0, 0, 0, planar ? 2 : 1};
   PbPin pin;
-  if ((rc = pb_table(interp, pr->sw, pr->sh, pr->dw, pr->dh, st, &pin))) return rc;
-  PbHalfArgs a;
-  if (!pb_half_ok(pin.t, interp, pr->sw, pr->sh, pr->dw, pr->dh, sb, lb, &a.hyper, &a.ashift)) {
-    set_error("lgpu_chain_to_yuv: the scaler's table is not the exact 2:1 outer product");
-    return LGPU_E_UNSUPPORTED;
-  }
   PbSinkDst S;
-  if (planar && (rc = cavg_forms_checked())) return rc;
-  if ((rc = get_sink_tables(sk->which_tables, sk->in_order, &S.tab))) return rc;
-  if ((rc = get_kscale(&a.kscale))) return rc;
-  a.sw = pr->sw; a.sh = pr->sh; a.irow = pr->irow; a.dw = pr->dw; a.dh = pr->dh; a.orow = sk->orow[0];
-  a.swap_rb = pr->swap_rb ? 1 : 0; a.blend = 1; a.irow2 = noblend ? pr->irow : pr->irow2; a.use_lut = pr->use_lut ? 1 : 0;
-  a.bf = 0; a.bf_d = nullptr; a.bf_tracks = amounts ? 1 : 0; a.nt_out = 1;
-  pb_half_geometry(&a, ntracks);
-  // Launch-shape switches: PBH_TH and PBH_OCC are honoured; PBH_ALIGNED = 0 is OVERRIDDEN (the sink form exists on strips of 64 quads only: a quad of lanes must
-  // start on an 8-byte luma boundary); PBH_ORDER and PBH_GROUP are NOT consulted -- the work order is pb_chain_half's default for the launch's size.
-  if (!a.aligned) { a.aligned = 1; a.strips = (int)cdiv((unsigned)a.dw, 128u); a.cgroups = (a.strips + 3) / 4; }
+  const uint2 *kscale;
+  if ((rc = pb_half_tables(fn, "", pr, sb, lb, sk, st, &f, &pin, &kscale, &S.tab))) return rc;
+  PbHalfArgs a = pb_half_args(f.chain, pr->sw, pr->sh, pr->irow, pr->dw, pr->dh, sk->orow[0], f.hyper, f.swap, noblend ? pr->irow : pr->irow2, pr->use_lut ? 1 : 0, kscale,
+                              amounts ? 1 : 0);
+  // Launch-shape switches: PBH_TH and PBH_OCC are honoured; PBH_ALIGNED = 0 is overridden (pb_half_geometry); PBH_ORDER and PBH_GROUP are NOT consulted -- the
+  // work order is pb_chain_half's default for the launch's size.
+  pb_half_geometry(&a, ntracks, &f);
   S.pairs = pb_half_shape(&a, ntracks, nullptr, planar);
   PbTracks T;
   for (int i = 0; i < ntracks; i++) {
@@ -3042,21 +3061,10 @@ extern "C" int lgpu_chain_to_yuv(const lgpu_chain_params *pr, const lgpu_chain_s
     S.u[i] = planar ? tracks[i].dst_d[1] : nullptr; S.v[i] = planar ? tracks[i].dst_d[2] : nullptr;
   }
   pb_fill_sink(&S, sk);
-  const Lut8 l = pack_lut(pr->use_lut ? pr->lut8 : nullptr);
-  const dim3 grid((unsigned)a.main_blocks);
   // pb_chain_half's five workgroups per CU for launches of more than one generation, less the 12 KB of static LDS the sink's tables take, so that the count stays
   // what it was (5 x (14.25 KB static + 17 KB dynamic) fits 160 KB, six do not)
   const size_t occ_lds = pb_half_occ_lds(a, ntracks, true, 3072 + sizeof(PbSinkLds<1>));
-#define PBS_LAUNCH(CH, HY, SW, SK) hipLaunchKernelGGL((k_pb_half<CH, HY, 0, 1, SW, 0, 0, SK>), grid, dim3(256), occ_lds, st, a, T, l, S)
-#define PBS_SWAP(CH, HY, SK) do { if (a.swap_rb) PBS_LAUNCH(CH, HY, 1, SK); else PBS_LAUNCH(CH, HY, 0, SK); } while (0)
-#define PBS_HYPER(CH, SK) do { if (a.hyper) PBS_SWAP(CH, 1, SK); else PBS_SWAP(CH, 0, SK); } while (0)
-  if (planar) { if (noblend) PBS_HYPER(2, 2); else PBS_HYPER(1, 2); }
-  else { if (noblend) PBS_HYPER(2, 1); else PBS_HYPER(1, 1); }
-#undef PBS_HYPER
-#undef PBS_SWAP
-#undef PBS_LAUNCH
-  LGPU_CHECK_LAUNCH();
-  return LGPU_OK;
+  return pb_half_launch(f, dim3((unsigned)a.main_blocks), occ_lds, st, a, T, pack_lut(pr->use_lut ? pr->lut8 : nullptr), S);
 }
 
 // lgpu_chain_yuv420p_to_yuv: both ends at once -- K2's conversion in registers -> the exact 2:1 scaler (all-opaque arithmetic) [-> chroma blend with layer 2] [-> gamma
@@ -3098,29 +3106,19 @@ extern "C" int lgpu_chain_yuv420p_to_yuv(const lgpu_chain_params *pr, const lgpu
   if ((rc = check_plane_sizes(fn, {(long long)pr->sh * lys, ys->u_size, ys->v_size, (long long)pr->dh * sk->orow[0], noblend ? 0 : (long long)pr->dh * pr->irow2},
                               "lgpu_chain_yuv420p + lgpu_rgb_to_yuv_batch"))) return rc;
   hipStream_t st = (hipStream_t)stream;
+  PbHalfForm f = {noblend ? 2 : 1, 0, 0, 0, chain_order, 1, 1, planar ? 2 : 1};
   PbPin pin;
-  if ((rc = pb_table(interp, pr->sw, pr->sh, pr->dw, pr->dh, st, &pin))) return rc;
-  PbHalfArgs a;
-  if (!pb_half_ok(pin.t, interp, pr->sw, pr->sh, pr->dw, pr->dh, 0, lb, &a.hyper, &a.ashift)) {
-    set_error("lgpu_chain_yuv420p_to_yuv: the scaler's table is not the exact 2:1 outer product (lgpu_chain_yuv420p + lgpu_rgb_to_yuv_batch)");
-    return LGPU_E_UNSUPPORTED;
-  }
   PbYuvSink Y;
-  if ((rc = pb_opaque_check())) return rc;
-  if (planar && (rc = cavg_forms_checked())) return rc;
-  if ((rc = get_sink_tables(sk->which_tables, sk->in_order, &Y.s.tab))) return rc;
-  if ((rc = get_kscale(&a.kscale))) return rc;
-  a.sw = pr->sw; a.sh = pr->sh; a.irow = lys; a.dw = pr->dw; a.dh = pr->dh; a.orow = sk->orow[0];
-  a.swap_rb = chain_order; a.blend = 1; a.irow2 = noblend ? sk->orow[0] : pr->irow2; a.use_lut = pr->use_lut ? 1 : 0;
-  a.bf = 0; a.bf_d = nullptr; a.bf_tracks = 1; a.nt_out = 1;
+  const uint2 *kscale;
+  if ((rc = pb_half_tables(fn, " (lgpu_chain_yuv420p + lgpu_rgb_to_yuv_batch)", pr, 0, lb, sk, st, &f, &pin, &kscale, &Y.s.tab))) return rc;
+  PbHalfArgs a = pb_half_args(f.chain, pr->sw, pr->sh, lys, pr->dw, pr->dh, sk->orow[0], f.hyper, f.swap, noblend ? sk->orow[0] : pr->irow2, pr->use_lut ? 1 : 0, kscale, 1);
   pb_fill_yuv_src(&Y.y, ys);
   pb_fill_sink(&Y.s, sk);
   const Lut8 l = pack_lut(pr->use_lut ? pr->lut8 : nullptr);
   // kPbTranscodeTracks tracks per launch (the kernel arguments, PbYuvSink's comment): a longer tick goes as two launches on the stream
   for (int t0 = 0; t0 < ntracks; t0 += kPbTranscodeTracks) {
     const int n = std::min(kPbTranscodeTracks, ntracks - t0);
-    // the 4:2:0 sink walks strips of 60 storing lanes (whole quads of k per wave, k_pb_half's comment); the packed sinks keep the source form's 62
-    pb_half_geometry(&a, n, 0, 0, 1, planar ? 120 : 0);
+    pb_half_geometry(&a, n, &f);
     Y.s.pairs = pb_half_shape(&a, n, nullptr, planar);
     PbTracks T;
     for (int i = 0; i < n; i++) {
@@ -3129,17 +3127,8 @@ extern "C" int lgpu_chain_yuv420p_to_yuv(const lgpu_chain_params *pr, const lgpu
       Y.y.u[i] = t.u_d; Y.y.v[i] = t.v_d;
       Y.s.u[i] = planar ? t.dst_d[1] : nullptr; Y.s.v[i] = planar ? t.dst_d[2] : nullptr;
     }
-    const dim3 grid((unsigned)a.main_blocks);
     // no dynamic LDS, as lgpu_chain_yuv420p: the registers hold this form to five waves per SIMD or fewer (docs/KERNELS.md)
-#define PBT_LAUNCH(CH, HY, SW, SK) hipLaunchKernelGGL((k_pb_half<CH, HY, 0, 0, SW, 1, 1, SK>), grid, dim3(256), 0, st, a, T, l, Y)
-#define PBT_SWAP(CH, HY, SK) do { if (a.swap_rb) PBT_LAUNCH(CH, HY, 1, SK); else PBT_LAUNCH(CH, HY, 0, SK); } while (0)
-#define PBT_HYPER(CH, SK) do { if (a.hyper) PBT_SWAP(CH, 1, SK); else PBT_SWAP(CH, 0, SK); } while (0)
-    if (planar) { if (noblend) PBT_HYPER(2, 2); else PBT_HYPER(1, 2); }
-    else { if (noblend) PBT_HYPER(2, 1); else PBT_HYPER(1, 1); }
-#undef PBT_HYPER
-#undef PBT_SWAP
-#undef PBT_LAUNCH
-    LGPU_CHECK_LAUNCH();
+    if ((rc = pb_half_launch(f, dim3((unsigned)a.main_blocks), 0, st, a, T, l, Y))) return rc;
   }
   return LGPU_OK;
 }
