@@ -617,6 +617,36 @@ int lgpu_chain_flat_yuv422(const lgpu_chain_params *params, const lgpu_yuv422_so
                            const lgpu_chain_yuv_sink_track *tracks /* packed: y_d is the frame, u_d / v_d NULL */, int ntracks,
                            const uint8_t *amounts, void *stream);
 
+/* the transition between two decoded frames of ANY of the four decoded formats, still ONE launch and still no RGBA frame anywhere: a camera or capture card
+   (UYVY / YUYV) fading into a decoded clip, two MJPEG / DV / 4:2:2-intermediate clips (YUV422P), a 4:2:0 clip into a 4:2:2 one.  Each layer has its own
+   lgpu_yuv_layer_source; both are sw x sh.  The bytes are DEFINED as those of two steps.
+   Step 1, layer 2 through the single-frame call of src2->in_fmt into a tight sw x sh RGBA frame of rowstride 4 * sw:
+     4 (YUV420P): lgpu_yuv420p_to_rgb(.., opsize 4, src2->out_order, is_422 = 0, src2->which_tables, src2->pb_quality, no LUT, src2->flags);
+     5 (YUV422P): the same call with is_422 = 1 and flags 0;
+     2 / 3 (UYVY / YUYV): lgpu_yuv_to_rgb(.., src2->in_fmt, in_alpha 0, .., src2->out_order, out_alpha 1, src2->which_tables);
+   src2->out_order must be src->out_order ^ params->swap_rb, the byte order the blend works in (the rule of lgpu_chain_flat_yuv420p_mix).
+   Step 2, today's one-launch form of src->in_fmt with that frame as layer 2 (sink == NULL: RGBA into dst_d[0], rowstride params->orow):
+     4: lgpu_chain_flat_yuv420p[_to_yuv];   2 / 3 / 5: lgpu_chain_flat_yuv422.
+   So every quirk of K2's 4:2:0 walk, of K2's 4:2:2 walk (the first pair of row i seeded from chroma row i >> 1, the read one past a row's end the next row's first
+   sample or clamped to THAT layer's u_size / v_size) and of K3's macropixel conversion holds on either layer, and every K4 quirk behind them.  pb_quality and flags
+   are checked for every format and change nothing where the single-frame call ignores them (4:2:2 and packed).  With in_fmt 4 on both layers the call gives the bytes
+   of lgpu_chain_flat_yuv420p_mix.  The tracks are lgpu_chain_yuv_mix_track: a packed layer is its y_d / y2_d with rowstride istrides[0]; its two chroma pointers are
+   not read and may be NULL.  params->irow2 is not read.  YVU on either layer or on the sink: pass the planes swapped.  Layer 2's pointers may be layer 1's.
+   LGPU_E_BADARG: what lgpu_chain_flat_yuv420p_mix and lgpu_chain_flat_yuv422 call a bad argument, for either source under its own format (numbers out of range,
+   unknown flags, strides or chroma planes too small for the format, which_tables & 2 with a packed layer, another src2->out_order); an in_fmt outside 2..5; a null
+   plane that the layer's format reads; a destination plane that is one of the planes either layer reads; LGPU_INTERP_NOBLEND; null amounts; 0 or 65 tracks.
+   LGPU_E_UNSUPPORTED: sw != dw or sh != dh, do_blur, out_fmt 5, an odd dh with out_fmt 4, the sinks' store-alignment classes, a packed layer (1 or 2) whose plane or
+   rowstride is not a multiple of 4 (a macropixel is one 4-byte load), planes of 2 GiB or more on either layer.  Nothing is enqueued or written in either case.  No
+   canvas, as in lgpu_chain_flat_yuv420p_mix.  LGPU_CHAIN_MIX_TRACKS tracks per launch, 33..64 as two launches on `stream`.  With a sink, the first call with a new
+   (sink->which_tables, sink->in_order) pair builds a device table outside `stream`, as in lgpu_chain_to_yuv. */
+typedef struct { int in_fmt;              /* 2 UYVY, 3 YUYV, 4 YUV420P, 5 YUV422P */
+                 int istrides[3];         /* packed: [0] only */
+                 long u_size, v_size;     /* planar: chroma plane bytes; packed: ignored */
+                 int out_order, which_tables, pb_quality, flags; } lgpu_yuv_layer_source;
+int lgpu_chain_flat_yuv_mix(const lgpu_chain_params *params, const lgpu_yuv_layer_source *src, const lgpu_yuv_layer_source *src2,
+                            const lgpu_chain_sink *sink /* NULL: RGBA into dst_d[0], rowstride params->orow */,
+                            const lgpu_chain_yuv_mix_track *tracks, int ntracks, const uint8_t *amounts, void *stream);
+
 /* ---- timing helper: HIP events on `stream` around `reps` launches of the last-configured chain; used by
    bench.py to measure the kernel's average launch duration on the stream it is launched on. */
 int lgpu_chain_timed(const lgpu_chain_params *params, const lgpu_chain_track *tracks, int ntracks,

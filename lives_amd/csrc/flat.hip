@@ -18,6 +18,9 @@
 //
 // lgpu_chain_flat_yuv422 (the SRC policy): layer 1 is a planar 4:2:2 frame (YUV422P) or a packed one (UYVY / YUYV).  The unit walk, emit and the sink stores stay; a lane
 // converts its two pixels of each row of its unit with flat_row422 -- yuv.hip's 4:2:2 walk with the reference's seed quirk, or K3's macropixel conversion.
+//
+// lgpu_chain_flat_yuv_mix: L2YUV is layer 2's source policy as SRC is layer 1's (1 planar 4:2:0, 2 YUV422P, 3 packed), and the two combine freely: a camera fading
+// into a decoded clip, two 4:2:2 clips in a transition, a 4:2:0 clip into a 4:2:2 one -- each one launch with no RGBA frame anywhere.
 #include "lgpu_common.h"
 #include <algorithm>
 #include <string.h>
@@ -50,8 +53,8 @@ template <int NT, int NDST> struct FlatTracksT {
   uint8_t *dst[NDST][NT];
   uint8_t bf[NT];
 };
-// L2YUV: layer 2 is a decoded 4:2:0 frame too (lgpu_chain_flat_yuv420p_mix).  Its description travels with the tracks, so FlatArgs and the argument layout of the
-// L2YUV = 0 instantiations stay what they were
+// L2YUV: layer 2 is a decoded frame too (lgpu_chain_flat_yuv420p_mix, lgpu_chain_flat_yuv_mix).  Its description travels with the tracks, so FlatArgs and the argument
+// layout of the L2YUV = 0 instantiations stay what they were
 template <int NT, int NDST> struct FlatMixTracksT {
   const uint8_t *y[NT], *u[NT], *v[NT], *y2[NT], *u2[NT], *v2[NT];
   uint8_t *dst[NDST][NT];
@@ -61,15 +64,25 @@ template <int NT, int NDST> struct FlatMixTracksT {
   int ys2, us2, vs2;
   int clamped2, lowq2, fix_edges2;
 };
-template <int SINK, int L2YUV = 0> struct FlatTr { typedef FlatTracksT<LGPU_CHAIN_MAX_TRACKS, 1> type; };
+// L2YUV == 3: layer 2's packed format rides at the tail, so no offset of the planar forms moves (theirs is the struct above, as it was)
+template <int NT, int NDST> struct FlatMixTracksPackedT : FlatMixTracksT<NT, NDST> {
+  int sfmt2;                     // 2 UYVY, 3 YUYV (wave-uniform, as FlatArgs::sfmt is for layer 1)
+};
+// L2YUV, layer 2's source policy: 0 an RGBA frame or none, 1 planar 4:2:0, 2 planar 4:2:2 (YUV422P), 3 packed 4:2:2 (UYVY / YUYV)
+template <int SINK, int L2YUV = 0> struct FlatTr { typedef FlatMixTracksT<LGPU_CHAIN_MIX_TRACKS, SINK == 2 ? 3 : 1> type; };
+template <int SINK> struct FlatTr<SINK, 0> { typedef FlatTracksT<LGPU_CHAIN_MAX_TRACKS, 1> type; };
 template <> struct FlatTr<2, 0> { typedef FlatTracksT<kFlatPlanarTracks, 3> type; };
-template <int SINK> struct FlatTr<SINK, 1> { typedef FlatMixTracksT<LGPU_CHAIN_MIX_TRACKS, SINK == 2 ? 3 : 1> type; };
+template <int SINK> struct FlatTr<SINK, 3> { typedef FlatMixTracksPackedT<LGPU_CHAIN_MIX_TRACKS, SINK == 2 ? 3 : 1> type; };
 template <int SINK> struct FlatSinkLds { uint2 t[6 * 256]; };
 template <> struct FlatSinkLds<0> {};
-template <int L2YUV> struct FlatL2Lds { uint32_t ty[256]; uint2 rg[256], gb[256]; };      // layer 2's own K2 tables (5 KB), staged when its which_tables differs
+template <int NT, int NDST> static inline void set_sfmt2(FlatMixTracksT<NT, NDST> &, int) {}
+template <int NT, int NDST> static inline void set_sfmt2(FlatMixTracksPackedT<NT, NDST> &T, int sfmt2) { T.sfmt2 = sfmt2; }
+template <int L2YUV> struct FlatL2Lds { uint32_t ty[256]; uint2 rg[256], gb[256]; };      // layer 2's own K2 tables (5 KB), staged when its table set or index clamp differs
 template <> struct FlatL2Lds<0> {};
 static_assert(sizeof(FlatArgs) + sizeof(FlatTr<0>::type) + sizeof(Lut8) <= 4096 && sizeof(FlatArgs) + sizeof(FlatTr<2>::type) + sizeof(Lut8) <= 4096 &&
-              sizeof(FlatArgs) + sizeof(FlatTr<0, 1>::type) + sizeof(Lut8) <= 4096 && sizeof(FlatArgs) + sizeof(FlatTr<2, 1>::type) + sizeof(Lut8) <= 4096,
+              sizeof(FlatArgs) + sizeof(FlatTr<0, 1>::type) + sizeof(Lut8) <= 4096 && sizeof(FlatArgs) + sizeof(FlatTr<2, 1>::type) + sizeof(Lut8) <= 4096 &&
+              sizeof(FlatArgs) + sizeof(FlatTr<0, 2>::type) + sizeof(Lut8) <= 4096 && sizeof(FlatArgs) + sizeof(FlatTr<2, 2>::type) + sizeof(Lut8) <= 4096 &&
+              sizeof(FlatArgs) + sizeof(FlatTr<0, 3>::type) + sizeof(Lut8) <= 4096 && sizeof(FlatArgs) + sizeof(FlatTr<2, 3>::type) + sizeof(Lut8) <= 4096,
               "HIP documents 4 KB of arguments for a __global__ function");
 
 // an address or pitch as a multiple of n (a power of two).  Every alignment decision of this file goes through it, in the kernel and in the entry points;
@@ -86,8 +99,8 @@ struct FlatPlanes {
 struct FlatK2Lds { const uint32_t *ty; const uint2 *rg, *gb; };
 template <int KIND> struct FlatCell { static constexpr int value = KIND; };      // 0: row 0, 1: a row pair, 2: the trailing row
 
-// K2's walk for cell (unit, k) of one layer: its two pixels of one row or its 2 x 2 quad go to out(FlatCell<KIND>, first row, chroma row, p0, p1, second row's p0, p1).  Both layers
-// of the L2YUV form come through here, each with its own planes and tables
+// K2's walk for cell (unit, k) of one layer: its two pixels of one row or its 2 x 2 quad go to out(FlatCell<KIND>, first row, chroma row, p0, p1, second row's p0, p1).  Either layer
+// of the L2YUV forms comes through here when it is planar 4:2:0, each with its own planes and tables
 template <int SWAP, class Out>
 __device__ __forceinline__ void flat_cell(const FlatPlanes &P, const FlatK2Lds &L, int unit, int k, int hw, int H, int npairs, Out &&out) {
   const uint8_t *py = P.y, *pu = P.u, *pv = P.v;
@@ -158,7 +171,7 @@ __device__ __forceinline__ void flat_cell(const FlatPlanes &P, const FlatK2Lds &
   }
 }
 
-// one row's pixel pair of cell k of a 4:2:2 frame (the SRC policies of k_flat_yuv420).
+// one row's pixel pair of cell k of a 4:2:2 frame (the SRC policies of k_flat_yuv420 for layer 1, L2YUV - 1 for layer 2).
 // SRC == 1, planar (YUV422P): yuv.hip's yuv422_cell walk (:3593-3640 / :3858-3901).  "this / last" are seeded from chroma row i >> 1 (reference), so the first pair of a
 // row takes its left samples from there; the read one past a row's end is the next row's first sample or is clamped to the plane's last byte; pb_quality and
 // LGPU_YUV_FIX_EDGES change nothing in this walk.  THE 4:2:2 SEED QUIRK IS NOW WRITTEN DOWN TWICE (yuv.hip yuv422_cell / k_yuv420p_to_rgb_s<.., V422>, and here): a quirk
@@ -222,14 +235,15 @@ __device__ __forceinline__ void flat_cell422(const FlatPlanes &P, const FlatK2Ld
   }
 }
 
-// SINK: 0 RGBA, 1 packed 4:2:2 (UYVY / YUYV), 2 planar 4:2:0.  SWAP: the finished pixel is BGRA (src->out_order ^ params->swap_rb).  L2YUV: layer 2 is a 4:2:0 frame
-// of the same size (BLEND is 1, no canvas): the lane converts ITS cell of layer 2 first, with the same walk, keeps the two or four finished pixels and only then
-// walks layer 1, so the temporaries of the two walks are never live together.  Layer 2's alpha is 255 by construction: the blend is the opaque one.
+// SINK: 0 RGBA, 1 packed 4:2:2 (UYVY / YUYV), 2 planar 4:2:0.  SWAP: the finished pixel is BGRA (src->out_order ^ params->swap_rb).  L2YUV: layer 2 is a decoded frame
+// of the same size (BLEND is 1, no canvas) -- 1 planar 4:2:0, 2 planar 4:2:2, 3 packed 4:2:2 (T.sfmt2: UYVY / YUYV; T.y2 is the frame, T.u2 / T.v2 are not read): the
+// lane converts ITS cell of layer 2 first, with that format's walk, keeps the two or four finished pixels and only then walks layer 1, so the temporaries of the
+// two walks are never live together.  Layer 2's alpha is 255 by construction: the blend is the opaque one.  L2YUV and SRC combine freely.
 // SRC: layer 1 is 0 planar 4:2:0, 1 planar 4:2:2 (YUV422P), 2 packed 4:2:2 (A.sfmt: UYVY / YUYV; T.y is the frame, T.u / T.v are not read).  The units, emit and
 // the chroma-row stores are the same for all three: a 4:2:2 lane owns two pixels of each row of its unit too (flat_cell422)
 template <int BLEND, int SWAP, int SINK, int L2YUV = 0, int SRC = 0>
 __global__ __launch_bounds__(256) void k_flat_yuv420(const FlatArgs A, const typename FlatTr<SINK, L2YUV>::type T, const Lut8 lut) {
-  static_assert(SRC >= 0 && SRC <= 2 && !(SRC && L2YUV), "layer 2 of the mix form is a 4:2:0 frame beside a 4:2:0 layer 1");
+  static_assert(SRC >= 0 && SRC <= 2 && L2YUV >= 0 && L2YUV <= 3, "SRC: 0 4:2:0, 1 YUV422P, 2 packed; L2YUV: 0 RGBA or none, then the same three as SRC + 1");
   __shared__ uint32_t s_ty[256];
   __shared__ uint2 s_rg[256], s_gb[256];
   __shared__ __attribute__((aligned(16))) uint8_t s_lut[256];
@@ -331,9 +345,12 @@ __global__ __launch_bounds__(256) void k_flat_yuv420(const FlatArgs A, const typ
       const FlatPlanes P2 = {T.y2[z], T.u2[z], T.v2[z], T.usize2, T.vsize2, T.ys2, T.us2, T.vs2, T.lowq2, T.fix_edges2};
       const bool own = T.tables2 != nullptr;      // wave-uniform
       const FlatK2Lds L2 = {own ? s_l2.ty : s_ty, own ? s_l2.rg : s_rg, own ? s_l2.gb : s_gb};
-      flat_cell<SWAP>(P2, L2, unit, k, hw, H, npairs, [&](auto, int, int, uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1) __attribute__((always_inline)) {
+      auto keep = [&](auto, int, int, uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1) __attribute__((always_inline)) {
         q[0] = a0; q[1] = a1; q[2] = b0; q[3] = b1;
-      });
+      };
+      if constexpr (L2YUV == 1) flat_cell<SWAP>(P2, L2, unit, k, hw, H, npairs, keep);
+      else if constexpr (L2YUV == 2) flat_cell422<SWAP, 1>(P2, L2, 0, unit, k, H, npairs, keep);
+      else flat_cell422<SWAP, 2>(P2, L2, T.sfmt2, unit, k, H, npairs, keep);
     }
     auto rows = [&](auto cell, int i, int r, uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1) __attribute__((always_inline)) {
       constexpr int kind = decltype(cell)::value;
@@ -360,12 +377,12 @@ __global__ __launch_bounds__(256) void k_flat_yuv420(const FlatArgs A, const typ
 
 using namespace lgpu;
 
-// all four entry points: tracks in the sink form's layout (the RGBA form's destination is dst_d[0]); cv or sk is null.  ys2 / mix: the second source and the
-// caller's tracks of lgpu_chain_flat_yuv420p_mix (layer 2's planes are read from them; tracks[].layer2_d is null then), null otherwise.  sfmt: layer 1's format,
-// 4 planar 4:2:0, 5 planar 4:2:2, 2 UYVY, 3 YUYV (lgpu_chain_flat_yuv422; a packed frame is tracks[].y_d with rowstride ys->istrides[0], the rest of ys unread)
+// all five entry points: tracks in the sink form's layout (the RGBA form's destination is dst_d[0]); cv or sk is null.  ys2 / mix: the second source and the
+// caller's tracks of the mix forms (layer 2's planes are read from them; tracks[].layer2_d is null then), null otherwise.  sfmt / sfmt2: each layer's format,
+// 4 planar 4:2:0, 5 planar 4:2:2, 2 UYVY, 3 YUYV (a packed frame is y_d / y2_d with rowstride istrides[0]; the entry points zero the rest of its source)
 static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv_source *ys, const lgpu_canvas *cv, const lgpu_chain_sink *sk,
                      const lgpu_chain_yuv_sink_track *tracks, int ntracks, const uint8_t *amounts, void *stream, const lgpu_yuv_source *ys2 = nullptr,
-                     const lgpu_chain_yuv_mix_track *mix = nullptr, int sfmt = 4) {
+                     const lgpu_chain_yuv_mix_track *mix = nullptr, int sfmt = 4, int sfmt2 = 4) {
 #define FLAT_REQUIRE(cond, msg) do { if (!(cond)) { set_error("%s: %s", fn, msg); return LGPU_E_BADARG; } } while (0)
 #define FLAT_REFUSE(msg) do { set_error("%s: %s", fn, msg); return LGPU_E_UNSUPPORTED; } while (0)
   const bool noblend = (pr->interp & LGPU_INTERP_NOBLEND) != 0;
@@ -375,26 +392,33 @@ static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv
   FLAT_REQUIRE(amounts || noblend, "null amounts");
   const bool packed = sfmt == 2 || sfmt == 3;
   const int srcp = packed ? 2 : sfmt == 5 ? 1 : 0;      // the kernel's SRC policy
+  const bool packed2 = ys2 && (sfmt2 == 2 || sfmt2 == 3);
+  const int l2p = !ys2 ? 0 : packed2 ? 3 : sfmt2 == 5 ? 2 : 1;      // the kernel's L2YUV policy
   const int hw = pr->sw >> 1, lys = ys->istrides[0], us = packed ? 0 : ys->istrides[1], vs = packed ? 0 : ys->istrides[2];
   const long usz = packed ? 0 : ys->u_size, vsz = packed ? 0 : ys->v_size;
   int rc;
-  if ((rc = check_yuv_source(fn, pr, ys, sfmt)) || (ys2 && (rc = check_yuv_source(fn, pr, ys2, sfmt)))) return rc;
+  if ((rc = check_yuv_source(fn, pr, ys, sfmt)) || (ys2 && (rc = check_yuv_source(fn, pr, ys2, sfmt2)))) return rc;
   const int chain_order = (ys->out_order ^ (pr->swap_rb ? 1 : 0)) & 1;
   FLAT_REQUIRE(!ys2 || ys2->out_order == chain_order, "src2->out_order must state the byte order the blend works in: src->out_order ^ params->swap_rb");
   const bool planar = sk && sk->out_fmt >= 4;
   const int nplanes = planar ? 3 : 1;
   const int cw = cv && !sk ? cv->nwidth : pr->dw, ch = cv && !sk ? cv->nheight : pr->dh;
   if ((rc = sk ? check_yuv_sink(fn, pr, sk, chain_order, l2rgba) : check_rgba_dest(fn, pr, cv, l2rgba))) return rc;
-  uintptr_t pb = 0, sb = 0;
+  uintptr_t pb = 0, sb = 0, sb2 = 0;
   for (int i = 0; i < ntracks; i++) {
     const lgpu_chain_yuv_sink_track &t = tracks[i];
     const uint8_t *const planes[3] = {t.y_d, t.u_d, t.v_d};
     if ((rc = check_track(fn, planes, packed ? 1 : 3, false, t.layer2_d, l2rgba, t.dst_d, nplanes, !sk))) return rc;
     sb |= (uintptr_t)t.y_d;
-    FLAT_REQUIRE(!mix || (mix[i].y2_d && mix[i].u2_d && mix[i].v2_d), "null layer-2 plane");
-    for (int k = 0; k < nplanes; k++)
-      FLAT_REQUIRE(!mix || ((const uint8_t *)t.dst_d[k] != mix[i].y2_d && (const uint8_t *)t.dst_d[k] != mix[i].u2_d && (const uint8_t *)t.dst_d[k] != mix[i].v2_d),
-                   "a destination plane is one of layer 2's planes");
+    if (mix) {
+      // a packed layer 2 is y2_d alone: its chroma pointers are not read, so they may be null and are no plane a destination could collide with
+      const uint8_t *const u2 = packed2 ? nullptr : mix[i].u2_d, *const v2 = packed2 ? nullptr : mix[i].v2_d;
+      FLAT_REQUIRE(mix[i].y2_d && (packed2 || (u2 && v2)), "null layer-2 plane");
+      for (int k = 0; k < nplanes; k++)
+        FLAT_REQUIRE((const uint8_t *)t.dst_d[k] != mix[i].y2_d && (const uint8_t *)t.dst_d[k] != u2 && (const uint8_t *)t.dst_d[k] != v2,
+                     "a destination plane is one of layer 2's planes");
+      sb2 |= (uintptr_t)mix[i].y2_d;
+    }
     pb |= (uintptr_t)t.dst_d[0];
   }
   // the one-launch form; anything else is refused, never run some other way
@@ -405,6 +429,7 @@ static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv
   if (pr->do_blur) FLAT_REFUSE("the gaussian is not offered with a 4:2:0 or 4:2:2 source");
   // K3 reads a macropixel as one aligned dword; the reference divides that rowstride by 4 (docs/QUIRKS.md, K3-c): there is no behaviour to follow elsewhere
   if (packed && !multiple_of(sb | (uintptr_t)lys, 4)) FLAT_REFUSE("a UYVY / YUYV source is read as 4-byte macropixels (plane and rowstride % 4 == 0)");
+  if (packed2 && !multiple_of(sb2 | (uintptr_t)ys2->istrides[0], 4)) FLAT_REFUSE("a UYVY / YUYV layer 2 is read as 4-byte macropixels (plane and rowstride % 4 == 0)");
   if (sk) {
     if (sk->out_fmt == 5) FLAT_REFUSE("YUV422P is not served (lgpu_chain_flat_yuv420p + lgpu_rgb_to_yuv_batch)");
     if (planar && (pr->dh & 1)) FLAT_REFUSE("the 4:2:0 sink needs an even height");
@@ -451,8 +476,10 @@ static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv
     const unsigned bar_gy = bar_px > 0 ? (unsigned)std::min<long long>(64, (bar_px + 1024ll * gx - 1) / (1024ll * gx)) : 0u;
     const dim3 grid(gx, (unsigned)gy + bar_gy, (unsigned)n);
     if (ys2) {
-      // L2YUV: one staged copy of the K2 tables serves both layers when the sources name the same set
-      const bool own = (ys2->which_tables & 3) != (ys->which_tables & 3);
+      // L2YUV: one staged copy of the K2 tables serves both layers when they index the same set the same way.  A planar layer with clamped tables indexes rg / gb
+      // through the 16..240 clamp that staging folds into the index, a packed layer with the sample itself: UYVY over YUV420P, both with which_tables 0, needs two copies
+      const int clamped2 = !packed2 && !(ys2->which_tables & 1);
+      const bool own = (ys2->which_tables & 3) != (ys->which_tables & 3) || clamped2 != a.clamped;
       auto fill = [&](auto &T) {
         for (int i = 0; i < n; i++) {
           const lgpu_chain_yuv_mix_track &t = mix[t0 + i];
@@ -461,17 +488,25 @@ static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv
         }
         T.tables2 = own ? device_tables()->yuv2rgb[ys2->which_tables & 3] : nullptr;
         T.usize2 = (uint32_t)ys2->u_size; T.vsize2 = (uint32_t)ys2->v_size; T.ys2 = ys2->istrides[0]; T.us2 = ys2->istrides[1]; T.vs2 = ys2->istrides[2];
-        T.clamped2 = !(ys2->which_tables & 1); T.lowq2 = ys2->pb_quality == 1; T.fix_edges2 = (ys2->flags & LGPU_YUV_FIX_EDGES) ? 1 : 0;
+        T.clamped2 = clamped2; T.lowq2 = ys2->pb_quality == 1; T.fix_edges2 = (ys2->flags & LGPU_YUV_FIX_EDGES) ? 1 : 0;
       };
-#define FLAT_MIX_LAUNCH(SK) do {                                                                                                             \
-        FlatTr<SK, 1>::type T;                                                                                                               \
+      // THE dispatch point of the mix forms: 3 sinks x SRC x L2YUV x SWAP, the six of lgpu_chain_flat_yuv420p_mix (SRC 0, L2YUV 1) among them
+#define FLAT_MIX_LAUNCH_L2(SK, SR, L2) do {                                                                                                  \
+        FlatTr<SK, L2>::type T;                                                                                                              \
         memset(&T, 0, sizeof T);                                                                                                             \
         fill(T);                                                                                                                             \
-        if (chain_order) hipLaunchKernelGGL((k_flat_yuv420<1, 1, SK, 1>), grid, dim3(256), 0, st, a, T, l);                                 \
-        else hipLaunchKernelGGL((k_flat_yuv420<1, 0, SK, 1>), grid, dim3(256), 0, st, a, T, l);                                             \
+        set_sfmt2(T, sfmt2);                                                                                                                 \
+        if (chain_order) hipLaunchKernelGGL((k_flat_yuv420<1, 1, SK, L2, SR>), grid, dim3(256), 0, st, a, T, l);                            \
+        else hipLaunchKernelGGL((k_flat_yuv420<1, 0, SK, L2, SR>), grid, dim3(256), 0, st, a, T, l);                                        \
       } while (0)
+#define FLAT_MIX_LAUNCH_SRC(SK, SR) do {                                                                                                     \
+        if (l2p == 3) FLAT_MIX_LAUNCH_L2(SK, SR, 3); else if (l2p == 2) FLAT_MIX_LAUNCH_L2(SK, SR, 2); else FLAT_MIX_LAUNCH_L2(SK, SR, 1);   \
+      } while (0)
+#define FLAT_MIX_LAUNCH(SK) do { if (srcp == 2) FLAT_MIX_LAUNCH_SRC(SK, 2); else if (srcp == 1) FLAT_MIX_LAUNCH_SRC(SK, 1); else FLAT_MIX_LAUNCH_SRC(SK, 0); } while (0)
       if (planar) FLAT_MIX_LAUNCH(2); else if (sk) FLAT_MIX_LAUNCH(1); else FLAT_MIX_LAUNCH(0);
 #undef FLAT_MIX_LAUNCH
+#undef FLAT_MIX_LAUNCH_SRC
+#undef FLAT_MIX_LAUNCH_L2
     } else if (planar) {
       FlatTr<2>::type T;
       for (int i = 0; i < n; i++) {
@@ -554,4 +589,33 @@ extern "C" int lgpu_chain_flat_yuv422(const lgpu_chain_params *pr, const lgpu_yu
   ys.u_size = packed ? 0 : s4->u_size; ys.v_size = packed ? 0 : s4->v_size;
   ys.out_order = s4->out_order; ys.which_tables = s4->which_tables; ys.pb_quality = s4->pb_quality;
   return flat_impl("lgpu_chain_flat_yuv422", pr, &ys, cv, sk, tracks, ntracks, amounts, stream, nullptr, nullptr, s4->in_fmt);
+}
+
+// lgpu_chain_flat_yuv_mix: each track's layer 2 converted by the single-frame call of ITS format (lgpu_yuv420p_to_rgb with is_422 0 / 1, lgpu_yuv_to_rgb) into a tight
+// RGBA frame + the one-launch form of layer 1's format with that frame as layer 2, as ONE launch per LGPU_CHAIN_MIX_TRACKS tracks and with no RGBA frame anywhere;
+// every argument is checked before anything is enqueued.  With in_fmt 4 on both layers it is lgpu_chain_flat_yuv420p_mix, the same six instantiations
+extern "C" int lgpu_chain_flat_yuv_mix(const lgpu_chain_params *pr, const lgpu_yuv_layer_source *s1, const lgpu_yuv_layer_source *s2, const lgpu_chain_sink *sk,
+                                       const lgpu_chain_yuv_mix_track *tracks, int ntracks, const uint8_t *amounts, void *stream) {
+  int rc = ensure_init();
+  if (rc) return rc;
+  LGPU_REQUIRE(pr && s1 && s2 && tracks && ntracks > 0 && ntracks <= LGPU_CHAIN_MAX_TRACKS, "params, both sources and 1..64 tracks required");
+  LGPU_REQUIRE(s1->in_fmt >= 2 && s1->in_fmt <= 5 && s2->in_fmt >= 2 && s2->in_fmt <= 5, "in_fmt must be 2 (UYVY), 3 (YUYV), 4 (YUV420P) or 5 (YUV422P) on either layer");
+  // one layer's description as flat_impl reads it; what a packed layer does not have is zero
+  auto source_of = [](const lgpu_yuv_layer_source *s) {
+    lgpu_yuv_source ys;
+    memset(&ys, 0, sizeof ys);
+    const bool packed = s->in_fmt < 4;
+    ys.istrides[0] = s->istrides[0]; ys.istrides[1] = packed ? 0 : s->istrides[1]; ys.istrides[2] = packed ? 0 : s->istrides[2];
+    ys.u_size = packed ? 0 : s->u_size; ys.v_size = packed ? 0 : s->v_size;
+    ys.out_order = s->out_order; ys.which_tables = s->which_tables; ys.pb_quality = s->pb_quality; ys.flags = s->flags;
+    return ys;
+  };
+  const lgpu_yuv_source ys = source_of(s1), ys2 = source_of(s2);
+  const bool packed1 = s1->in_fmt < 4;
+  lgpu_chain_yuv_sink_track tr[LGPU_CHAIN_MAX_TRACKS];
+  for (int i = 0; i < ntracks; i++) {
+    tr[i].y_d = tracks[i].y_d; tr[i].u_d = packed1 ? nullptr : tracks[i].u_d; tr[i].v_d = packed1 ? nullptr : tracks[i].v_d; tr[i].layer2_d = nullptr;
+    for (int k = 0; k < 3; k++) tr[i].dst_d[k] = tracks[i].dst_d[k];
+  }
+  return flat_impl("lgpu_chain_flat_yuv_mix", pr, &ys, nullptr, sk, tr, ntracks, amounts, stream, &ys2, tracks, s1->in_fmt, s2->in_fmt);
 }

@@ -78,6 +78,11 @@ class Yuv422Source(ctypes.Structure):
     _fields_ = [("in_fmt", ci), ("istrides", ci * 3), ("u_size", cl), ("v_size", cl), ("out_order", ci), ("which_tables", ci), ("pb_quality", ci)]
 
 
+class YuvLayerSource(ctypes.Structure):
+    """lgpu_yuv_layer_source"""
+    _fields_ = [("in_fmt", ci), ("istrides", ci * 3), ("u_size", cl), ("v_size", cl), ("out_order", ci), ("which_tables", ci), ("pb_quality", ci), ("flags", ci)]
+
+
 class Canvas(ctypes.Structure):
     """lgpu_canvas"""
     _fields_ = [("nwidth", ci), ("nheight", ci), ("offs_x", ci), ("offs_y", ci)]
@@ -219,6 +224,7 @@ PROTOTYPES = {
     "lgpu_chain_flat_yuv420p_to_yuv": [vp, vp, vp, vp, ci, vp, vp],
     "lgpu_chain_flat_yuv420p_mix": [vp, vp, vp, vp, vp, ci, vp, vp],
     "lgpu_chain_flat_yuv422": [vp, vp, vp, vp, vp, ci, vp, vp],
+    "lgpu_chain_flat_yuv_mix": [vp, vp, vp, vp, vp, ci, vp, vp],
     "lgpu_pixbuf_scale_check": [ci, ci, ci, ci, ci, ci, vp],
     "lgpu_pixbuf_scale_batch": [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp],
     "lgpu_fx_batch": [ctypes.POINTER(FxParams), ctypes.POINTER(FxFrame), ci, vp],

@@ -576,13 +576,14 @@ def chain_flat_yuv422(params, src, tracks, amounts, sink=None, canvas=None, chec
 
 
 def chain_yuv_mix_tracks(ys, us, vs, y2s, u2s, v2s, dst_planes):
-    """lgpu_chain_yuv_mix_track[]: the planes of each track's two 4:2:0 layers (u / v swapped for YVU420P, per layer) and its destination planes (one tensor for RGBA /
-    UYVY / YUYV; Y, U, V for YUV420P -- the chroma planes swapped for YVU420P)"""
+    """lgpu_chain_yuv_mix_track[]: the planes of each track's two layers (u / v swapped for YVU, per layer; None for both: a packed frame, which is the y plane --
+    lgpu_chain_flat_yuv_mix) and its destination planes (one tensor for RGBA / UYVY / YUYV; Y, U, V for YUV420P -- the chroma planes swapped for YVU420P)"""
     n = len(ys)
     arr = (lib.ChainYuvMixTrack * n)()
     for i in range(n):
-        arr[i].y_d, arr[i].u_d, arr[i].v_d = ys[i].data_ptr(), us[i].data_ptr(), vs[i].data_ptr()
-        arr[i].y2_d, arr[i].u2_d, arr[i].v2_d = y2s[i].data_ptr(), u2s[i].data_ptr(), v2s[i].data_ptr()
+        arr[i].y_d, arr[i].y2_d = ys[i].data_ptr(), y2s[i].data_ptr()
+        arr[i].u_d, arr[i].v_d = (us[i].data_ptr(), vs[i].data_ptr()) if us is not None else (None, None)
+        arr[i].u2_d, arr[i].v2_d = (u2s[i].data_ptr(), v2s[i].data_ptr()) if u2s is not None else (None, None)
         for k, t in enumerate(dst_planes[i]):
             arr[i].dst_d[k] = t.data_ptr()
     return arr
@@ -597,6 +598,27 @@ def chain_flat_yuv420p_mix(params, src, src2, tracks, amounts, sink=None, check=
     if not check:
         return lib.load().lgpu_chain_flat_yuv420p_mix(*args)
     return lib.call("lgpu_chain_flat_yuv420p_mix", *args)
+
+
+def yuv_layer_source(in_fmt, istrides, u_size=0, v_size=0, out_order=0, which_tables=0, pb_quality=2, flags=0):
+    """lgpu_yuv_layer_source: in_fmt 4 YUV420P / 5 YUV422P (three rowstrides, the chroma planes' sizes) / 2 UYVY / 3 YUYV (one rowstride)"""
+    s = lib.YuvLayerSource()
+    s.in_fmt = in_fmt
+    for k, v in enumerate(istrides):
+        s.istrides[k] = int(v)
+    s.u_size, s.v_size, s.out_order, s.which_tables, s.pb_quality, s.flags = u_size, v_size, out_order, which_tables, pb_quality, flags
+    return s
+
+
+def chain_flat_yuv_mix(params, src, src2, tracks, amounts, sink=None, check=True):
+    """lgpu_chain_flat_yuv_mix: two decoded frames of the project's size, each YUV420P, YUV422P, UYVY or YUYV, mixed in one launch, to RGBA (sink=None, rowstride
+    params.orow) or to a YUV sink; no RGBA frame anywhere.  src / src2: yuv_layer_source (src2.out_order is src.out_order ^ params.swap_rb); tracks:
+    chain_yuv_mix_tracks (a packed frame is the y plane; u / v None).  check=False returns the library's code instead of raising (tests of the refusals)"""
+    am = (ctypes.c_uint8 * max(1, len(tracks)))(*[int(a) & 0xFF for a in amounts]) if amounts is not None else None
+    args = (ctypes.byref(params), ctypes.byref(src), ctypes.byref(src2), ctypes.byref(sink) if sink is not None else None, tracks, len(tracks), am, stream_ptr())
+    if not check:
+        return lib.load().lgpu_chain_flat_yuv_mix(*args)
+    return lib.call("lgpu_chain_flat_yuv_mix", *args)
 
 
 def stream_probe(params, tracks, reps):
