@@ -14,8 +14,11 @@ for f in runtime swizzle yuv effects resize stencil palette pixbuf fused flat; d
     pids+=($!)
   fi
 done
-for f in host_tables layer_seam dist; do
-  if [ -f $f.cpp ] && { [ ! -f $OBJ/$f.o ] || [ $f.cpp -nt $OBJ/$f.o ] || [ ../../include/lives_gpu.h -nt $OBJ/$f.o ]; }; then
+# the layer seam's units (layer_seam.cpp and seam_*.cpp) share the internal headers seam_*.h: a newer one rebuilds them all
+for f in host_tables layer_seam seam_weed seam_resident seam_lazy dist; do
+  stale=
+  case $f in layer_seam|seam_*) for h in seam_*.h ../../include/lives_gpu_layer.h; do [ $h -nt $OBJ/$f.o ] && stale=1; done ;; esac
+  if [ -f $f.cpp ] && { [ ! -f $OBJ/$f.o ] || [ $f.cpp -nt $OBJ/$f.o ] || [ ../../include/lives_gpu.h -nt $OBJ/$f.o ] || [ -n "$stale" ]; }; then
     g++ -O2 -std=c++17 -fPIC -fno-fast-math -ffp-contract=off -Wall -c $f.cpp -o $OBJ/$f.o &
     pids+=($!)
   fi

@@ -2770,7 +2770,7 @@ static int pb_scale_n(const uint8_t *const *srcs, uint8_t *const *dsts, int n, i
 
 // what lgpu_pixbuf_scale would answer for this geometry, without launching anything (the weight table is built and cached on the way, so the scale that follows
 // finds it): LGPU_OK, LGPU_E_BADARG, or LGPU_E_UNSUPPORTED for a reduction past the library's one-step range.  The layer seam asks before it records a scale
-// for later (deferred execution, layer_seam.cpp): a recorded call must not turn into a refusal.
+// for later (deferred execution, seam_lazy.h; resize_pixbuf_body in layer_seam.cpp): a recorded call must not turn into a refusal.
 int lgpu::pb_scale_fused(const uint8_t *const *srcs, uint8_t *const *dsts, int n, int irow, int sw, int sh, int orow, int dw, int dh, int interp, hipStream_t st, const PbEpi *epi) {
   return pb_scale_n(srcs, dsts, n, irow, sw, sh, orow, dw, dh, 4, interp, (void *)st, epi);
 }

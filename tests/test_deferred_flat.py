@@ -19,7 +19,7 @@ pytestmark = [needs_ref, pytest.mark.gpu]
 RGBA32, BGRA32, YUV420P, YVU420P, UYVY, YUYV = 3, 4, 512, 513, 564, 565
 CLAMPED, UNCLAMPED = 0, 1
 NSTATS = 15
-# the sink formats lives_gpu_set_flat_yuv(1) routes to the one launch (layer_seam.cpp, FLAT_SINK_FORMATS: those tools/bench_flat_chain.py shows ahead of today's
+# the sink formats lives_gpu_set_flat_yuv(1) routes to the one launch (seam_lazy.cpp, FLAT_SINK_FORMATS: those tools/bench_flat_chain.py shows ahead of today's
 # three launches, profiles/r11/flat_chain.md: 157.2 us against 274.2 to UYVY, 159.7 against 271.7 to YUV420P, spreads below 1 us -- all taken); YUV420P: 32 tracks per launch
 FLAT_SINK = {UYVY: True, YUYV: True, YUV420P: True, YVU420P: True}
 

@@ -23,7 +23,7 @@ SINK_LEAVES = ("current_palette", "width", "height", "YUV_clamping", "YUV_subspa
 SINKS = [YUV420P, YVU420P, UYVY, YUYV]
 # the seam's choice per sink format: True -- a group in the one-launch form runs as lgpu_chain_yuv420p_to_yuv.  profiles/r09/transcode_chain.md (16 x 4K -> 1080p, blend
 # + LUT): to UYVY the one launch takes 214.3 us against 244.7 for lgpu_chain_yuv420p + lgpu_rgb_to_yuv_batch (spread 0.2 us) and the seam takes it, for YUYV too (the same
-# kernel instantiation); to YUV420P it takes 258.9 us against 243.4 (spread 1.9 us), so the seam keeps the two launches for the planar sinks (layer_seam.cpp,
+# kernel instantiation); to YUV420P it takes 258.9 us against 243.4 (spread 1.9 us), so the seam keeps the two launches for the planar sinks (seam_lazy.cpp,
 # lazy_run_sink) and the counters below expect that; the planar launch itself is held against the oracle in tests/test_chain_transcode.py
 FUSED = {YUV420P: False, YVU420P: False, UYVY: True, YUYV: True}
 PER_LAUNCH = 32            # LGPU_CHAIN_TRANSCODE_TRACKS: tracks per launch of lgpu_chain_yuv420p_to_yuv (the counters count launches)
