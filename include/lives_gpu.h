@@ -637,7 +637,7 @@ int lgpu_chain_flat_yuv422(const lgpu_chain_params *params, const lgpu_yuv422_so
    plane that the layer's format reads; a destination plane that is one of the planes either layer reads; LGPU_INTERP_NOBLEND; null amounts; 0 or 65 tracks.
    LGPU_E_UNSUPPORTED: sw != dw or sh != dh, do_blur, out_fmt 5, an odd dh with out_fmt 4, the sinks' store-alignment classes, a packed layer (1 or 2) whose plane or
    rowstride is not a multiple of 4 (a macropixel is one 4-byte load), planes of 2 GiB or more on either layer.  Nothing is enqueued or written in either case.  No
-   canvas, as in lgpu_chain_flat_yuv420p_mix.  LGPU_CHAIN_MIX_TRACKS tracks per launch, 33..64 as two launches on `stream`.  With a sink, the first call with a new
+   canvas here (lgpu_chain_flat_yuv_mix_canvas below takes one, to RGBA).  LGPU_CHAIN_MIX_TRACKS tracks per launch, 33..64 as two launches on `stream`.  With a sink, the first call with a new
    (sink->which_tables, sink->in_order) pair builds a device table outside `stream`, as in lgpu_chain_to_yuv. */
 typedef struct { int in_fmt;              /* 2 UYVY, 3 YUYV, 4 YUV420P, 5 YUV422P */
                  int istrides[3];         /* packed: [0] only */
@@ -646,6 +646,22 @@ typedef struct { int in_fmt;              /* 2 UYVY, 3 YUYV, 4 YUV420P, 5 YUV422
 int lgpu_chain_flat_yuv_mix(const lgpu_chain_params *params, const lgpu_yuv_layer_source *src, const lgpu_yuv_layer_source *src2,
                             const lgpu_chain_sink *sink /* NULL: RGBA into dst_d[0], rowstride params->orow */,
                             const lgpu_chain_yuv_mix_track *tracks, int ntracks, const uint8_t *amounts, void *stream);
+/* the same transition LETTERBOXED: two decoded frames whose aspect is not the project's, both sw x sh and both at (offs_x, offs_y) on one canvas of opaque black,
+   still ONE launch (the bars included) and still no RGBA frame anywhere.  RGBA only: there is no sink with a canvas, as in lgpu_chain_flat_yuv422.  The bytes are
+   DEFINED as those of three steps.
+   Step 1, layer 2 through the single-frame call of src2->in_fmt into a tight sw x sh RGBA frame, exactly as lgpu_chain_flat_yuv_mix defines it.
+   Step 1b, that frame letterboxed onto opaque black: lgpu_letterbox_at(.., sw, sh, .., nwidth, nheight, 4, {0, 0, 0, 255}, offs_x, offs_y) into a tight
+   nwidth x nheight frame.
+   Step 2, the one-launch form of src->in_fmt (4: lgpu_chain_flat_yuv420p; 2 / 3 / 5: lgpu_chain_flat_yuv422) with `canvas` and that frame as layer 2.
+   So a bar pixel is the chroma blend of opaque black with opaque black under the track's amount, then the LUT.  params->irow2 is not read; the destination is dst_d[0]
+   with rowstride params->orow, canvas-sized; dst_d[1], dst_d[2] are not read.  Any offs_x (8-byte stores where the address allows, 4-byte ones elsewhere).
+   canvas == NULL: the bytes of lgpu_chain_flat_yuv_mix without a sink.  LGPU_E_BADARG: what lgpu_chain_flat_yuv_mix (sink == NULL) calls a bad argument; a frame that
+   does not lie inside the canvas; params->orow below the canvas row or not a multiple of 4.  LGPU_E_UNSUPPORTED: what lgpu_chain_flat_yuv_mix refuses (planes of
+   2 GiB or more: the canvas-sized destination counts).  Nothing is enqueued or written in either case.  LGPU_CHAIN_MIX_TRACKS tracks per launch, 33..64 as two
+   launches on `stream`. */
+int lgpu_chain_flat_yuv_mix_canvas(const lgpu_chain_params *params, const lgpu_yuv_layer_source *src, const lgpu_yuv_layer_source *src2,
+                                   const lgpu_canvas *canvas /* NULL: lgpu_chain_flat_yuv_mix without a sink */,
+                                   const lgpu_chain_yuv_mix_track *tracks, int ntracks, const uint8_t *amounts, void *stream);
 
 /* ---- timing helper: HIP events on `stream` around `reps` launches of the last-configured chain; used by
    bench.py to measure the kernel's average launch duration on the stream it is launched on. */

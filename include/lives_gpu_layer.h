@@ -175,6 +175,25 @@ int lives_gpu_set_deferred(int on);
    lgpu_yuv420p_to_rgb_batch (is_422) / lgpu_yuv_to_rgb_batch into scratch and the RGBA paths: the 2:1 YUV chains are 4:2:0 only (tests/test_deferred_flat422.py).
    With the switch off nothing is recorded for these palettes.  A process-wide setting like lives_gpu_set_deferred. */
 int lives_gpu_set_flat_yuv(int on);
+/* opt-in (0 = off, the default; returns the previous mode; process-wide like the two setters above): the second layer of a recorded "chroma blend" may STAY a
+   pending program.  Off, lives_gpu_deferred_blend_chroma runs a pending layer 2 the moment the blend is recorded -- alone, on the calling thread -- which is what
+   every decoded layer 2 is (its convert_layer_palette was recorded): a tick of 16 transitions between decoded clips is 16 one-frame launches plus one chain launch.
+   On (1, 2 or 3), a layer 2 that is a pending program with no blend and no sink of its own, standing for a plane of the blend's width, height and rowstride, is NOT
+   run: the blend is recorded against it, it counts the reader as a resident plane does, and it is still read as it was when the blend was called -- no further stage
+   can be recorded on it while it has readers; whoever needs its pixels or changes, replaces or releases it runs it and then its readers first.  A flush (or whoever
+   runs a reader alone) then takes one of two routes for a group of readers of one shape whose layer-2 programs have one shape too.
+   FOLD, ONE launch per 32 tracks (lgpu_chain_flat_yuv_mix, to RGBA or to a UYVY / YUYV / YUV420P / YVU420P sink; lgpu_chain_flat_yuv_mix_canvas when both layers were
+   letterboxed onto the same canvas at the same place): lives_gpu_set_flat_yuv(1) is on and LGPU_SEAM_STAGED off; layer 1 is a YUV program that keeps its size; layer
+   2 is a YUV conversion alone, or that conversion plus the letterbox; both frames have one size; layer 2 was converted to the byte order the blend works in (layer
+   1's target, swapped when layer 1 has an R <-> B stage); no sink behind a canvas.  The layer-2 programs are NOT run by this: they STAY pending, with one reader
+   fewer, also when their layers were listed in the flush, and run only if somebody asks for their pixels (a layer nobody looks at again costs nothing).
+   LAYER 2 FIRST, TWO launches whatever the shape: everything else, and whatever the mix entry points refuse.  The distinct layer-2 programs of the group run as
+   groups of THEIR shape ahead of their readers -- one batched conversion, one lgpu_chain_yuv420p launch without a blend for a 2:1 group, ... -- and become resident
+   planes; the readers then take the routes they take today.  A flush finds the layer-2 programs through their readers, listed or not.
+   Mode 1 folds the pairs of formats for which the one launch was measured ahead of the two by more than the latter's round-to-round spread (seam_lazy.cpp,
+   MIX_FOLD_PAIRS; profiles/r17/seam_transition.md: none so far, the two forms are within each other's spread, so mode 1 runs the second layers first); mode 2 folds every pair the one-launch forms take and mode 3 none (tests and sweeps).  Same bytes in every mode (tests/test_deferred_mix.py).  A
+   device error leaves readers, layer 2 and reader counts as they were. */
+int lives_gpu_set_pending_layer2(int mode);
 int lives_gpu_layers_flush(lives_gpu_layer_t *const *layers, int nlayers);
 /* counters since load: [0] stages recorded, [1] fused chain launches made for pending programs, [2] programs (tracks) those carried, [3] programs run stage by stage */
 void lives_gpu_deferred_stats(unsigned long long out[4]);
@@ -186,9 +205,13 @@ void lives_gpu_deferred_stats(unsigned long long out[4]);
    each is also counted in [1], [5], [9] and [11] with its tracks in [2], [6] and [10], and makes no pre-launch [7]), [13] launches of the unscaled one-launch forms
    (lives_gpu_set_flat_yuv(1): lgpu_chain_flat_yuv420p, also counted in [1]; lgpu_chain_flat_yuv420p_to_yuv, also counted in [1], [9] and [11]; lgpu_chain_flat_yuv422
    from YUV422P / UYVY / YUYV layers, counted as whichever of the two it stands for, its conversions in [4] and its batched fallback conversions in [7]; no pre-launch [7]) and
-   [14] the tracks they carried; at most n entries are written (callers that pass n = 12 or 13 see what they saw before) */
+   [14] the tracks they carried; lives_gpu_set_pending_layer2: [15] blends recorded against a pending layer 2, [16] mix launches (lgpu_chain_flat_yuv_mix[_canvas]; each is
+   also counted in [1] and [13], and with a sink in [9] and [11]) and [17] the tracks they carried, [18] layer-2 programs run ahead of their readers (by the route
+   "layer 2 first"; one that ran because somebody asked for its pixels is not counted); 19 entries exist and at most n are written (callers that pass n <= 15 see what
+   they saw before) */
 void lives_gpu_deferred_stats_n(unsigned long long *out, int n);
-/* (for livesgpu_fx.so) record an in-place "chroma blend" of the pending plane dst_host with the resident plane layer2_host; 1 = recorded, 0 = run the kernel */
+/* (for livesgpu_fx.so) record an in-place "chroma blend" of the pending plane dst_host with the resident plane layer2_host (a pending one runs first, or -- under
+   lives_gpu_set_pending_layer2 -- stays pending); 1 = recorded, 0 = run the kernel */
 int lives_gpu_deferred_blend_chroma(const void *dst_host, int orow, int width, int height, int palette, const void *layer2_host, int irow2, int bf);
 /* the host is about to free or replace the pixel_data of a pinned layer itself (weed_layer_pixel_data_free, an error path): release the
    device copies without a download and clear the leaf.  Device copies are keyed by host plane pointer, so this (or unpin) MUST precede

@@ -236,7 +236,7 @@ __device__ __forceinline__ void flat_cell422(const FlatPlanes &P, const FlatK2Ld
 }
 
 // SINK: 0 RGBA, 1 packed 4:2:2 (UYVY / YUYV), 2 planar 4:2:0.  SWAP: the finished pixel is BGRA (src->out_order ^ params->swap_rb).  L2YUV: layer 2 is a decoded frame
-// of the same size (BLEND is 1, no canvas) -- 1 planar 4:2:0, 2 planar 4:2:2, 3 packed 4:2:2 (T.sfmt2: UYVY / YUYV; T.y2 is the frame, T.u2 / T.v2 are not read): the
+// of the same size (BLEND is 1; with a canvas, lgpu_chain_flat_yuv_mix_canvas, both layers sit at the same place on it) -- 1 planar 4:2:0, 2 planar 4:2:2, 3 packed 4:2:2 (T.sfmt2: UYVY / YUYV; T.y2 is the frame, T.u2 / T.v2 are not read): the
 // lane converts ITS cell of layer 2 first, with that format's walk, keeps the two or four finished pixels and only then walks layer 1, so the temporaries of the
 // two walks are never live together.  Layer 2's alpha is 255 by construction: the blend is the opaque one.  L2YUV and SRC combine freely.
 // SRC: layer 1 is 0 planar 4:2:0, 1 planar 4:2:2 (YUV422P), 2 packed 4:2:2 (A.sfmt: UYVY / YUYV; T.y is the frame, T.u / T.v are not read).  The units, emit and
@@ -252,9 +252,10 @@ __global__ __launch_bounds__(256) void k_flat_yuv420(const FlatArgs A, const typ
   const int tid = threadIdx.x, z = blockIdx.z;
   const uint32_t bf = BLEND ? (uint32_t)T.bf[z] : 0u, nbf = 255u - bf;
   stage_lut(s_lut, lut);
-  if constexpr (SINK == 0 && !L2YUV) {
+  if constexpr (SINK == 0) {
     if ((int)blockIdx.y >= A.gy_units) {
-      // letterbox bars (letterbox_layer's black canvas under the rest of the chain): opaque black [-> chroma blend with layer 2] [-> LUT]
+      // letterbox bars (letterbox_layer's black canvas under the rest of the chain): opaque black [-> chroma blend with layer 2] [-> LUT].  L2YUV: layer 2 is
+      // letterboxed onto the same canvas, so its bar pixel is opaque black too and nothing is read
       __syncthreads();
       const int bb = ((int)blockIdx.y - A.gy_units) * (int)gridDim.x + (int)blockIdx.x, nbb = ((int)gridDim.y - A.gy_units) * (int)gridDim.x;
       const int top = A.oy * A.cw, bottom = (A.ch - A.oy - A.h) * A.cw, sw_ = A.cw - A.w, total = top + bottom + A.h * sw_;
@@ -264,7 +265,8 @@ __global__ __launch_bounds__(256) void k_flat_yuv420(const FlatArgs A, const typ
         else if (q < top + bottom) { q -= top; y = q / A.cw; x = q - y * A.cw; y += A.oy + A.h; }
         else { q -= top + bottom; y = q / sw_; x = q - y * sw_; y += A.oy; if (x >= A.ox) x += A.w; }
         uint32_t c = 0xFF000000u;
-        if (BLEND) c = pb_chroma_rgba(c, reinterpret_cast<const uint32_t *>(T.l2[z] + (size_t)y * A.irow2)[x], bf, nbf);
+        if constexpr (L2YUV) c = pb_chroma_opaque(c, 0xFF000000u, bf, nbf);
+        else if (BLEND) c = pb_chroma_rgba(c, reinterpret_cast<const uint32_t *>(T.l2[z] + (size_t)y * A.irow2)[x], bf, nbf);
         if (A.use_lut) c = lut3_rgba(s_lut, c);
         reinterpret_cast<uint32_t *>(T.dst[0][z] + (size_t)y * A.orow)[x] = c;
       }
@@ -377,8 +379,8 @@ __global__ __launch_bounds__(256) void k_flat_yuv420(const FlatArgs A, const typ
 
 using namespace lgpu;
 
-// all five entry points: tracks in the sink form's layout (the RGBA form's destination is dst_d[0]); cv or sk is null.  ys2 / mix: the second source and the
-// caller's tracks of the mix forms (layer 2's planes are read from them; tracks[].layer2_d is null then), null otherwise.  sfmt / sfmt2: each layer's format,
+// all six entry points: tracks in the sink form's layout (the RGBA form's destination is dst_d[0]); cv or sk is null.  ys2 / mix: the second source and the
+// caller's tracks of the mix forms (layer 2's planes are read from them; tracks[].layer2_d is null then), null otherwise; with cv both layers are letterboxed onto it.  sfmt / sfmt2: each layer's format,
 // 4 planar 4:2:0, 5 planar 4:2:2, 2 UYVY, 3 YUYV (a packed frame is y_d / y2_d with rowstride istrides[0]; the entry points zero the rest of its source)
 static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv_source *ys, const lgpu_canvas *cv, const lgpu_chain_sink *sk,
                      const lgpu_chain_yuv_sink_track *tracks, int ntracks, const uint8_t *amounts, void *stream, const lgpu_yuv_source *ys2 = nullptr,
@@ -593,13 +595,16 @@ extern "C" int lgpu_chain_flat_yuv422(const lgpu_chain_params *pr, const lgpu_yu
 
 // lgpu_chain_flat_yuv_mix: each track's layer 2 converted by the single-frame call of ITS format (lgpu_yuv420p_to_rgb with is_422 0 / 1, lgpu_yuv_to_rgb) into a tight
 // RGBA frame + the one-launch form of layer 1's format with that frame as layer 2, as ONE launch per LGPU_CHAIN_MIX_TRACKS tracks and with no RGBA frame anywhere;
-// every argument is checked before anything is enqueued.  With in_fmt 4 on both layers it is lgpu_chain_flat_yuv420p_mix, the same six instantiations
-extern "C" int lgpu_chain_flat_yuv_mix(const lgpu_chain_params *pr, const lgpu_yuv_layer_source *s1, const lgpu_yuv_layer_source *s2, const lgpu_chain_sink *sk,
-                                       const lgpu_chain_yuv_mix_track *tracks, int ntracks, const uint8_t *amounts, void *stream) {
+// every argument is checked before anything is enqueued.  With in_fmt 4 on both layers it is lgpu_chain_flat_yuv420p_mix, the same six instantiations.
+// lgpu_chain_flat_yuv_mix_canvas: the same with both layers letterboxed onto one canvas (cv, RGBA only), the bars written by the same launch
+static int flat_mix(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv_layer_source *s1, const lgpu_yuv_layer_source *s2, const lgpu_canvas *cv,
+                    const lgpu_chain_sink *sk, const lgpu_chain_yuv_mix_track *tracks, int ntracks, const uint8_t *amounts, void *stream) {
   int rc = ensure_init();
   if (rc) return rc;
-  LGPU_REQUIRE(pr && s1 && s2 && tracks && ntracks > 0 && ntracks <= LGPU_CHAIN_MAX_TRACKS, "params, both sources and 1..64 tracks required");
-  LGPU_REQUIRE(s1->in_fmt >= 2 && s1->in_fmt <= 5 && s2->in_fmt >= 2 && s2->in_fmt <= 5, "in_fmt must be 2 (UYVY), 3 (YUYV), 4 (YUV420P) or 5 (YUV422P) on either layer");
+#define MIX_REQUIRE(cond, msg) do { if (!(cond)) { set_error("%s: %s", fn, msg); return LGPU_E_BADARG; } } while (0)
+  MIX_REQUIRE(pr && s1 && s2 && tracks && ntracks > 0 && ntracks <= LGPU_CHAIN_MAX_TRACKS, "params, both sources and 1..64 tracks required");
+  MIX_REQUIRE(s1->in_fmt >= 2 && s1->in_fmt <= 5 && s2->in_fmt >= 2 && s2->in_fmt <= 5, "in_fmt must be 2 (UYVY), 3 (YUYV), 4 (YUV420P) or 5 (YUV422P) on either layer");
+#undef MIX_REQUIRE
   // one layer's description as flat_impl reads it; what a packed layer does not have is zero
   auto source_of = [](const lgpu_yuv_layer_source *s) {
     lgpu_yuv_source ys;
@@ -617,5 +622,13 @@ extern "C" int lgpu_chain_flat_yuv_mix(const lgpu_chain_params *pr, const lgpu_y
     tr[i].y_d = tracks[i].y_d; tr[i].u_d = packed1 ? nullptr : tracks[i].u_d; tr[i].v_d = packed1 ? nullptr : tracks[i].v_d; tr[i].layer2_d = nullptr;
     for (int k = 0; k < 3; k++) tr[i].dst_d[k] = tracks[i].dst_d[k];
   }
-  return flat_impl("lgpu_chain_flat_yuv_mix", pr, &ys, nullptr, sk, tr, ntracks, amounts, stream, &ys2, tracks, s1->in_fmt, s2->in_fmt);
+  return flat_impl(fn, pr, &ys, cv, sk, tr, ntracks, amounts, stream, &ys2, tracks, s1->in_fmt, s2->in_fmt);
+}
+extern "C" int lgpu_chain_flat_yuv_mix(const lgpu_chain_params *pr, const lgpu_yuv_layer_source *s1, const lgpu_yuv_layer_source *s2, const lgpu_chain_sink *sk,
+                                       const lgpu_chain_yuv_mix_track *tracks, int ntracks, const uint8_t *amounts, void *stream) {
+  return flat_mix("lgpu_chain_flat_yuv_mix", pr, s1, s2, nullptr, sk, tracks, ntracks, amounts, stream);
+}
+extern "C" int lgpu_chain_flat_yuv_mix_canvas(const lgpu_chain_params *pr, const lgpu_yuv_layer_source *s1, const lgpu_yuv_layer_source *s2, const lgpu_canvas *cv,
+                                              const lgpu_chain_yuv_mix_track *tracks, int ntracks, const uint8_t *amounts, void *stream) {
+  return flat_mix("lgpu_chain_flat_yuv_mix_canvas", pr, s1, s2, cv, nullptr, tracks, ntracks, amounts, stream);
 }

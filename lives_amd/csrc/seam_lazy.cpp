@@ -1,7 +1,7 @@
 // seam_lazy.cpp -- deferred programs (seam_lazy.h; the rationale stands there, "deferred execution on pinned layers"): recording a stage on a plane's pending
 // program, routing a group of programs of one shape to the one-launch forms of the frame-level API (lives_gpu.h) and running what those refuse stage by stage;
-// and the public entry points about programs: lives_gpu_set_deferred, lives_gpu_set_flat_yuv, lives_gpu_deferred_stats[_n], lives_gpu_layers_flush,
-// lives_gpu_deferred_blend_chroma.
+// and the public entry points about programs: lives_gpu_set_deferred, lives_gpu_set_flat_yuv, lives_gpu_set_pending_layer2, lives_gpu_deferred_stats[_n],
+// lives_gpu_layers_flush, lives_gpu_deferred_blend_chroma.
 #include <stdint.h>
 #include <string.h>
 #include <algorithm>
@@ -21,6 +21,8 @@ std::atomic<unsigned long long> g_lz_yuv_recorded{0}, g_lz_yuv_launches{0}, g_lz
 std::atomic<unsigned long long> g_lz_sink_recorded{0}, g_lz_sink_launches{0}, g_lz_sink_tracks{0}, g_lz_sink_fused{0};    // lives_gpu_deferred_stats_n [8..11]
 std::atomic<unsigned long long> g_lz_transcode{0};                                                                          // lives_gpu_deferred_stats_n [12]
 std::atomic<unsigned long long> g_lz_flat_launches{0}, g_lz_flat_tracks{0};                                                     // lives_gpu_deferred_stats_n [13..14]
+std::atomic<unsigned long long> g_lz_l2_recorded{0}, g_lz_mix_launches{0}, g_lz_mix_tracks{0}, g_lz_l2_first{0};               // lives_gpu_deferred_stats_n [15..18]
+std::atomic<int> g_pending_l2{0};   // lives_gpu_set_pending_layer2: 0 a blend runs a pending layer 2 when it is recorded (today), 1 / 2 / 3 it stays pending (the flush folds by MIX_FOLD_PAIRS / always / never)
 std::atomic<int> g_flat_yuv{0};     // lives_gpu_set_flat_yuv: unscaled YUV groups take the one-launch forms of flat.hip (off until the default is flipped with the tests' expectations)
 std::mutex g_lazy_mu;               // one program (group) runs at a time; never taken with a table lock held
 
@@ -49,7 +51,22 @@ void lazy_discard(Lazy *z) {
   lazy_unread(z);
   lazy_free(z, false);
 }
-static bool lazy_same_shape(const Lazy *a, const Lazy *b) {
+// (g_lazy_mu held) the program that the pending layer 2 of z still is; nullptr: z's layer 2 is not pending -- or no longer: it has run meanwhile (somebody needed
+// its pixels), so they are taken as a blend recorded against a resident plane has them
+static Lazy *lazy_l2_program(Lazy *z) {
+  if (!z->l2pend) return nullptr;
+  Dev e;
+  const bool there = res_peek(z->l2h, &e);
+  if (there && e.lazy) return e.lazy;
+  z->l2 = there ? e : Dev();          // (no entry at all: cannot happen, a plane with readers is not dropped before they have run)
+  z->l2pend = false;
+  return nullptr;
+}
+// (g_lazy_mu held where a layer 2 is pending) one launch can carry both: the same stages on frames of the same geometry and, behind a pending layer 2, layer-2
+// programs of one shape as well
+static bool lazy_same_shape(Lazy *a, Lazy *b) {
+  Lazy *const a2 = lazy_l2_program(a), *const b2 = lazy_l2_program(b);
+  if ((a2 != nullptr) != (b2 != nullptr) || (a2 && a2 != b2 && !lazy_same_shape(a2, b2))) return false;
   return a->sw == b->sw && a->sh == b->sh && a->srs == b->srs && a->swap == b->swap && a->scale == b->scale && a->dw == b->dw && a->dh == b->dh &&
          a->interp == b->interp && a->opaque == b->opaque && a->canvas == b->canvas && a->nw == b->nw && a->nh == b->nh && a->ox == b->ox && a->oy == b->oy && a->blend == b->blend &&
          a->l2rs == b->l2rs &&          /* (not the blend amount: every track of a launch has its own, lgpu_chain_amounts) */ a->lut == b->lut && (!a->lut || !memcmp(a->lut8, b->lut8, 256)) && a->w == b->w && a->h == b->h && a->rs == b->rs &&
@@ -176,7 +193,7 @@ static void lazy_await(const Lazy *z) {
 // What a one-launch route answered: LGPU_OK -- the group is done (true) and the route's counters move: the chain's always, those of the kinds it names beside them,
 // by the call's `launches` and n tracks; LGPU_E_BADARG / LGPU_E_UNSUPPORTED -- the shape is not the form's, the next route takes the group; anything else is the
 // group's error (*rc)
-enum { RT_YUV = 1, RT_SINK = 2, RT_FLAT = 4, RT_TRANSCODE = 8 };
+enum { RT_YUV = 1, RT_SINK = 2, RT_FLAT = 4, RT_TRANSCODE = 8, RT_MIX = 16 };
 static bool lazy_route(int crc, unsigned kinds, int launches, int n, int *rc) {
   if (crc != LGPU_OK) {
     if (crc != LGPU_E_BADARG && crc != LGPU_E_UNSUPPORTED) *rc = crc;
@@ -188,6 +205,7 @@ static bool lazy_route(int crc, unsigned kinds, int launches, int n, int *rc) {
   if (kinds & RT_SINK) { g_lz_sink_launches += nl; g_lz_sink_tracks += nt; g_lz_sink_fused += nl; }
   if (kinds & RT_FLAT) { g_lz_flat_launches += nl; g_lz_flat_tracks += nt; }
   if (kinds & RT_TRANSCODE) g_lz_transcode += nl;
+  if (kinds & RT_MIX) { g_lz_mix_launches += nl; g_lz_mix_tracks += nt; }
   return true;
 }
 // the RGBA stages of n programs of one shape into outp[i] (rowstride z0->rs): one fused launch where the shape allows, else stage by stage.  The routes, in order:
@@ -288,19 +306,126 @@ static int lazy_run_rgba(Lazy *const *zs, int n, uint8_t *const *outp) {
   return rc;
 }
 static int lazy_run_sink(Lazy *const *zs, int n, Dev (*souts)[3]);
+static int lazy_run_group(Lazy *const *zs, const void *const *hs, int n);
+#define FLAT_SINK_FORMATS(fmt) ((fmt) == 2 || (fmt) == 3 || (fmt) == 4)
+// Which pairs (layer 1's format f1, layer 2's format f2: 4 YUV420P, 5 YUV422P, 2 UYVY, 3 YUYV; canvas: both layers letterboxed) mode 1 of
+// lives_gpu_set_pending_layer2 folds into ONE lgpu_chain_flat_yuv_mix launch: those for which tools/bench_seam_transition.py shows the launch ahead of mode 3's two
+// launches (the second layers' batched conversion, then the readers' flat launch) by more than the round-to-round spread of the latter.
+// profiles/r17/seam_transition.md (16 x 1080p, convert -> chroma blend -> gamma, host clock around 8 ticks, five interleaved rounds; layer 2 over layer 1, one launch
+// against two, the two launches' spread): YUV420P over YUV420P 548.1 us against 557.3 (spread 123.4), UYVY over YUV420P 524.4 against 542.0 (18.4), YUV420P over
+// UYVY 530.9 against 530.2 (7.0), YUV422P over YUV422P 589.5 against 584.8 (20.1); to a UYVY sink 596.2 / 609.5 (17.3), 549.8 / 558.8 (30.7), 546.4 / 553.3 (14.8),
+// 581.0 / 584.0 (118.6); 1440x1080 letterboxed into 1920x1080, YUV420P over YUV420P, 618.4 against 635.2 (28.8).  The tick is bound by the host's calls at this
+// size, both forms are 34 to 58 us ahead of today's 17 launches and within each other's spread: NO pair is taken, mode 1 runs the second layers first for every
+// pair until a measurement tells them apart.  The pairs not timed (YUYV, YVU420P, the other cross pairs) are not taken either.
+#define MIX_FOLD_PAIRS(f1, f2, canvas) (false && (f1) && (f2) && (canvas))
+// (g_lazy_mu held) may the group zs, whose layer 2 are the pending programs z2s, run as lgpu_chain_flat_yuv_mix[_canvas]?  The mode allows the pair, the flat route
+// is on, SEAM_STAGED is off; layer 1 is a YUV program that keeps its size; layer 2 is a conversion alone, or a conversion letterboxed onto layer 1's canvas at layer
+// 1's place; both frames have one size; layer 2 was converted into the byte order the blend works in; and no sink stands behind a canvas
+static bool lazy_folds(Lazy *const *zs, Lazy *const *z2s, int n) {
+  const Lazy *z1 = zs[0], *z2 = z2s[0];
+  const int mode = g_pending_l2.load();
+  if (mode == 0 || mode == 3 || !g_flat_yuv.load() || lgpu_tuning_get("SEAM_STAGED") > 0 || n > LGPU_CHAIN_MAX_TRACKS) return false;
+  if (!z1->yuv || z1->scale || !z2->yuv || z2->scale || z2->swap || z2->lut || z2->blend || z2->sink) return false;
+  if (z1->sw != z2->sw || z1->sh != z2->sh || z2->order != (z1->order ^ (z1->swap ? 1 : 0))) return false;
+  if (z1->canvas != z2->canvas || (z1->canvas && (z1->nw != z2->nw || z1->nh != z2->nh || z1->ox != z2->ox || z1->oy != z2->oy))) return false;
+  if (z1->sink && (z1->canvas || z1->sww != z1->w || z1->shh != z1->h || !FLAT_SINK_FORMATS(z1->sfmt))) return false;
+  if (mode == 1 && !MIX_FOLD_PAIRS(z1->yfmt, z2->yfmt, z1->canvas)) return false;
+  for (int i = 1; i < n; i++) if (z2s[i] != z2 && !lazy_same_shape(z2s[i], const_cast<Lazy *>(z2))) return false;
+  return true;
+}
+static lgpu_yuv_layer_source lazy_layer_source(const Lazy *z) {
+  lgpu_yuv_layer_source s;
+  memset(&s, 0, sizeof s);
+  s.in_fmt = z->yfmt; s.istrides[0] = z->ystr[0]; s.istrides[1] = z->ystr[1]; s.istrides[2] = z->ystr[2]; s.u_size = z->usz; s.v_size = z->vsz;
+  s.out_order = z->order; s.which_tables = z->which; s.pb_quality = z->quality;
+  return s;
+}
+// the fold: n programs of one shape and their pending layer-2 programs as ONE lgpu_chain_flat_yuv_mix (RGBA or a sink) or lgpu_chain_flat_yuv_mix_canvas per
+// LGPU_CHAIN_MIX_TRACKS tracks, into outs[track][plane].  true: done.  false with *rc == LGPU_OK: the entry point refused the shape, nothing was enqueued and the
+// layer-2 programs run first instead
+static bool lazy_run_mix(Lazy *const *zs, Lazy *const *z2s, int n, Dev (*outs)[3], int *rc) {
+  const Lazy *z0 = zs[0];
+  const int np = z0->sink ? z0->snp : 1;
+  const int row_bytes[3] = {z0->sink ? (z0->sfmt == 4 ? z0->sww : z0->sww * 2) : z0->w * 4, z0->sww >> 1, z0->sww >> 1};
+  for (int i = 0; i < n; i++) {
+    lazy_await(zs[i]);
+    await(z2s[i]->src, false); await(z2s[i]->yu, false); await(z2s[i]->yv, false);          // the launch reads layer 2's source planes on this stream
+    for (int p = 0; p < np && !*rc; p++)
+      if ((z0->sink ? z0->sors[p] : z0->rs) != row_bytes[p]) *rc = lgpu_fill(outs[i][p].d, 0, z0->sink ? z0->sbytes[p] : (size_t)z0->rs * z0->h, S());      // the row padding of a fresh plane is zero
+  }
+  if (*rc) return false;
+  const lgpu_chain_params pr = lazy_params(z0, z0->sink);
+  const lgpu_yuv_layer_source s1 = lazy_layer_source(z0), s2 = lazy_layer_source(z2s[0]);
+  const lgpu_chain_sink sk = lazy_sink(z0);
+  const lgpu_canvas cv = {z0->nw, z0->nh, z0->ox, z0->oy};
+  const std::vector<uint8_t> amounts = lazy_amounts(zs, n);
+  std::vector<lgpu_chain_yuv_mix_track> tr((size_t)n);
+  for (int i = 0; i < n; i++) {
+    lgpu_chain_yuv_mix_track &t = tr[(size_t)i];
+    memset(&t, 0, sizeof t);
+    t.y_d = (const uint8_t *)zs[i]->src.d; t.u_d = (const uint8_t *)zs[i]->yu.d; t.v_d = (const uint8_t *)zs[i]->yv.d;
+    t.y2_d = (const uint8_t *)z2s[i]->src.d; t.u2_d = (const uint8_t *)z2s[i]->yu.d; t.v2_d = (const uint8_t *)z2s[i]->yv.d;
+    for (int p = 0; p < np; p++) t.dst_d[p] = (uint8_t *)outs[i][p].d;
+  }
+  const int crc = z0->canvas ? lgpu_chain_flat_yuv_mix_canvas(&pr, &s1, &s2, &cv, tr.data(), n, amounts.data(), S())
+                             : lgpu_chain_flat_yuv_mix(&pr, &s1, &s2, z0->sink ? &sk : nullptr, tr.data(), n, amounts.data(), S());
+  if (!lazy_route(crc, RT_FLAT | RT_MIX | (z0->sink ? RT_SINK : 0), (n + LGPU_CHAIN_MIX_TRACKS - 1) / LGPU_CHAIN_MIX_TRACKS, n, rc)) return false;
+  for (int i = 0; i < n; i++) { note_use(z2s[i]->src, false); note_use(z2s[i]->yu, false); note_use(z2s[i]->yv, false); }      // (not table entries: the program owns them)
+  return true;
+}
+// layer 2 first: the distinct pending layer-2 programs of a group run as groups of THEIR shape -- one batched conversion, one lgpu_chain_yuv420p launch without a
+// blend, whatever lazy_run_group makes of them -- and become resident planes with their reader counts kept
+static int lazy_run_l2_first(Lazy *const *z2s, const void *const *l2hs, int n) {
+  std::vector<Lazy *> ps;
+  std::vector<const void *> ph;
+  for (int i = 0; i < n; i++)
+    if (z2s[i] && std::find(ps.begin(), ps.end(), z2s[i]) == ps.end()) { ps.push_back(z2s[i]); ph.push_back(l2hs[i]); }
+  std::vector<char> done(ps.size(), 0);
+  for (size_t i = 0; i < ps.size(); i++) {
+    if (done[i]) continue;
+    std::vector<Lazy *> gz;
+    std::vector<const void *> gh;
+    for (size_t k = i; k < ps.size() && (int)gz.size() < LGPU_CHAIN_MAX_TRACKS; k++)
+      if (!done[k] && (k == i || lazy_same_shape(ps[i], ps[k]))) { done[k] = 1; gz.push_back(ps[k]); gh.push_back(ph[k]); }
+    const int rc = lazy_run_group(gz.data(), gh.data(), (int)gz.size());      // (ps[i] is gz[0]: it is not looked at again)
+    if (rc) return rc;
+    g_lz_l2_first += (unsigned long long)gz.size();
+  }
+  return LGPU_OK;
+}
 // run n pending programs of ONE shape (g_lazy_mu held by the caller; hs[i]: the host plane zs[i] is registered under; a program that ends in LZ_SINK names its planes itself, Lazy::sph).  Afterwards the planes are ordinary
-// resident planes whose last writer is the calling thread's stream.
+// resident planes whose last writer is the calling thread's stream.  A group whose layer 2 is pending (Lazy::l2pend) is folded with it into one launch
+// (lazy_folds, lazy_run_mix) -- the layer-2 programs then STAY pending, with one reader fewer -- or has its layer-2 programs run first (lazy_run_l2_first)
 static int lazy_run_group(Lazy *const *zs, const void *const *hs, int n) {
   const Lazy *z0 = zs[0];
   const bool sink = z0->sink;
   const int np = sink ? z0->snp : 1;
   std::vector<Dev> outs((size_t)n * 3);                                               // [track][plane]
   int rc = LGPU_OK;
+  std::vector<Lazy *> z2s((size_t)n);
+  std::vector<const void *> l2hs((size_t)n);
+  int npend = 0;
+  for (int i = 0; i < n; i++) { z2s[(size_t)i] = lazy_l2_program(zs[i]); l2hs[(size_t)i] = zs[i]->l2h; npend += z2s[(size_t)i] ? 1 : 0; }
+  const bool fold = npend == n && lazy_folds(zs, z2s.data(), n);
+  auto l2_first = [&]() {
+    const int r = lazy_run_l2_first(z2s.data(), l2hs.data(), n);
+    if (r) return r;
+    for (int i = 0; i < n; i++) if (lazy_l2_program(zs[i])) return (int)LGPU_E_BADARG;      // (cannot happen: each has just become a resident plane)
+    npend = 0;
+    return (int)LGPU_OK;
+  };
+  if (npend && !fold) rc = l2_first();
+  if (rc) return rc;
   for (int i = 0; i < n && !rc; i++)
     for (int p = 0; p < np && !rc; p++)
       if (!pool_take(sink ? z0->sbytes[p] : (size_t)z0->rs * z0->h, &outs[(size_t)i * 3 + p])) rc = LGPU_E_NOMEM;
-  if (!rc && sink) rc = lazy_run_sink(zs, n, reinterpret_cast<Dev (*)[3]>(outs.data()));
-  else if (!rc) {
+  bool folded = false;
+  if (!rc && fold) {
+    folded = lazy_run_mix(zs, z2s.data(), n, reinterpret_cast<Dev (*)[3]>(outs.data()), &rc);
+    if (!rc && !folded) rc = l2_first();
+  }
+  if (!rc && !folded && sink) rc = lazy_run_sink(zs, n, reinterpret_cast<Dev (*)[3]>(outs.data()));
+  else if (!rc && !folded) {
     std::vector<uint8_t *> outp((size_t)n);
     for (int i = 0; i < n; i++) outp[(size_t)i] = (uint8_t *)outs[(size_t)i * 3].d;
     rc = lazy_run_rgba(zs, n, outp.data());
@@ -323,8 +448,8 @@ static int lazy_run_group(Lazy *const *zs, const void *const *hs, int n) {
       });
     }
     if (z->blend && z->l2h)
-      res_update(z->l2h, [z](Dev *l2) {
-        if (l2) { note_use(*l2, false); if (l2->lazy_readers > 0) l2->lazy_readers--; }
+      res_update(z->l2h, [z, folded](Dev *l2) {
+        if (l2) { if (!folded) note_use(*l2, false); if (l2->lazy_readers > 0) l2->lazy_readers--; }      // folded: the entry is still the program, whose source planes lazy_run_mix has marked
         z->l2h = nullptr;
       });
     for (int p = 0; p < np; p++) { Dev &o = outs[(size_t)i * 3 + p]; if (o.d) { o.stream = S(); pool_give(o); o = Dev(); } }          // (the plane vanished meanwhile: cannot happen under the host's own ordering)
@@ -336,8 +461,7 @@ static int lazy_run_group(Lazy *const *zs, const void *const *hs, int n) {
 // measurement (profiles/r08/sink_chain.md: 16 x 4K -> 1080p, blend + LUT, the fused launch 157 us against 185 for the two launches to YUV420P, 147 against 187 to
 // UYVY, rounds within 2 us of each other): whatever fits lgpu_chain_to_yuv's one-launch form takes it -- ONE launch, no RGBA frame; every other shape runs its RGBA
 // stages as the chain group into scratch frames, followed by ONE lgpu_rgb_to_yuv_batch per 16 tracks; a program of the sink stage alone is that batch on the
-// resident frames.  SEAM_STAGED: stage by stage and one conversion per track, for tests.
-#define FLAT_SINK_FORMATS(fmt) ((fmt) == 2 || (fmt) == 3 || (fmt) == 4)
+// resident frames.  SEAM_STAGED: stage by stage and one conversion per track, for tests.  (FLAT_SINK_FORMATS: above lazy_folds, which asks it too.)
 static int lazy_run_sink(Lazy *const *zs, int n, Dev (*souts)[3]) {
   const Lazy *z0 = zs[0];
   const bool staged = lgpu_tuning_get("SEAM_STAGED") > 0;
@@ -547,6 +671,10 @@ extern "C" {
 int lives_gpu_set_deferred(int on) { return g_deferred.exchange(on ? 1 : 0); }
 // unscaled YUV groups as one launch (flat.hip): off (default) / on; returns the previous setting
 int lives_gpu_set_flat_yuv(int on) { return g_flat_yuv.exchange(on ? 1 : 0); }
+// a blend's second layer may stay pending: 0 off (default: a blend runs a pending layer 2 when it is recorded), 1 on and a flush folds the pairs MIX_FOLD_PAIRS
+// names, 2 on and it folds every pair the one-launch forms take, 3 on and it never folds (the layer-2 programs run as a group ahead of their readers); returns the
+// previous mode.  Another number is taken as 0
+int lives_gpu_set_pending_layer2(int mode) { return g_pending_l2.exchange(mode >= 1 && mode <= 3 ? mode : 0); }
 // counters since the library was loaded: [0] stages recorded, [1] fused chain launches made for pending programs, [2] tracks (programs) those launches carried,
 // [3] programs run stage by stage (shapes the fused kernel does not take)
 void lives_gpu_deferred_stats(unsigned long long out[4]) {
@@ -559,14 +687,17 @@ void lives_gpu_deferred_stats(unsigned long long out[4]) {
 // RGBA frame), [12] launches that ran from YUV planes to YUV planes (lgpu_chain_yuv420p_to_yuv; each is also counted in [1], [5], [9] and [11]), [13] launches of the
 // unscaled one-launch forms (lives_gpu_set_flat_yuv: lgpu_chain_flat_yuv420p, counted in [1] too, and lgpu_chain_flat_yuv420p_to_yuv, counted in [1], [9] and [11] too;
 // lgpu_chain_flat_yuv422 from YUV422P / UYVY / YUYV layers as whichever of the two it stands for, such layers' recorded conversions in [4], their batched fallback in [7]) and
-// [14] the tracks they carried; at most n entries are written
+// [14] the tracks they carried; lives_gpu_set_pending_layer2: [15] blends recorded against a pending layer 2, [16] mix launches (lgpu_chain_flat_yuv_mix[_canvas]: each is
+// also counted in [1] and [13], and with a sink in [9] and [11]) and [17] the tracks they carried, [18] layer-2 programs run ahead of their readers; at most n entries are
+// written (19 exist; a caller that passes n <= 15 sees what it saw before)
 void lives_gpu_deferred_stats_n(unsigned long long *out, int n) {
   if (!out || n <= 0) return;
-  const unsigned long long v[15] = {g_lz_recorded.load(), g_lz_chain_launches.load(), g_lz_chain_tracks.load(), g_lz_staged.load(),
+  const unsigned long long v[19] = {g_lz_recorded.load(), g_lz_chain_launches.load(), g_lz_chain_tracks.load(), g_lz_staged.load(),
                                     g_lz_yuv_recorded.load(), g_lz_yuv_launches.load(), g_lz_yuv_tracks.load(), g_lz_yuv_pre.load(),
                                     g_lz_sink_recorded.load(), g_lz_sink_launches.load(), g_lz_sink_tracks.load(), g_lz_sink_fused.load(),
-                                    g_lz_transcode.load(), g_lz_flat_launches.load(), g_lz_flat_tracks.load()};
-  for (int i = 0; i < n && i < 15; i++) out[i] = v[i];
+                                    g_lz_transcode.load(), g_lz_flat_launches.load(), g_lz_flat_tracks.load(),
+                                    g_lz_l2_recorded.load(), g_lz_mix_launches.load(), g_lz_mix_tracks.load(), g_lz_l2_first.load()};
+  for (int i = 0; i < n && i < 19; i++) out[i] = v[i];
 }
 // Run the pending programs of these layers now, on the calling thread's stream: programs of equal shape (the tracks of one plan step) share ONE launch of the
 // fused chain kernel.  The layers stay pinned, nothing is downloaded, the host does not wait.  What a host calls once per tick when the plan steps of its tracks
@@ -594,6 +725,11 @@ int lives_gpu_layers_flush(lives_gpu_layer_t *const *layers, int nlayers) {
   }
   int rc = LGPU_OK;
   std::vector<char> done(zs.size(), 0);
+  // a listed program that is the pending layer 2 of a listed program is not a group member of its own: its readers' group folds it into its launch -- it then
+  // STAYS pending -- or runs it ahead of them (lazy_run_group), as it does for a layer 2 that is not listed at all
+  for (size_t i = 0; i < zs.size(); i++)
+    if (Lazy *z2 = lazy_l2_program(zs[i]))
+      for (size_t k = 0; k < zs.size(); k++) if (zs[k] == z2) done[k] = 1;
   for (size_t i = 0; i < zs.size(); i++) {
     if (done[i]) continue;
     std::vector<Lazy *> gz;
@@ -615,6 +751,32 @@ int lives_gpu_deferred_blend_chroma(const void *dst_host, int orow, int width, i
     return !(z->stage >= LZ_BLEND || z->w != width || z->h != height || z->rs != orow);
   });
   if (!takes_it) return 0;
+  // lives_gpu_set_pending_layer2: a layer 2 that is itself a pending program of this size, with no blend and no sink of its own, is NOT run: it becomes a plane a
+  // pending program reads as it stands, and whoever runs the reader resolves it (lazy_l2_program)
+  if (g_pending_l2.load()) {
+    const bool pending = res_update(layer2_host, [&](Dev *l2) {
+      if (!l2 || !l2->lazy) return false;
+      const Lazy *z2 = l2->lazy;
+      if (z2->blend || z2->sink || z2->w != width || z2->h != height || z2->rs != irow2) return false;
+      l2->lazy_readers++;
+      return true;
+    });
+    if (pending) {
+      const bool taken = res_update(dst_host, [&](Dev *e) {
+        if (!(e && e->lazy && e->lazy->stage < LZ_BLEND)) return false;
+        Lazy *z = e->lazy;
+        g_lz_recorded++;
+        z->blend = true; z->bf = bf & 0xFF; z->l2h = layer2_host; z->l2 = Dev(); z->l2pend = true; z->l2rs = irow2; z->stage = LZ_BLEND;
+        return true;
+      });
+      if (!taken) {
+        res_update(layer2_host, [](Dev *l2) { if (l2 && l2->lazy_readers > 0) l2->lazy_readers--; });
+        return 0;
+      }
+      g_lz_l2_recorded++;
+      return 1;
+    }
+  }
   const size_t n2 = (size_t)irow2 * height;
   uint8_t *l2d = acquire(layer2_host, n2, false);          // layer 2 itself may be pending: it runs; this thread's stream is behind its writer
   if (!l2d) return 0;

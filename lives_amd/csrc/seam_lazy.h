@@ -35,6 +35,10 @@ struct Lazy {
   bool scale = false; int dw = 0, dh = 0, interp = 0; bool opaque = false;     // opaque: the layer carried the host's word when the scale was recorded
   bool canvas = false; int nw = 0, nh = 0, ox = 0, oy = 0;
   bool blend = false; int bf = 0; const void *l2h = nullptr; Dev l2; int l2rs = 0;
+  // lives_gpu_set_pending_layer2: layer 2 was itself a pending program when the blend was recorded and was NOT run for it -- l2 is empty, l2h names its plane (whose
+  // lazy_readers counts this program as for a resident plane).  Whoever runs this program looks at that entry first (g_lazy_mu held): still a program -- it is folded
+  // into the launch or run ahead of it; pixels meanwhile -- they become l2 and the flag goes
+  bool l2pend = false;
   bool lut = false; uint8_t lut8[256];
   int w = 0, h = 0, rs = 0;         // the plane the program stands for
   // LZ_YUV: src is the luma plane; yu / yv the chroma planes (U, V order: a YVU420P layer's planes are swapped when recorded).  yfmt: the source's format in

@@ -225,6 +225,7 @@ PROTOTYPES = {
     "lgpu_chain_flat_yuv420p_mix": [vp, vp, vp, vp, vp, ci, vp, vp],
     "lgpu_chain_flat_yuv422": [vp, vp, vp, vp, vp, ci, vp, vp],
     "lgpu_chain_flat_yuv_mix": [vp, vp, vp, vp, vp, ci, vp, vp],
+    "lgpu_chain_flat_yuv_mix_canvas": [vp, vp, vp, vp, vp, ci, vp, vp],
     "lgpu_pixbuf_scale_check": [ci, ci, ci, ci, ci, ci, vp],
     "lgpu_pixbuf_scale_batch": [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp],
     "lgpu_fx_batch": [ctypes.POINTER(FxParams), ctypes.POINTER(FxFrame), ci, vp],

@@ -621,6 +621,18 @@ def chain_flat_yuv_mix(params, src, src2, tracks, amounts, sink=None, check=True
     return lib.call("lgpu_chain_flat_yuv_mix", *args)
 
 
+def chain_flat_yuv_mix_canvas(params, src, src2, tracks, amounts, canvas=None, check=True):
+    """lgpu_chain_flat_yuv_mix_canvas: chain_flat_yuv_mix to RGBA with both layers letterboxed onto one canvas = (nwidth, nheight, offs_x, offs_y) of opaque black, the
+    bars written by the same launch (rowstride params.orow, canvas-sized).  canvas=None: the bytes of chain_flat_yuv_mix without a sink.  check=False returns the
+    library's code instead of raising (tests of the refusals)"""
+    am = (ctypes.c_uint8 * max(1, len(tracks)))(*[int(a) & 0xFF for a in amounts]) if amounts is not None else None
+    cv = lib.Canvas(*canvas) if canvas is not None else None
+    args = (ctypes.byref(params), ctypes.byref(src), ctypes.byref(src2), ctypes.byref(cv) if cv is not None else None, tracks, len(tracks), am, stream_ptr())
+    if not check:
+        return lib.load().lgpu_chain_flat_yuv_mix_canvas(*args)
+    return lib.call("lgpu_chain_flat_yuv_mix_canvas", *args)
+
+
 def stream_probe(params, tracks, reps):
     """lgpu_debug_stream_probe: the chain's algorithmic bytes as a bare stream on the same frames, ms for `reps` launches (destinations left dirty)"""
     ms = ctypes.c_float()
