@@ -9,7 +9,9 @@ OBJ=build
 mkdir -p $OBJ
 pids=()
 for f in runtime swizzle yuv effects resize stencil palette pixbuf fused flat; do
-  if [ ! -f $OBJ/$f.o ] || [ $f.hip -nt $OBJ/$f.o ] || [ lgpu_common.h -nt $OBJ/$f.o ] || [ ../../include/lives_gpu.h -nt $OBJ/$f.o ]; then
+  stale=
+  case $f in yuv|flat|pixbuf) [ k2_walk.h -nt $OBJ/$f.o ] && stale=1 ;; esac      # K2's chroma walk, shared by the three
+  if [ ! -f $OBJ/$f.o ] || [ $f.hip -nt $OBJ/$f.o ] || [ lgpu_common.h -nt $OBJ/$f.o ] || [ ../../include/lives_gpu.h -nt $OBJ/$f.o ] || [ -n "$stale" ]; then
     $HIPCC $FLAGS -c $f.hip -o $OBJ/$f.o &
     pids+=($!)
   fi

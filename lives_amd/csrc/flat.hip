@@ -7,8 +7,7 @@
 // then (even heights) the trailing row -- that is two pixels of one row or a 2 x 2 quad.  K4's 4:2:0 chroma walk pairs the rows the same way: chroma row r is
 // cavg(row 2r + 2, row 2r + 1) with U of a pair's first pixel and V of its second, and the last chroma row is row dh - 1's alone (palette.hip, k_rgb_to_yuv FMT 4).
 // So unit p feeds chroma row p - 1 from the quad it already holds, unit 0 gives luma only, and the trailing-row unit of an even height gives the last chroma row.
-// THIS IS THE THIRD PLACE the 4:2:0 quirk walk is written down (yuv.hip yuv420_cell / k_yuv420p_to_rgb_s, pixbuf.hip k_pb_half<.., YUV>): a quirk changed
-// there must change here too.
+// Which chroma sample feeds which pixel is k2_walk.h's word, here as in yuv.hip and pixbuf.hip (sites that keep their own text name the header's function they repeat).
 //
 // Tables: K2's as in k_yuv420p_to_rgb_s (RGB_Y, {R_Cr, G_Cr}[v], {G_Cb, B_Cb}[u] with the chroma clamp folded into the index: 5 KB), the LUT (256 B) and, with a
 // sink, the {Y, U} / {Y, V} tables of get_sink_tables (12 KB), all staged in LDS once per workgroup; a workgroup then walks a run of consecutive units.
@@ -22,6 +21,7 @@
 // lgpu_chain_flat_yuv_mix: L2YUV is layer 2's source policy as SRC is layer 1's (1 planar 4:2:0, 2 YUV422P, 3 packed), and the two combine freely: a camera fading
 // into a decoded clip, two 4:2:2 clips in a transition, a 4:2:0 clip into a 4:2:2 one -- each one launch with no RGBA frame anywhere.
 #include "lgpu_common.h"
+#include "k2_walk.h"
 #include <algorithm>
 #include <string.h>
 
@@ -99,7 +99,17 @@ struct FlatPlanes {
 struct FlatK2Lds { const uint32_t *ty; const uint2 *rg, *gb; };
 template <int KIND> struct FlatCell { static constexpr int value = KIND; };      // 0: row 0, 1: a row pair, 2: the trailing row
 
-// K2's walk for cell (unit, k) of one layer: its two pixels of one row or its 2 x 2 quad go to out(FlatCell<KIND>, first row, chroma row, p0, p1, second row's p0, p1).  Either layer
+// xyuv2rgb on the paired tables; the chroma index is the blended value itself
+template <int SWAP>
+__device__ __forceinline__ uint32_t flat_px(const FlatK2Lds &L, uint32_t yv, uint32_t iu, uint32_t iv) {
+  const uint32_t yy = L.ty[yv];
+  const uint2 rg = L.rg[iv], gb = L.gb[iu];
+  uint32_t r, g, b;
+  yuv_rgb(yy, rg.x, rg.y, gb.x, gb.y, r, g, b);
+  return SWAP ? (b | (g << 8) | (r << 16) | 0xFF000000u) : (r | (g << 8) | (b << 16) | 0xFF000000u);
+}
+
+// K2's walk (k2_walk.h) for cell (unit, k) of one layer: its two pixels of one row or its 2 x 2 quad go to out(FlatCell<KIND>, first row, chroma row, p0, p1, second row's p0, p1).  Either layer
 // of the L2YUV forms comes through here when it is planar 4:2:0, each with its own planes and tables
 template <int SWAP, class Out>
 __device__ __forceinline__ void flat_cell(const FlatPlanes &P, const FlatK2Lds &L, int unit, int k, int hw, int H, int npairs, Out &&out) {
@@ -108,28 +118,21 @@ __device__ __forceinline__ void flat_cell(const FlatPlanes &P, const FlatK2Lds &
   auto PV = [&](int r, int kk) -> uint32_t { long i = (long)r * P.vs + kk; return pv[i < (long)P.vsize ? i : (long)P.vsize - 1]; };
   auto ld32 = [](const uint8_t *p) -> uint32_t { uint32_t w; __builtin_memcpy(&w, p, 4); return w; };
   auto ld16 = [](const uint8_t *p) -> uint32_t { uint16_t w; __builtin_memcpy(&w, p, 2); return w; };
-  // xyuv2rgb on the paired tables; the chroma index is the blended value itself
-  auto px = [&](uint32_t yv, uint32_t iu, uint32_t iv) -> uint32_t {
-    const uint32_t yy = L.ty[yv];
-    const uint2 rg = L.rg[iv], gb = L.gb[iu];
-    uint32_t r, g, b;
-    yuv_rgb(yy, rg.x, rg.y, gb.x, gb.y, r, g, b);
-    return SWAP ? (b | (g << 8) | (r << 16) | 0xFF000000u) : (r | (g << 8) | (b << 16) | 0xFF000000u);
-  };
+  auto px = [&](uint32_t yv, uint32_t iu, uint32_t iv) -> uint32_t { return flat_px<SWAP>(L, yv, iu, iv); };
   // K2's vblend: (2a + b) / 3 and (a + 2b) / 3 on doubled sums, or the halves with pb_quality LOW
   auto vtop = [&](uint32_t s1, uint32_t s2) -> uint32_t { return P.lowq ? s1 >> 1 : yuv_third(s1, s2); };
   auto vbot = [&](uint32_t s1, uint32_t s2) -> uint32_t { return P.lowq ? s2 >> 1 : yuv_third(s2, s1); };
   if (unit == 0) {
-    // row 0 (:3399-3443)
-    const int kp = k ? k - 1 : 0, kn = (k + 1 < hw) ? k + 1 : hw - 1;
-    const uint32_t yy = ld16(py + 2 * k), uk = PU(0, k), vk = PV(0, k);
-    const uint32_t p0 = px(yy & 0xFF, (uk + PU(0, kp)) >> 1, (vk + PV(0, kp)) >> 1);
-    const uint32_t p1 = px(yy >> 8, (uk + PU(0, kn)) >> 1, (vk + PV(0, kn)) >> 1);
+    const uint32_t yy = ld16(py + 2 * k);
+    uint32_t p0, p1;
+    k2_row_pixels(k2_row_edge(0, k, hw, PU, PV), yy & 0xFF, yy >> 8, px, p0, p1);
     out(FlatCell<0>(), 0, 0, p0, p1, 0u, 0u);
   } else if (unit <= npairs) {
-    // rows (i, i + 1), chroma rows r and r + 1 (:3445-3554)
+    // rows (i, i + 1), chroma rows r and r + 1
     const int i = 2 * unit - 1, r = unit - 1;
     const uint32_t ya = ld16(py + (size_t)i * P.ys + 2 * k), yb = ld16(py + (size_t)(i + 1) * P.ys + 2 * k);
+    // k2_walk.h's k2_pair_samples + k2_pair_pixels (rules b-f) in this kernel's own text and statement order: through the header two instantiations ran 0.6 % slower
+    // (profiles/r18/k2_walk.md)
     uint32_t u_l, u_c, u_n, u1_c, u1_n, v_c, v_n, v1_l, v1_c, v1_n, v1_0;
     const long ou = (long)(r + 1) * P.us, ov = (long)(r + 1) * P.vs;
     if (k >= 1 && ou + k + 3 <= (long)P.usize && ov + k + 3 <= (long)P.vsize) {
@@ -146,22 +149,20 @@ __device__ __forceinline__ void flat_cell(const FlatPlanes &P, const FlatK2Lds &
       u_n = PU(r, k + 1); u1_c = PU(r + 1, k); u1_n = PU(r + 1, k + 1);
       v_n = PV(r, k + 1); v1_n = PV(r + 1, k + 1);
     }
-    // left pixel: the second row's U sum rebuilt from the first row (:3461); V of row r with the previous V of row r + 1, "last V" frozen at column 0 (:3544)
     const uint32_t su = u_c + u_l, s1v = v_c + v1_l, s2v = v1_c + v1_0;
     const uint32_t a0 = px(ya & 0xFF, vtop(su, su), vtop(s1v, s2v)), b0 = px(yb & 0xFF, vbot(su, su), vbot(s1v, s2v));
-    // right pixel
     const uint32_t s1u = u_c + u_n, s2u = u1_c + u1_n, s1w = v_c + v_n, s2w = v1_c + v1_n;
     const uint32_t a1 = px(ya >> 8, vtop(s1u, s2u), vtop(s1w, s2w)), b1 = px(yb >> 8, vbot(s1u, s2u), vbot(s1w, s2w));
     out(FlatCell<1>(), i, r, a0, a1, b0, b1);
   } else {
-    // trailing row H - 1 (:3556-3592)
+    // trailing row H - 1
     const int i = H - 1, r = i >> 1;
+    // k2_walk.h's k2_trailing_pixels (rules g, h) in this kernel's own text
     const int kp = k ? k - 1 : 0, kn = (k + 1 < hw) ? k + 1 : hw - 1;
     const uint32_t yy = ld16(py + (size_t)i * P.ys + 2 * k), uk = PU(r, k), vk = PV(r, k);
     uint32_t p0;
     if (P.fix_edges) p0 = px(yy & 0xFF, (uk + PU(r, kp)) >> 1, (vk + PV(r, kp)) >> 1);
     else {
-      // 1-thread reference: luma from row 0; this / last walk = {row r col 0, row r col 0, row 0 col 1, row 0 col 2, ...}
       const uint32_t tu = k ? PU(0, k) : PU(r, 0), tv = k ? PV(0, k) : PV(r, 0);
       const uint32_t lu = (k >= 2) ? PU(0, k - 1) : PU(r, 0), lv = (k >= 2) ? PV(0, k - 1) : PV(r, 0);
       p0 = px(py[2 * k], (tu + lu) >> 1, (tv + lv) >> 1);
@@ -172,21 +173,12 @@ __device__ __forceinline__ void flat_cell(const FlatPlanes &P, const FlatK2Lds &
 }
 
 // one row's pixel pair of cell k of a 4:2:2 frame (the SRC policies of k_flat_yuv420 for layer 1, L2YUV - 1 for layer 2).
-// SRC == 1, planar (YUV422P): yuv.hip's yuv422_cell walk (:3593-3640 / :3858-3901).  "this / last" are seeded from chroma row i >> 1 (reference), so the first pair of a
-// row takes its left samples from there; the read one past a row's end is the next row's first sample or is clamped to the plane's last byte; pb_quality and
-// LGPU_YUV_FIX_EDGES change nothing in this walk.  THE 4:2:2 SEED QUIRK IS NOW WRITTEN DOWN TWICE (yuv.hip yuv422_cell / k_yuv420p_to_rgb_s<.., V422>, and here): a quirk
-// changed there must change here too.
+// SRC == 1, planar (YUV422P): K2's 4:2:2 row (k2_walk.h, rules i and e); pb_quality and LGPU_YUV_FIX_EDGES change nothing in this walk.
 // SRC == 2, packed (UYVY / YUYV): K3's conversion (palette.hip k_yuv_to_rgb / k_uyvy_to_rgb_s, uyvy2rgb :2410-2415, yuyv2rgb :2418-2423): both pixels of a macropixel
 // under its own U and V, no interpolation and no chroma clamp (the host stages the tables with the identity index); one aligned dword per lane and row
 template <int SWAP, int SRC>
 __device__ __forceinline__ void flat_row422(const FlatPlanes &P, const FlatK2Lds &L, int sfmt, int i, int k, uint32_t &p0, uint32_t &p1) {
-  auto px = [&](uint32_t yv, uint32_t iu, uint32_t iv) -> uint32_t {
-    const uint32_t yy = L.ty[yv];
-    const uint2 rg = L.rg[iv], gb = L.gb[iu];
-    uint32_t r, g, b;
-    yuv_rgb(yy, rg.x, rg.y, gb.x, gb.y, r, g, b);
-    return SWAP ? (b | (g << 8) | (r << 16) | 0xFF000000u) : (r | (g << 8) | (b << 16) | 0xFF000000u);
-  };
+  auto px = [&](uint32_t yv, uint32_t iu, uint32_t iv) -> uint32_t { return flat_px<SWAP>(L, yv, iu, iv); };
   if constexpr (SRC == 2) {
     const uint32_t m = *reinterpret_cast<const uint32_t *>(P.y + (size_t)i * P.ys + 4 * (size_t)k);
     uint32_t y0, y1, u, v;
@@ -200,20 +192,20 @@ __device__ __forceinline__ void flat_row422(const FlatPlanes &P, const FlatK2Lds
     uint16_t yy;
     __builtin_memcpy(&yy, P.y + (size_t)i * P.ys + 2 * k, 2);
     const long ou = (long)i * P.us + k, ov = (long)i * P.vs + k;
-    uint32_t tu, lu, nu, tv, lv, nv;
+    K2Row<uint32_t> s;
     if (k >= 2 && ou + 3 <= (long)P.usize && ov + 3 <= (long)P.vsize) {
-      // interior: one 4-byte window (columns k - 1 .. k + 2, the last unused) per chroma plane
+      // interior (no seeded sample from column 2 on): one 4-byte window (columns k - 1 .. k + 2, the last unused) per chroma plane
       uint32_t wu, wv;
       __builtin_memcpy(&wu, pu + (ou - 1), 4); __builtin_memcpy(&wv, pv + (ov - 1), 4);
-      lu = wu & 0xFF; tu = (wu >> 8) & 0xFF; nu = (wu >> 16) & 0xFF;
-      lv = wv & 0xFF; tv = (wv >> 8) & 0xFF; nv = (wv >> 16) & 0xFF;
+      s.lu = wu & 0xFF; s.tu = (wu >> 8) & 0xFF; s.nu = (wu >> 16) & 0xFF;
+      s.lv = wv & 0xFF; s.tv = (wv >> 8) & 0xFF; s.nv = (wv >> 16) & 0xFF;
     } else {
-      tu = k ? PU(i, k) : PU(i >> 1, 0); tv = k ? PV(i, k) : PV(i >> 1, 0);
-      lu = (k >= 2) ? PU(i, k - 1) : PU(i >> 1, 0); lv = (k >= 2) ? PV(i, k - 1) : PV(i >> 1, 0);
-      nu = PU(i, k + 1); nv = PV(i, k + 1);
+      // k2_walk.h's k2_row_422 (rules i and e) in this function's own text: through the header four instantiations take one more register
+      s.tu = k ? PU(i, k) : PU(i >> 1, 0); s.tv = k ? PV(i, k) : PV(i >> 1, 0);
+      s.lu = (k >= 2) ? PU(i, k - 1) : PU(i >> 1, 0); s.lv = (k >= 2) ? PV(i, k - 1) : PV(i >> 1, 0);
+      s.nu = PU(i, k + 1); s.nv = PV(i, k + 1);
     }
-    p0 = px(yy & 0xFFu, (tu + lu) >> 1, (tv + lv) >> 1);
-    p1 = px((uint32_t)yy >> 8, (tu + nu) >> 1, (tv + nv) >> 1);
+    k2_row_pixels(s, yy & 0xFFu, (uint32_t)yy >> 8, px, p0, p1);
   }
 }
 

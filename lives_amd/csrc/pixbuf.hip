@@ -23,6 +23,7 @@
 // two-dimensional (rounded and corrected per phase), not separable.
 #include <atomic>
 #include "lgpu_common.h"
+#include "k2_walk.h"
 #include <cmath>
 #include <cstdlib>
 #include <map>
@@ -788,7 +789,7 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
           w |= (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r, (int)q, 0, 0) << (8 * i);
         }
       }
-      return kc ? w : (w << 8) | (w & 0xFFu);                     // column -1 := column 0
+      return kc ? w : (w << 8) | (w & 0xFFu);                     // column -1 := column 0 (k2_walk.h: rule d for U, rule a's kp)
     };
     auto yrow = [&](int row) -> uint32_t { return __builtin_amdgcn_raw_buffer_load_b32(r_src, (int)(4u * (uint32_t)kc), __builtin_amdgcn_readfirstlane(row * A.irow), 0); };
     auto yload = [&](int p) -> Raw {
@@ -814,67 +815,63 @@ __global__ __launch_bounds__(256) void k_pb_half(const PbHalfArgs A, const PbTra
     auto at = [](uint32_t w, int j) -> uint32_t { return (w >> (8 * (j + 1))) & 0xFFu; };      // chroma column 2kc + j, j = -1 .. 2
     auto lu = [](uint32_t w, int i) -> uint32_t { return (w >> (8 * i)) & 0xFFu; };           // luma column 4kc + i
     auto bl = [&](uint32_t s1, uint32_t s2) -> uint32_t { return YS.lowq ? s1 >> 1 : yuv_third(s1, s2); };
-    auto rclamp = [&](uint32_t w) -> uint32_t { return kc == kmax ? (w & 0x00FFFFFFu) | ((w << 8) & 0xFF000000u) : w; };      // column hw := hw - 1
-    auto px = [&](uint32_t y, uint32_t iu, uint32_t iv, uint32_t *c) {
+    auto rclamp = [&](uint32_t w) -> uint32_t { return kc == kmax ? (w & 0x00FFFFFFu) | ((w << 8) & 0xFF000000u) : w; };      // column hw := hw - 1 (k2_walk.h: rule a's kn)
+    struct Px3 { uint32_t c[3]; };
+    auto px = [&](uint32_t y, uint32_t iu, uint32_t iv) -> Px3 {
       const pb_u2 rg = s_rg[iv], gb = s_gb[iu];
       uint32_t r, g, b;
       yuv_rgb(s_ty[y], rg.x, rg.y, gb.x, gb.y, r, g, b);
-      c[0] = SWAP ? b : r; c[1] = g; c[2] = SWAP ? r : b;
+      return Px3{{SWAP ? b : r, g, SWAP ? r : b}};
     };
     // pair p -> the H columns of its first consumed row (hf) and its second (hs_): top first walking down, bottom first walking up
-    // The chroma walk below is yuv.hip's yuv420_cell() (and k_yuv420p_to_rgb_s's fast cell) on a 4-byte window: row 0, the row pair with its (2a + b) / 3 blend,
-    // the left pixel's U rebuilt from the first row, the frozen V(r + 1, 0), the read one past the last pair's end, the 1-thread trailing row.  A change to one of
-    // those quirks there must be made here too; tests/test_chain_yuv.py holds both against the oracle's K2 bit for bit.
+    // The chroma walk is k2_walk.h's, on 4-byte windows; tests/test_chain_yuv.py holds it against the oracle's K2 bit for bit.
     auto cvt = [&](Raw w, int p, uint32_t hf[8], uint32_t hs_[8]) __attribute__((always_inline)) {
-      uint32_t t[4][3], b[4][3];
+      Px3 t[4], b[4];
       p = __builtin_amdgcn_readfirstlane(p);
       if (p > 0 && p < dh) {
-        // rows (2p - 1, 2p), chroma rows r = p - 1 and r + 1 (:3445-3554; yuv.hip yuv420_cell)
-        if (!kc) w.v1 = (w.v1 & ~0xFFu) | (w.v0 & 0xFFu);           // left pixel of column 0: V(r, 0) in place of V(r + 1, -1)
+        // rows (2p - 1, 2p), chroma rows r = p - 1 and r + 1
+        if (!kc) w.v1 = (w.v1 & ~0xFFu) | (w.v0 & 0xFFu);           // k2_walk.h rule d: V(r + 1, -1) := V(r, 0)
 #pragma unroll
         for (int j = 0; j < 2; j++) {
-          const uint32_t u_rk = at(w.u0, j), v_rk = at(w.v0, j), v_r1k = at(w.v1, j);
-          const uint32_t su = u_rk + at(w.u0, j - 1), iul = bl(su, su);      // the left pixel's U: second row rebuilt from the first (:3461)
-          const uint32_t s1v = v_rk + at(w.v1, j - 1), s2v = v_r1k + w.e0;
-          const uint32_t s1u = u_rk + at(w.u0, j + 1), s2u = at(w.u1, j) + at(w.u1, j + 1);
-          const uint32_t s1w = v_rk + at(w.v0, j + 1), s2w = v_r1k + at(w.v1, j + 1);
-          px(lu(w.ya, 2 * j), iul, bl(s1v, s2v), t[2 * j]);
-          px(lu(w.yb, 2 * j), iul, bl(s2v, s1v), b[2 * j]);
-          px(lu(w.ya, 2 * j + 1), bl(s1u, s2u), bl(s1w, s2w), t[2 * j + 1]);
-          px(lu(w.yb, 2 * j + 1), bl(s2u, s1u), bl(s2w, s1w), b[2 * j + 1]);
+          const K2Pair<uint32_t> s = {at(w.u0, j - 1), at(w.u0, j), at(w.u0, j + 1), at(w.u1, j), at(w.u1, j + 1), at(w.v0, j), at(w.v0, j + 1), at(w.v1, j - 1), at(w.v1, j), at(w.v1, j + 1), w.e0};
+          const K2Quad<Px3> q = k2_pair_pixels(s, lu(w.ya, 2 * j), lu(w.ya, 2 * j + 1), lu(w.yb, 2 * j), lu(w.yb, 2 * j + 1), [&](uint32_t s1, uint32_t s2, uint32_t &top, uint32_t &bot) { top = bl(s1, s2); bot = bl(s2, s1); }, px);
+          t[2 * j] = q.a0; t[2 * j + 1] = q.a1; b[2 * j] = q.b0; b[2 * j + 1] = q.b1;
         }
       } else {
         if (p == 0) {
-          // row 0 (:3399-3443): neighbours clamped into the row
+          // row 0
           const uint32_t u0 = rclamp(w.u0), v0 = rclamp(w.v0);
 #pragma unroll
           for (int j = 0; j < 2; j++) {
-            px(lu(w.ya, 2 * j), (at(u0, j) + at(u0, j - 1)) >> 1, (at(v0, j) + at(v0, j - 1)) >> 1, t[2 * j]);
-            px(lu(w.ya, 2 * j + 1), (at(u0, j) + at(u0, j + 1)) >> 1, (at(v0, j) + at(v0, j + 1)) >> 1, t[2 * j + 1]);
+            const K2Row<uint32_t> s = {at(u0, j), at(v0, j), at(u0, j - 1), at(v0, j - 1), at(u0, j + 1), at(v0, j + 1)};
+            k2_row_pixels(s, lu(w.ya, 2 * j), lu(w.ya, 2 * j + 1), px, t[2 * j], t[2 * j + 1]);
           }
         } else {
-          // the trailing row H - 1 (:3556-3592)
+          // the trailing row H - 1, chroma row r in u1 / v1
           const uint32_t u1 = rclamp(w.u1), v1 = rclamp(w.v1);
 #pragma unroll
           for (int j = 0; j < 2; j++) {
-            if (YS.fix_edges) px(lu(w.ya, 2 * j), (at(u1, j) + at(u1, j - 1)) >> 1, (at(v1, j) + at(v1, j - 1)) >> 1, t[2 * j]);
+            const K2Row<uint32_t> e = {at(u1, j), at(v1, j), at(u1, j - 1), at(v1, j - 1), at(u1, j + 1), at(v1, j + 1)};
+            if (YS.fix_edges) t[2 * j] = k2_row_left(e, lu(w.ya, 2 * j), px);
             else {
+              // k2_walk.h rule h: luma of row 0 (yb), this / last from chroma row 0 (u0 / v0) with e0 / e1 = {row r, column 0} for column 0 / the columns below 2
               const bool c0 = !kc && !j, c2 = kc != 0;                 // chroma column 0 / >= 2
-              const uint32_t tu = c0 ? w.e0 : at(w.u0, j), tv = c0 ? w.e1 : at(w.v0, j);
-              const uint32_t lu_ = c2 ? at(w.u0, j - 1) : w.e0, lv_ = c2 ? at(w.v0, j - 1) : w.e1;
-              px(lu(w.yb, 2 * j), (tu + lu_) >> 1, (tv + lv_) >> 1, t[2 * j]);
+              K2Row<uint32_t> s = e;
+              s.tu = c0 ? w.e0 : at(w.u0, j); s.tv = c0 ? w.e1 : at(w.v0, j);
+              s.lu = c2 ? at(w.u0, j - 1) : w.e0; s.lv = c2 ? at(w.v0, j - 1) : w.e1;
+              t[2 * j] = k2_row_left(s, lu(w.yb, 2 * j), px);
             }
-            px(lu(w.ya, 2 * j + 1), (at(u1, j) + at(u1, j + 1)) >> 1, (at(v1, j) + at(v1, j + 1)) >> 1, t[2 * j + 1]);
+            t[2 * j + 1] = k2_row_right(e, lu(w.ya, 2 * j + 1), px);
           }
         }
 #pragma unroll
-        for (int i = 0; i < 4; i++) { b[i][0] = t[i][0]; b[i][1] = t[i][1]; b[i][2] = t[i][2]; }
+        for (int i = 0; i < 4; i++) b[i] = t[i];
       }
       uint32_t At[4], Bt[4], Ab[4], Bb[4];
 #pragma unroll
       for (int c = 0; c < 3; c++) {
-        At[c] = t[0][c] | (t[1][c] << 16); Bt[c] = t[2][c] | (t[3][c] << 16);
-        Ab[c] = b[0][c] | (b[1][c] << 16); Bb[c] = b[2][c] | (b[3][c] << 16);
+        At[c] = t[0].c[c] | (t[1].c[c] << 16); Bt[c] = t[2].c[c] | (t[3].c[c] << 16);
+        Ab[c] = b[0].c[c] | (b[1].c[c] << 16); Bb[c] = b[2].c[c] | (b[3].c[c] << 16);
       }
       At[3] = Bt[3] = Ab[3] = Bb[3] = 0u;
       if (edge_strip) {

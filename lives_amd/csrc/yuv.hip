@@ -7,14 +7,11 @@
 // cache lines three times (k-1, k, k+1) and stores are 8 B/lane contiguous per row.  The five int32
 // conversion tables (5 KB) are staged in LDS once per workgroup together with the LUT.
 //
-// Reference behaviours kept bit-for-bit (see DESIGN.md, quirk list K2-a..e):
-//   - left pixel of a pair: second-row U sum rebuilt from the first row (:3461); V of row r paired with the
-//     previous V of row r+1 (:3544); "last V" of row r+1 frozen at column 0
-//   - right pixel of the last pair reads the chroma sample one past the row end
-//   - last row (1-thread reference): luma from row 0, "next" chroma from chroma row 0, even x only
+// Reference behaviours kept bit-for-bit (see DESIGN.md, quirk list K2-a..e): which sample feeds which pixel is stated in k2_walk.h.
 // Pixels whose reference value is undefined (row 0 odd x: out-of-bounds table index; last row odd x: never
 // written) get the evident intent.
 #include "lgpu_common.h"
+#include "k2_walk.h"
 #include <algorithm>
 #include <atomic>
 #include <type_traits>
@@ -84,9 +81,7 @@ struct YuvCtx {
   }
 };
 
-// (the same walk runs in registers in pixbuf.hip's k_pb_half<.., YUV>, the 2:1 chain from a 4:2:0 source, and in flat.hip's k_flat_yuv420, the unscaled chain: a quirk
-// changed here must change in both)
-// one (unit, chroma column k) cell of the 4:2:0 walk: 2 pixels of row 0, a 2 x 2 quad of a row pair, or 2 pixels of the trailing row
+// one (unit, chroma column k) cell of the 4:2:0 walk (the rules: k2_walk.h): 2 pixels of row 0, a 2 x 2 quad of a row pair, or 2 pixels of the trailing row
 // units: 0 = row 0; p >= 1 = rows (2p-1, 2p) while 2p <= H-1; then (even H) the trailing row H-1
 __device__ __forceinline__ void yuv420_cell(const YuvArgs &a, const YuvCtx &c, int unit, int k, int hw, int npairs) {
   const int ops = a.opsize;
@@ -94,33 +89,31 @@ __device__ __forceinline__ void yuv420_cell(const YuvArgs &a, const YuvCtx &c, i
   auto PU = [&](int r, int kk) -> int { long i = (long)r * a.us + kk; return a.u[i < a.usize ? i : a.usize - 1]; };
   auto PV = [&](int r, int kk) -> int { long i = (long)r * a.vs + kk; return a.v[i < a.vsize ? i : a.vsize - 1]; };
   if (unit == 0) {
-    // row 0 (:3399-3443)
+    // k2_walk.h's k2_row_edge + k2_row_pixels (rule a) in this function's own text, as the rest of the cell
     const int kp = k ? k - 1 : 0, kn = (k + 1 < hw) ? k + 1 : hw - 1;
     const uint32_t p0 = c.rgb(a.y[2 * k], c.cuv((PU(0, k) + PU(0, kp)) >> 1), c.cuv((PV(0, k) + PV(0, kp)) >> 1));
     const uint32_t p1 = c.rgb(a.y[2 * k + 1], c.cuv((PU(0, k) + PU(0, kn)) >> 1), c.cuv((PV(0, k) + PV(0, kn)) >> 1));
     c.store2(a.dst + (size_t)(2 * k) * ops, p0, p1);
   } else if (unit <= npairs) {
-    // rows (i, i+1), chroma rows r and r+1 (:3445-3554)
     const int i = 2 * unit - 1, r = i >> 1;
     const uint8_t *y0 = a.y + (size_t)i * a.ys + 2 * k, *y1 = y0 + a.ys;
     uint8_t *d0 = a.dst + (size_t)i * a.orow + (size_t)(2 * k) * ops, *d1 = d0 + a.orow;
+    // k2_walk.h's k2_pair_samples + k2_pair_pixels (rules b-f) in this function's own text: through the header the general kernel is 3 % longer
     const int u_rk = PU(r, k), v_rk = PV(r, k), v_r1k = PV(r + 1, k);
     int ut, ub, vt, vb;
-    // left pixel
     const int lu1 = k ? PU(r, k - 1) : u_rk;
     const int lv1 = k ? PV(r + 1, k - 1) : v_rk;
     const int lv2 = PV(r + 1, 0);
     c.vblend(u_rk + lu1, u_rk + lu1, ut, ub);
     c.vblend(v_rk + lv1, v_r1k + lv2, vt, vb);
     const uint32_t a0 = c.rgb(y0[0], ut, vt), b0 = c.rgb(y1[0], ub, vb);
-    // right pixel
     c.vblend(u_rk + PU(r, k + 1), PU(r + 1, k) + PU(r + 1, k + 1), ut, ub);
     c.vblend(v_rk + PV(r, k + 1), v_r1k + PV(r + 1, k + 1), vt, vb);
     const uint32_t a1 = c.rgb(y0[1], ut, vt), b1 = c.rgb(y1[1], ub, vb);
     c.store2(d0, a0, a1);
     c.store2(d1, b0, b1);
   } else {
-    // trailing row H-1 (:3556-3592)
+    // k2_walk.h's k2_trailing_pixels (rules g, h) in this function's own text, row r's samples read per pixel: through the header the general kernel is 3 % longer
     const int i = H - 1, r = i >> 1;
     const int kp = k ? k - 1 : 0, kn = (k + 1 < hw) ? k + 1 : hw - 1;
     const uint8_t *yr = a.y + (size_t)i * a.ys;
@@ -128,7 +121,6 @@ __device__ __forceinline__ void yuv420_cell(const YuvArgs &a, const YuvCtx &c, i
     if (a.fix_edges) {
       p0 = c.rgb(yr[2 * k], c.cuv((PU(r, k) + PU(r, kp)) >> 1), c.cuv((PV(r, k) + PV(r, kp)) >> 1));
     } else {
-      // 1-thread reference: this/last walk = {row r col 0, row r col 0, row 0 col 1, row 0 col 2, ...}
       const int tu = k ? PU(0, k) : PU(r, 0), tv = k ? PV(0, k) : PV(r, 0);
       const int lu = (k >= 2) ? PU(0, k - 1) : PU(r, 0), lv = (k >= 2) ? PV(0, k - 1) : PV(r, 0);
       p0 = c.rgb(a.y[2 * k], c.cuv((tu + lu) >> 1), c.cuv((tv + lv) >> 1));
@@ -169,7 +161,7 @@ __global__ __launch_bounds__(kBlock) void k_yuv420p_to_rgb(YuvArgs a, Lut8 lut, 
   if (k >= hw) return;
   int unit = unit0;
   if (pre) {
-    // the row-pair branch of yuv420_cell on the samples already here (same expressions, :3445-3554)
+    // k2_walk.h's k2_pair_pixels (rules b, c, f) on the samples already here, in this kernel's own text: through the header the kernel is 3 % longer
     uint8_t *d0 = a.dst + (size_t)i0 * a.orow + (size_t)(2 * k) * a.opsize, *d1 = d0 + a.orow;
     int ut, ub, vt, vb;
     c.vblend(u_c + u_l, u_c + u_l, ut, ub);
@@ -185,10 +177,8 @@ __global__ __launch_bounds__(kBlock) void k_yuv420p_to_rgb(YuvArgs a, Lut8 lut, 
   for (; unit < nunits; unit += gridDim.y) yuv420_cell(a, c, unit, k, hw, npairs);
 }
 
-// one (row i, chroma column k) cell of the 4:2:2 walk (:3593-3640 / :3858-3901): "last / this" are seeded from chroma row i >> 1 (reference), so the first pair of a
-// row takes its left samples from there
-// (THE 4:2:2 SEED QUIRK IS WRITTEN DOWN TWICE: here, with the V422 fast path of k_yuv420p_to_rgb_s below, and in flat.hip's flat_row422, the unscaled chain from
-// YUV422P frames (lgpu_chain_flat_yuv422): a quirk changed here must change there too)
+// one (row i, chroma column k) cell of the 4:2:2 walk: k2_walk.h's k2_row_422 + k2_row_pixels (rules i and e) in this function's own text -- through the header the seed
+// offset is shared and the V422 kernels take two more registers (profiles/r18/k2_walk.md)
 __device__ __forceinline__ void yuv422_cell(const YuvArgs &a, const YuvCtx &c, int i, int k) {
   auto PU = [&](int r, int kk) -> int { long q = (long)r * a.us + kk; return a.u[q < a.usize ? q : a.usize - 1]; };
   auto PV = [&](int r, int kk) -> int { long q = (long)r * a.vs + kk; return a.v[q < a.vsize ? q : a.vsize - 1]; };
@@ -234,8 +224,7 @@ __global__ __launch_bounds__(1024) void k_yuv420p_to_rgb_s(YuvArgs a, Lut8 lut, 
     q.valid = unit < (uint32_t)nunits;
     q.ya = q.yb = 0; q.u0 = q.u1 = q.v0 = q.v1 = 0; q.lv2 = 0;
     if (V422) {
-      // row q.unit; columns k0 >= 2 only (the first pairs of a row take their left samples from chroma row i >> 1), the window k0 - 1 .. inside the plane
-      // (the same split -- seeded cells sample by sample, interior cells on a window -- is written a second time in flat.hip's flat_row422: change both)
+      // row q.unit; columns k0 >= 2 only (k2_walk.h, rule i: the first pairs of a row are seeded and go through yuv422_cell), the window k0 - 1 .. inside the plane
       const int i2 = q.unit;
       // plane offsets are 32-bit products of 24-bit operands (the host sends larger planes to the general kernel): v_mul_u32_u24 instead of 64-bit multiply-adds at a quarter of the rate
       const uint32_t ou = __umul24((uint32_t)i2, (uint32_t)a.us) + (uint32_t)q.k0 - 1u, ov = __umul24((uint32_t)i2, (uint32_t)a.vs) + (uint32_t)q.k0 - 1u;
@@ -309,6 +298,7 @@ __global__ __launch_bounds__(1024) void k_yuv420p_to_rgb_s(YuvArgs a, Lut8 lut, 
     if (ORDER == 1) return __builtin_amdgcn_perm(r_, __builtin_amdgcn_perm(g_, b_, 0x0C0C0400u), 0x0D040100u);
     return __builtin_amdgcn_perm(b_, __builtin_amdgcn_perm(g_, r_, 0x0C04000Du), 0x04020100u);
   };
+  auto px = [&](uint32_t yv, uint32_t iu, uint32_t iv) -> uint32_t { return pixel(yv, (iu << 3) + bu, (iv << 3) + bv); };
   while (cur.valid) {
     idx += stride;
     const Cell nxt = fetch(idx);
@@ -320,37 +310,36 @@ __global__ __launch_bounds__(1024) void k_yuv420p_to_rgb_s(YuvArgs a, Lut8 lut, 
       c.lut = smem + kYsOffLut; c.lut16 = nullptr; c.clamped = a.clamped; c.lowq = false; c.use_lut = LUT; c.opsize = 4; c.order = ORDER;
       for (int k = cur.k0; k < cur.k0 + NC && k < hw; k++) { if (V422) yuv422_cell(a, c, cur.unit, k); else yuv420_cell(a, c, cur.unit, k, hw, npairs); }
     } else if (V422) {
-      uint32_t px[2 * NC];
+      uint32_t out[2 * NC];
 #pragma unroll
       for (int j = 0; j < NC; j++) {
         const uint32_t tu = at(cur.u0, j), tv = at(cur.v0, j);
-        px[2 * j] = pixel(yat(cur.ya, 2 * j), (((tu + at(cur.u0, j - 1)) >> 1) << 3) + bu, (((tv + at(cur.v0, j - 1)) >> 1) << 3) + bv);
-        px[2 * j + 1] = pixel(yat(cur.ya, 2 * j + 1), (((tu + at(cur.u0, j + 1)) >> 1) << 3) + bu, (((tv + at(cur.v0, j + 1)) >> 1) << 3) + bv);
+        const K2Row<uint32_t> s = {tu, tv, at(cur.u0, j - 1), at(cur.v0, j - 1), at(cur.u0, j + 1), at(cur.v0, j + 1)};
+        k2_row_pixels(s, yat(cur.ya, 2 * j), yat(cur.ya, 2 * j + 1), px, out[2 * j], out[2 * j + 1]);
       }
       uint8_t *d0 = a.dst + (__umul24((uint32_t)cur.unit, (uint32_t)a.orow) + 8u * (uint32_t)cur.k0);
-      if (NC == 1) *reinterpret_cast<uint2 *>(d0) = make_uint2(px[0], px[1]);
+      if (NC == 1) *reinterpret_cast<uint2 *>(d0) = make_uint2(out[0], out[1]);
       else {
         typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
 #pragma unroll
-        for (int q = 0; q < NC / 2; q++) { const u32x4s t = {px[4 * q], px[4 * q + 1], px[4 * q + 2], px[4 * q + 3]}; reinterpret_cast<u32x4s *>(d0)[q] = t; }
+        for (int q = 0; q < NC / 2; q++) { const u32x4s t = {out[4 * q], out[4 * q + 1], out[4 * q + 2], out[4 * q + 3]}; reinterpret_cast<u32x4s *>(d0)[q] = t; }
       }
     } else {
       win_t u0 = cur.u0, u1 = cur.u1, v0 = cur.v0, v1 = cur.v1;
       if (!cur.k0) {
-        // first group: the reference's k == 0 case takes U[r][0] / V[r][0] as the samples left of the group (:3447-3452)
+        // first group, k2_walk.h rule d: U(r, -1) := U(r, 0), V(r + 1, -1) := V(r, 0)
         u0 = (u0 << 8) | (u0 & 0xFF); u1 = u1 << 8; v1 = (v1 << 8) | (v0 & 0xFF); v0 = v0 << 8;
       }
       uint32_t top[2 * NC], bot[2 * NC];
 #pragma unroll
       for (int j = 0; j < NC; j++) {
+        // k2_walk.h's k2_pair_pixels (rules b, c, f) in this kernel's own text: through the header 16 x 1080p per launch took 0.9 us of 37.9 more (profiles/r18/k2_walk.md)
         const uint32_t u_rk = at(u0, j), v_rk = at(v0, j), v_r1k = at(v1, j);
-        // left pixel: U row pair (s, s) -> top == bottom (:3461); V of row r with the previous V of row r + 1, the "last V" frozen at column 0 (:3544)
         const uint32_t su = u_rk + at(u0, j - 1);
         const uint32_t uleft = blend(su, su, bu);
         const uint32_t s1v = v_rk + at(v1, j - 1), s2v = v_r1k + cur.lv2;
         top[2 * j] = pixel(yat(cur.ya, 2 * j), uleft, blend(s1v, s2v, bv));
         bot[2 * j] = pixel(yat(cur.yb, 2 * j), uleft, blend(s2v, s1v, bv));
-        // right pixel
         const uint32_t s1u = u_rk + at(u0, j + 1), s2u = at(u1, j) + at(u1, j + 1);
         const uint32_t s1w = v_rk + at(v0, j + 1), s2w = v_r1k + at(v1, j + 1);
         top[2 * j + 1] = pixel(yat(cur.ya, 2 * j + 1), blend(s1u, s2u, bu), blend(s1w, s2w, bv));
@@ -373,7 +362,7 @@ __global__ __launch_bounds__(1024) void k_yuv420p_to_rgb_s(YuvArgs a, Lut8 lut, 
   }
 }
 
-// 4:2:2 (:3593-3640 / :3858-3901): row i, pair k; "last/this" are seeded from chroma row i>>1 (reference)
+// 4:2:2: row i, pair k (k2_walk.h, rule i)
 __global__ __launch_bounds__(kBlock) void k_yuv422p_to_rgb(YuvArgs a, Lut8 lut, YuvBatch bt, int batched) {
   if (batched) { a.y = bt.y[blockIdx.z]; a.u = bt.u[blockIdx.z]; a.v = bt.v[blockIdx.z]; a.dst = bt.dst[blockIdx.z]; }
   __shared__ int32_t s_tab[5 * 256];
