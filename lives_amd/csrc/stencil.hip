@@ -1011,7 +1011,8 @@ extern "C" int lgpu_edge(const uint8_t *src_d, int irow, uint8_t *dst_d, int oro
       if (hipMalloc((void **)&e.map, need) != hipSuccess) { set_error("hipMalloc(%zu) for the edge map failed", need); return LGPU_E_NOMEM; }
       e.cap = need;
     }
-    if (!e.st) { LGPU_HIP(hipMalloc((void **)&e.st, sizeof(EdgeState))); LGPU_HIP(hipMemset(e.st, 0, sizeof(EdgeState))); }
+    // zeroed in the order of the launches below: hipMemset is a null-stream operation that is not promised to be complete on return, and `stream` may not block on it
+    if (!e.st) { LGPU_HIP(hipMalloc((void **)&e.st, sizeof(EdgeState))); LGPU_HIP(hipMemsetAsync(e.st, 0, sizeof(EdgeState), st)); }
     if (!e.slices) LGPU_HIP(hipMalloc((void **)&e.slices, (size_t)1024 * 1025 * sizeof(unsigned int)));      // one histogram slice per map workgroup
     sc = e;
   }
