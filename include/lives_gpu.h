@@ -63,6 +63,9 @@ int lgpu_event_create(void **event_out);
 int lgpu_event_destroy(void *event);
 int lgpu_event_record(void *event, void *stream);
 int lgpu_stream_wait_event(void *stream, void *event);
+/* lgpu_upload cannot be part of a stream capture: pageable memory is copied into the staging chunks on the host at call time (and waits for the chunk's last DMA),
+   and below the staging threshold, or from pinned memory, the copy reads src_h whenever it runs -- at every replay.  Upload outside the graph and order the streams with
+   lgpu_event_record / lgpu_stream_wait_event; small blocks travel as kernel arguments with lgpu_params_set. */
 int lgpu_upload(void *dst_d, const void *src_h, size_t bytes, void *stream);
 int lgpu_download(void *dst_h, const void *src_d, size_t bytes, void *stream);
 /* page-locked, zeroed host memory for frames (DMA at link rate); lgpu_upload / lgpu_download also accept pageable memory: uploads of it go through
@@ -215,7 +218,10 @@ int lgpu_letterbox_bars(uint8_t *dst_d, int orow, int nwidth, int nheight, int p
    :14940-15259).  PARITY UNPINNED: libswscale is neither vendored nor version-pinned by the reference;
    this follows the repo's own spec "lgpu-polyphase-v1" (DESIGN.md).  interp = LiVESInterpType
    (GdkInterpType values: 0 NEAREST/"fast", 2 BILINEAR, 3 HYPER/"best").  psize 4, 3 or 1.
-   lut8 (HOST, may be NULL) is the fused post-pass of :14718-14720. */
+   lut8 (HOST, may be NULL) is the fused post-pass of :14718-14720.
+   Stream capture: filter banks are built by the first call of a geometry (blocking copies); the generic two-pass path, the gaussian paths of lgpu_gauss5 and of the
+   polyphase lgpu_chain keep int16 / frame scratch per (device, stream), grown (stream synchronisation, hipFree + hipMalloc) by a larger call: make the largest call on
+   the stream before a capture begins; a graph captured before the scratch grew holds the freed block. */
 int lgpu_resize(const uint8_t *src_d, int irow, int sw, int sh, uint8_t *dst_d, int orow, int dw, int dh,
                 int psize, int interp, const uint8_t *lut8, void *stream);
 /* test hook: which kernel lgpu_resize / the polyphase lgpu_chain would launch for a call, decided by the very functions the calls go through (resize.hip: the host
@@ -374,7 +380,9 @@ int lgpu_yuv_switch_clamping(uint8_t *const planes_d[4], const int rowstrides[4]
    The reference functions take no destination rowstride and walk their 4:1:1 side as one stream: here too both sides are COMPACT STREAMS from the
    start of each plane and irow / orow are ignored, except irow[0] for the planar / packed 4:4:4 sources whose functions take one.  Their quirks
    are kept (DESIGN.md K5c-*): 4:4:4 planar -> 4:1:1 leaves only the frame's last macropixel, in the first slot; packed 4:4:4 -> 4:1:1 converts the rows
-   that begin within the first width * height bytes; YUV411 -> 4:2:0 leaves all chroma in chroma row 0. */
+   that begin within the first width * height bytes; YUV411 -> 4:2:0 leaves all chroma in chroma row 0.
+   Every pair is one launch and can be captured into a graph once warm, except YUV411 -> 4:2:0 with an even height: its fold table comes from the stream-ordered pool
+   (lgpu_malloc_ordered / lgpu_free_ordered) in every call, so make that call between graph launches, not inside a stream capture. */
 int lgpu_yuv_repack(int in_pal, int out_pal, const uint8_t *const src_d[4], const int irow[4], uint8_t *const dst_d[4],
                     const int orow[4], int width, int height, int clamping_unclamped, int sampling, void *stream);
 /* "softlight": lives-plugins/weed-plugins/softlight.c:62-141.  Planar YUV (palette 544 YUV444P, 545 YUVA4444P,
@@ -387,7 +395,9 @@ int lgpu_softlight(const uint8_t *const src_d[4], const int irow[4], uint8_t *co
 /* "edge detect": lives-plugins/weed-plugins/edge.c:129-248.  palette 1..5 (RGB24, BGR24, RGBA32, BGRA32, ARGB32);
    mode 0 normal (edges keep the source colour) / 1 monochrome (white) / 2 supercolour (luma pass + one pass per colour
    byte).  Gradient magnitude of the 3x3-summed central differences, global Otsu threshold over a 1017-bin histogram
-   (device-side, no host round trip), non-edges black.  dst_d may equal src_d (CAN_DO_INPLACE). */
+   (device-side, no host round trip), non-edges black.  dst_d may equal src_d (CAN_DO_INPLACE).
+   Stream capture: the edge map is scratch per (device, stream), grown by hipFree + hipMalloc when a larger frame arrives: make the largest call on the stream before a
+   capture begins; a graph captured before the scratch grew holds the freed block. */
 int lgpu_edge(const uint8_t *src_d, int irow, uint8_t *dst_d, int orow, int width, int height, int palette, int mode,
               void *stream);
 /* "blurzoom" (RadioacTV): lives-plugins/weed-plugins/blurzoom.c.  Stateful across frames (background luma, feedback
@@ -396,7 +406,11 @@ int lgpu_edge(const uint8_t *src_d, int irow, uint8_t *dst_d, int orow, int widt
    mode 0 normal / 1 strobe / 2 strobe2 / 3 trigger, pattern 0 blue / 1 green / 2 red / 3 white.  Per frame: background
    subtract + threshold, OR into the feedback plane, 4-neighbour blur (:149-168), zoom (the reference's serial pointer
    walk :171-192 as a gather over prefix-summed step tables), saturating palette add.  Modes 1 / 2 need compact source rows
-   (the reference walks its snapshot with the source's row padding, :391-396).  Calls on one handle must be stream-ordered. */
+   (the reference walks its snapshot with the source's row padding, :391-396).  Calls on one handle must be stream-ordered.
+   Stream capture: on a handle that has never run in modes 1 or 2, modes 0 and 3 keep the whole state on the device, so ONE captured lgpu_blurzoom_process on fixed
+   buffers can be replayed frame after frame (after strobe frames mode 3 reads the host's countdown at call time to decide whether the frame feeds the background: a
+   capture bakes that answer in).  In modes 1 and 2 the strobe countdown is kept on the host and decides at call time which kernels are enqueued: a replay repeats the captured frame's
+   choice, so a captured sequence is good for exactly one replay. */
 typedef struct lgpu_blurzoom lgpu_blurzoom;
 int lgpu_blurzoom_create(int width, int height, int palette, lgpu_blurzoom **out);
 int lgpu_blurzoom_process(lgpu_blurzoom *bz, const uint8_t *src_d, int irow, uint8_t *dst_d, int orow, int mode, int pattern,
@@ -418,7 +432,11 @@ int lgpu_byte_luts(const uint8_t *src_d, int irow, uint8_t *dst_d, int orow, int
    handle.  palette 1 RGB24 / 2 BGR24 / 588 YUV888 (yuv_clamped = the channel's YUV_clamping leaf is CLAMPED); maxcache = parameter 0;
    on[3 * j + c] = the R / G / B (Y / U / V) switches and strength[j] the blend strength of frame -j, j = 0..50 (parameters 4j + 1 .. 4j + 4).
    src_d == dst_d = in place.  The host-ease branch (:180-183, :407-412) is not taken.  Calls on one handle must be stream-ordered;
-   a change of geometry restarts the ring (the reference's in channel is REINIT_ON_SIZE_CHANGE). */
+   a change of geometry restarts the ring (the reference's in channel is REINIT_ON_SIZE_CHANGE).
+   Stream capture: the ring's rotation is kept on the host, so a replay repeats the captured ring positions -- a captured sequence of calls is good for exactly one
+   replay.  Not inside a capture at all: a call that changes the geometry or the ring's depth (it synchronises the stream and resizes the ring with hipMalloc /
+   hipFree), and a call with more than four jobs (active frames, plus one for clamped YUV): their table goes through the handle's one pinned staging block, filled at
+   call time behind an event wait. */
 typedef struct lgpu_rgbdelay lgpu_rgbdelay;
 int lgpu_rgbdelay_create(lgpu_rgbdelay **out);
 int lgpu_rgbdelay_process(lgpu_rgbdelay *rd, const uint8_t *src_d, int irow, uint8_t *dst_d, int orow, int width, int height, int palette,
@@ -428,7 +446,9 @@ void lgpu_rgbdelay_destroy(lgpu_rgbdelay *rd);
    width in macropixels for UYVY / YUYV); src_d == dst_d = in place (the reference's out channel is CAN_DO_INPLACE).  Rows
    r - 1 and r are written for every odd r < height - 2, everything else is left alone (alpha of 4-byte pixels: row r only,
    out of place).  LGPU_E_UNSUPPORTED: planar palettes, ARGB32 out of place, a width that is not a multiple of 3 with rows
-   too tight for the last partial triple. */
+   too tight for the last partial triple.
+   Stream capture: in place the source is snapshotted into scratch per (device, stream), grown (stream synchronisation, hipFree + hipMalloc) by a larger frame: make the
+   largest in-place call on the stream before a capture begins; a graph captured before the scratch grew holds the freed block. */
 int lgpu_deinterlace(const uint8_t *src_d, int irow, uint8_t *dst_d, int orow, int width, int height, int palette, void *stream);
 /* "triple split": lives-plugins/weed-plugins/layout_blends.c:24-113, RGB24 / BGR24.  start / end / border_width are the float parameters,
    symmetrical = "sym", split_rows = "vert", border_rgb[3] = "borderc".  src1_d == dst_d = in place (the middle band is then left alone). */
@@ -489,17 +509,31 @@ typedef struct {
                                    block rank 0 broadcasts over RCCL/xGMI in the multi-GPU batch:
                                    it is read by the kernel, stream-ordered, with no host round trip. */
 } lgpu_chain_params;
+/* Stream capture: once warm (filter banks, weight tables and the per-stream scratch of the gaussian path are created by the first call of a geometry on a stream --
+   make that call before a stream capture begins) the chain captures into a graph, except where lgpu_chain / lgpu_chain_canvas / lgpu_chain_amounts run STAGED: the
+   stages then go one by one through scratch frames from the stream-ordered pool (lgpu_malloc_ordered / lgpu_free_ordered in every call) -- make such a call between
+   graph launches, not inside a capture.  Staged are, of the calls with a resize stage:
+     - lgpu_chain_canvas without LGPU_INTERP_PIXBUF, always (lgpu_chain without the flag is the polyphase chain and captures);
+     - LGPU_INTERP_PIXBUF with do_blur, unless the one-launch 2:1 kernel takes the call: sw == 2 dw, sh == 2 dh, sw a multiple of 4, sources 16-byte and layer 2 /
+       destinations 8-byte aligned, no canvas, a layer 2 (no LGPU_INTERP_NOBLEND);
+     - LGPU_INTERP_PIXBUF without do_blur, where neither that kernel (a canvas needs an even offs_x there) nor a scaler with the chain's last stages in its store takes the
+       call: interp NEAREST (0), and geometries whose weights have no pair, gather or enlargement kernel (lgpu_debug_pixbuf_plan with LGPU_PB_PLAN_CHAIN answers
+       LGPU_PB_PATH_NOT_FUSED for both);
+     - anything under the measurement switch PB_CHAIN_GROUP. */
 int lgpu_chain(const lgpu_chain_params *params, const lgpu_chain_track *tracks, int ntracks, void *stream);
 /* the same chain with letterbox_layer (src/colourspace.c:15343-15567) between the resize and the blend -- BASELINE config 3: the scaled dw x dh frame sits at
    (offs_x, offs_y) of an nwidth x nheight canvas of opaque black (LiVES centres it: offs = (n - size + 1) >> 1, :15522-15523); layer 2 and the destination are
-   canvas-sized (irow2 / orow are their strides).  One launch on the pixbuf arithmetic for the exact aligned 2:1 case with an even offs_x; staged otherwise. */
+   canvas-sized (irow2 / orow are their strides).  One launch on the pixbuf arithmetic for the exact aligned 2:1 case with an even offs_x; staged otherwise.
+   Stream capture: the list at lgpu_chain -- in particular lgpu_chain_canvas WITHOUT LGPU_INTERP_PIXBUF and the gaussian onto a canvas are always staged through the
+   stream-ordered pool and stay outside a capture. */
 typedef struct { int nwidth, nheight, offs_x, offs_y; } lgpu_canvas;
 int lgpu_chain_canvas(const lgpu_chain_params *params, const lgpu_canvas *canvas, const lgpu_chain_track *tracks, int ntracks, void *stream);
 /* lgpu_chain / lgpu_chain_canvas (canvas may be NULL) on the gdk-pixbuf arithmetic with a blend amount PER TRACK (amounts[ntracks], 0..255; params->bf and
    params->param_block_d are not used): the tracks of a tick share geometry and gamma table, not necessarily their transition amount -- still one launch.  What
    lives_gpu_layers_flush() emits for the recorded plan steps of a tick (lives_gpu_layer.h).  Two more shapes are served here only: interp | LGPU_INTERP_NOBLEND (no
    layer 2; amounts may be NULL), and sw == dw && sh == dh -- no resize stage: [R <-> B] [-> letterbox] [-> blend] [-> gamma LUT] on frames that already have their
-   size (dst must not be src). */
+   size (dst must not be src).
+   Stream capture: the list at lgpu_chain (the form without a resize stage is one launch and captures). */
 int lgpu_chain_amounts(const lgpu_chain_params *params, const lgpu_canvas *canvas, const lgpu_chain_track *tracks, int ntracks, const uint8_t *amounts, void *stream);
 /* the same chain starting at decoded planar YUV 4:2:0 frames (YUV420P; YVU420P: pass the planes swapped): the K2 conversion (lgpu_yuv420p_to_rgb, every quirk kept,
    no gamma LUT in it) -> [R <-> B when params->swap_rb] -> scale [-> letterbox] [-> chroma blend] [-> gamma LUT], ONE launch for every track, and no RGBA frame is
