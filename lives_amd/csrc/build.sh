@@ -8,9 +8,12 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-ma
 OBJ=build
 mkdir -p $OBJ
 pids=()
-for f in runtime swizzle yuv effects resize stencil palette pixbuf fused flat; do
+for f in runtime swizzle yuv effects resize stencil palette pixbuf fused flat flat_select; do
   stale=
-  case $f in yuv|flat|pixbuf) [ k2_walk.h -nt $OBJ/$f.o ] && stale=1 ;; esac      # K2's chroma walk, shared by the three
+  case $f in yuv|flat|flat_select|pixbuf) [ k2_walk.h -nt $OBJ/$f.o ] && stale=1 ;; esac      # K2's chroma walk, shared by the four
+  case $f in flat|flat_select) [ flat_walk.h -nt $OBJ/$f.o ] && stale=1 ;; esac              # the per-cell conversions of the unscaled forms
+  case $f in effects|flat_select) [ select_pred.h -nt $OBJ/$f.o ] && stale=1 ;; esac         # the iris and dissolve predicates
+  case $f in flat_select) [ ../../include/lives_gpu_select.h -nt $OBJ/$f.o ] && stale=1 ;; esac
   if [ ! -f $OBJ/$f.o ] || [ $f.hip -nt $OBJ/$f.o ] || [ lgpu_common.h -nt $OBJ/$f.o ] || [ ../../include/lives_gpu.h -nt $OBJ/$f.o ] || [ -n "$stale" ]; then
     $HIPCC $FLAGS -c $f.hip -o $OBJ/$f.o &
     pids+=($!)

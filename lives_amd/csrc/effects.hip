@@ -10,6 +10,7 @@
 // kernel skeleton: a lane loads 4 pixels of each input (16 B for 4-byte palettes, 12 B for 3-byte ones,
 // normalised to one dword per pixel by v_perm), applies a per-pixel functor and stores 4 pixels.
 #include "lgpu_common.h"
+#include "select_pred.h"      // the iris and dissolve predicates, shared with flat_select.hip
 
 namespace lgpu {
 
@@ -714,21 +715,15 @@ struct TransArgs {
   float bf, hwidth, hheight, maxradsq;
   float uthr;                             // type 1: the largest float u with sqrt((double)(u / maxradsq)) <= bf (host, bisection over the floats): the test is u > uthr
 };
-struct TransAmt { int xx, yy; float bf, uthr; };      // what the transition amount decides: per frame of a batch
 struct TransAmts { TransAmt v[LGPU_FX_MAX_FRAMES]; };
 // where pixel (i, j / PS) comes from (multi_transitions.c:152-205), the reference's own float / double mix
 template <int PS>
 __device__ __forceinline__ const uint8_t *trans_from(const TransArgs &a, int i, int j) {
+  // the two irises: select_pred.h's predicates (k_flat_select takes the same ones)
   if (a.type == 0)
-    return (j < a.xx || j >= a.wb - a.xx || i < a.yy || i >= a.height - a.yy) ? a.src1 + (size_t)a.irow1 * i + j : a.src2 + (size_t)a.irow2 * i + j;
-  if (a.type == 1) {
-    // sqrt((xxf * xxf + yyf * yyf) / maxradsq) > bf: float terms, double square root (:185-187)
-    const float xxf = (float)(i - a.ihheight), yyf = __fdiv_rn((float)(j - a.ihwidth), (float)PS);
-    // the float division by maxradsq and the double square root are monotone in u = xxf^2 + yyf^2, so "sqrt(u / maxradsq) > bf" is "u > uthr" for the one float
-    // uthr the host finds with the same IEEE operations (exact: every float u falls on the same side); a division and a square root per pixel less
-    const float u = __fadd_rn(__fmul_rn(xxf, xxf), __fmul_rn(yyf, yyf));
-    return (u > a.uthr) ? a.src1 + (size_t)a.irow1 * i + j : a.src2 + (size_t)a.irow2 * i + j;
-  }
+    return LGPU_IRIS_RECT_SHOWS1(i, j, a.xx, a.yy, a.wb, a.height) ? a.src1 + (size_t)a.irow1 * i + j : a.src2 + (size_t)a.irow2 * i + j;
+  if (a.type == 1)
+    return LGPU_IRIS_CIRCLE_SHOWS1(PS, i, j, a.ihwidth, a.ihheight, a.uthr) ? a.src1 + (size_t)a.irow1 * i + j : a.src2 + (size_t)a.irow2 * i + j;
   const bool cross = __fdiv_rn(fabsf(__fsub_rn((float)i, a.hheight)), a.hheight) < a.bf ||
                      __fdiv_rn(fabsf(__fsub_rn((float)j, a.hwidth)), a.hwidth) < a.bf || a.bf == 1.f;
   return cross ? a.src2 + (size_t)a.irow2 * i + j
@@ -854,7 +849,7 @@ __global__ __launch_bounds__(kBlock) void k_dissolve(const uint8_t *src1, int ir
   const int x = blockIdx.x * kBlock + threadIdx.x;
   if (x >= width) return;
   for (int i = blockIdx.y; i < height; i += gridDim.y) {
-    const bool two = mask[(size_t)i * width + x] < bf;
+    const bool two = LGPU_DISSOLVE_SHOWS2(mask, width, i, x, bf);      // select_pred.h
     if (!two && inplace) continue;
     const uint8_t *s = two ? src2 + (size_t)i * irow2 + (size_t)x * PS : src1 + (size_t)i * irow1 + (size_t)x * PS;
     uint8_t *d = dst + (size_t)i * orow + (size_t)x * PS;
@@ -864,6 +859,39 @@ __global__ __launch_bounds__(kBlock) void k_dissolve(const uint8_t *src1, int ir
   }
 }
 }  // namespace lgpu
+
+// what the frame's size decides for a transition of `type`, and what the amount decides on top of it: the reference's own float / double mix (:129-150).  Shared by
+// transition_n below and the select form of the one-launch tick (flat_select.hip), so that the two derive xx, yy, bf and uthr by the same operations
+lgpu::TransGeom lgpu::transition_geometry(int type, int width, int height, int psize) {
+  lgpu::TransGeom g;
+  float hwidth = (float)width * 0.5f;
+  const float hheight = (float)height * 0.5f;
+  g.maxradsq = (type == 1) ? ((hheight * hheight) + (hwidth * hwidth)) : 0.f;
+  g.wb = width * psize;
+  hwidth = (float)g.wb * 0.5f;
+  g.hwidth = hwidth; g.hheight = hheight; g.ihwidth = g.wb >> 1; g.ihheight = height >> 1;
+  return g;
+}
+lgpu::TransAmt lgpu::transition_amount(const lgpu::TransGeom &g, int type, int psize, int irow1, double amount) {
+  lgpu::TransAmt m;
+  m.bf = (float)amount;
+  m.uthr = 0.f;
+  if (type == 1) {
+    auto pred = [&](uint32_t bits) { float u; __builtin_memcpy(&u, &bits, 4); const volatile float q = u / g.maxradsq; return sqrt((double)q) > (double)m.bf; };
+    if (pred(0u)) m.uthr = -1.f;                                 // true for every u >= 0
+    else {
+      uint32_t lo = 0u, hi = 0x7F7FFFFFu;                        // pred(lo) false; the largest finite float
+      if (!pred(hi)) lo = hi;
+      else while (hi - lo > 1u) { const uint32_t mid = lo + (hi - lo) / 2u; if (pred(mid)) hi = mid; else lo = mid; }
+      __builtin_memcpy(&m.uthr, &lo, 4);
+    }
+  }
+  const float bfneg = 1.f - m.bf;
+  m.xx = m.yy = 0;
+  if (type == 0) { m.xx = (int)((int)g.hwidth * bfneg + .5); m.yy = (int)((int)g.hheight * bfneg + .5); }
+  else if (type == 2) { m.xx = (int)(g.hheight * m.bf + .5) * irow1; m.yy = (int)(g.hwidth / (float)psize * m.bf + .5) * psize; }
+  return m;
+}
 
 int lgpu::transition_n(const FxFrames &F, int nframes, int type, int irow1, int irow2, int orow, int width, int height, int psize, const double *amounts, hipStream_t st) {
   LGPU_REQUIRE(type >= 0 && type <= 2, "type must be 0 (iris rectangle), 1 (iris circle) or 2 (4 way split)");
@@ -879,33 +907,10 @@ int lgpu::transition_n(const FxFrames &F, int nframes, int type, int irow1, int 
   lgpu::TransAmts A = {};
   a.src1 = nullptr; a.src2 = nullptr; a.dst = nullptr; a.irow1 = irow1; a.irow2 = irow2; a.orow = orow;
   a.width = width; a.height = height; a.type = type;
-  // the reference's own float / double mix (:129-150)
-  float hwidth = (float)width * 0.5f;
-  const float hheight = (float)height * 0.5f;
-  a.maxradsq = (type == 1) ? ((hheight * hheight) + (hwidth * hwidth)) : 0.f;
-  a.wb = width * psize;
-  hwidth = (float)a.wb * 0.5f;
-  a.hwidth = hwidth; a.hheight = hheight; a.ihwidth = a.wb >> 1; a.ihheight = height >> 1;
+  const lgpu::TransGeom g = lgpu::transition_geometry(type, width, height, psize);
+  a.maxradsq = g.maxradsq; a.wb = g.wb; a.hwidth = g.hwidth; a.hheight = g.hheight; a.ihwidth = g.ihwidth; a.ihheight = g.ihheight;
   a.bf = 0.f; a.uthr = 0.f; a.xx = a.yy = 0;                       // per frame: the kernel takes them from A
-  for (int f = 0; f < nframes; f++) {
-    lgpu::TransAmt &m = A.v[f];
-    m.bf = (float)amounts[f];
-    m.uthr = 0.f;
-    if (type == 1) {
-      auto pred = [&](uint32_t bits) { float u; __builtin_memcpy(&u, &bits, 4); const volatile float q = u / a.maxradsq; return sqrt((double)q) > (double)m.bf; };
-      if (pred(0u)) m.uthr = -1.f;                                 // true for every u >= 0
-      else {
-        uint32_t lo = 0u, hi = 0x7F7FFFFFu;                        // pred(lo) false; the largest finite float
-        if (!pred(hi)) lo = hi;
-        else while (hi - lo > 1u) { const uint32_t mid = lo + (hi - lo) / 2u; if (pred(mid)) hi = mid; else lo = mid; }
-        __builtin_memcpy(&m.uthr, &lo, 4);
-      }
-    }
-    const float bfneg = 1.f - m.bf;
-    m.xx = m.yy = 0;
-    if (type == 0) { m.xx = (int)((int)hwidth * bfneg + .5); m.yy = (int)((int)hheight * bfneg + .5); }
-    else if (type == 2) { m.xx = (int)(hheight * m.bf + .5) * irow1; m.yy = (int)(hwidth / (float)psize * m.bf + .5) * psize; }
-  }
+  for (int f = 0; f < nframes; f++) A.v[f] = lgpu::transition_amount(g, type, psize, irow1, amounts[f]);
   const int qpr = (width + 3) / 4;                                  // groups of four pixels per row
   LGPU_REQUIRE((long long)qpr * height < (1ll << 31), "frame too large");
   const unsigned total = (unsigned)qpr * (unsigned)height;

@@ -22,6 +22,7 @@
 // into a decoded clip, two 4:2:2 clips in a transition, a 4:2:0 clip into a 4:2:2 one -- each one launch with no RGBA frame anywhere.
 #include "lgpu_common.h"
 #include "k2_walk.h"
+#include "flat_walk.h"      // flat_cell, flat_row422, flat_cell422: the per-cell conversions, shared with flat_select.hip
 #include <algorithm>
 #include <string.h>
 
@@ -31,7 +32,6 @@ int get_sink_tables(int which_tables, int in_order, const uint2 **out);      // 
 namespace lgpu {
 
 constexpr int kFlatPlanarTracks = 32;     // tracks per launch with the 4:2:0 sink (seven pointers per track: 64 would not fit HIP's 4 KB of kernel arguments)
-constexpr int kFlatWgTarget = 2048;       // workgroups a launch aims at: each walks nunits * gx * ntracks / 2048 units (at least one) on one staging of the tables
 
 struct FlatArgs {
   const int32_t *tables;         // device [5][256] RGB_Y R_Cr G_Cb G_Cr B_Cb
@@ -84,148 +84,6 @@ static_assert(sizeof(FlatArgs) + sizeof(FlatTr<0>::type) + sizeof(Lut8) <= 4096 
               sizeof(FlatArgs) + sizeof(FlatTr<0, 2>::type) + sizeof(Lut8) <= 4096 && sizeof(FlatArgs) + sizeof(FlatTr<2, 2>::type) + sizeof(Lut8) <= 4096 &&
               sizeof(FlatArgs) + sizeof(FlatTr<0, 3>::type) + sizeof(Lut8) <= 4096 && sizeof(FlatArgs) + sizeof(FlatTr<2, 3>::type) + sizeof(Lut8) <= 4096,
               "HIP documents 4 KB of arguments for a __global__ function");
-
-// an address or pitch as a multiple of n (a power of two).  Every alignment decision of this file goes through it, in the kernel and in the entry points;
-// tests/test_chain_flat.py walks each class they tell apart (test_chain_flat_addresses, test_chain_flat_refusals)
-__host__ __device__ static inline bool multiple_of(uintptr_t v, unsigned n) { return v % n == 0; }
-
-// one layer's planes as K2 reads them, and the staged K2 tables they are converted with
-struct FlatPlanes {
-  const uint8_t *y, *u, *v;
-  uint32_t usize, vsize;         // chroma plane bytes; K2's read one past the last row's end is clamped to the last byte of THIS layer's plane
-  int ys, us, vs;
-  int lowq, fix_edges;
-};
-struct FlatK2Lds { const uint32_t *ty; const uint2 *rg, *gb; };
-template <int KIND> struct FlatCell { static constexpr int value = KIND; };      // 0: row 0, 1: a row pair, 2: the trailing row
-
-// xyuv2rgb on the paired tables; the chroma index is the blended value itself
-template <int SWAP>
-__device__ __forceinline__ uint32_t flat_px(const FlatK2Lds &L, uint32_t yv, uint32_t iu, uint32_t iv) {
-  const uint32_t yy = L.ty[yv];
-  const uint2 rg = L.rg[iv], gb = L.gb[iu];
-  uint32_t r, g, b;
-  yuv_rgb(yy, rg.x, rg.y, gb.x, gb.y, r, g, b);
-  return SWAP ? (b | (g << 8) | (r << 16) | 0xFF000000u) : (r | (g << 8) | (b << 16) | 0xFF000000u);
-}
-
-// K2's walk (k2_walk.h) for cell (unit, k) of one layer: its two pixels of one row or its 2 x 2 quad go to out(FlatCell<KIND>, first row, chroma row, p0, p1, second row's p0, p1).  Either layer
-// of the L2YUV forms comes through here when it is planar 4:2:0, each with its own planes and tables
-template <int SWAP, class Out>
-__device__ __forceinline__ void flat_cell(const FlatPlanes &P, const FlatK2Lds &L, int unit, int k, int hw, int H, int npairs, Out &&out) {
-  const uint8_t *py = P.y, *pu = P.u, *pv = P.v;
-  auto PU = [&](int r, int kk) -> uint32_t { long i = (long)r * P.us + kk; return pu[i < (long)P.usize ? i : (long)P.usize - 1]; };
-  auto PV = [&](int r, int kk) -> uint32_t { long i = (long)r * P.vs + kk; return pv[i < (long)P.vsize ? i : (long)P.vsize - 1]; };
-  auto ld32 = [](const uint8_t *p) -> uint32_t { uint32_t w; __builtin_memcpy(&w, p, 4); return w; };
-  auto ld16 = [](const uint8_t *p) -> uint32_t { uint16_t w; __builtin_memcpy(&w, p, 2); return w; };
-  auto px = [&](uint32_t yv, uint32_t iu, uint32_t iv) -> uint32_t { return flat_px<SWAP>(L, yv, iu, iv); };
-  // K2's vblend: (2a + b) / 3 and (a + 2b) / 3 on doubled sums, or the halves with pb_quality LOW
-  auto vtop = [&](uint32_t s1, uint32_t s2) -> uint32_t { return P.lowq ? s1 >> 1 : yuv_third(s1, s2); };
-  auto vbot = [&](uint32_t s1, uint32_t s2) -> uint32_t { return P.lowq ? s2 >> 1 : yuv_third(s2, s1); };
-  if (unit == 0) {
-    const uint32_t yy = ld16(py + 2 * k);
-    uint32_t p0, p1;
-    k2_row_pixels(k2_row_edge(0, k, hw, PU, PV), yy & 0xFF, yy >> 8, px, p0, p1);
-    out(FlatCell<0>(), 0, 0, p0, p1, 0u, 0u);
-  } else if (unit <= npairs) {
-    // rows (i, i + 1), chroma rows r and r + 1
-    const int i = 2 * unit - 1, r = unit - 1;
-    const uint32_t ya = ld16(py + (size_t)i * P.ys + 2 * k), yb = ld16(py + (size_t)(i + 1) * P.ys + 2 * k);
-    // k2_walk.h's k2_pair_samples + k2_pair_pixels (rules b-f) in this kernel's own text and statement order: through the header two instantiations ran 0.6 % slower
-    // (profiles/r18/k2_walk.md)
-    uint32_t u_l, u_c, u_n, u1_c, u1_n, v_c, v_n, v1_l, v1_c, v1_n, v1_0;
-    const long ou = (long)(r + 1) * P.us, ov = (long)(r + 1) * P.vs;
-    if (k >= 1 && ou + k + 3 <= (long)P.usize && ov + k + 3 <= (long)P.vsize) {
-      // interior: one 4-byte window (columns k - 1 .. k + 2, the last unused) per chroma row
-      const uint32_t wu0 = ld32(pu + (ou - P.us + k - 1)), wu1 = ld32(pu + (ou + k - 1)), wv0 = ld32(pv + (ov - P.vs + k - 1)), wv1 = ld32(pv + (ov + k - 1));
-      v1_0 = pv[ov];
-      u_l = wu0 & 0xFF; u_c = (wu0 >> 8) & 0xFF; u_n = (wu0 >> 16) & 0xFF; u1_c = (wu1 >> 8) & 0xFF; u1_n = (wu1 >> 16) & 0xFF;
-      v_c = (wv0 >> 8) & 0xFF; v_n = (wv0 >> 16) & 0xFF; v1_l = wv1 & 0xFF; v1_c = (wv1 >> 8) & 0xFF; v1_n = (wv1 >> 16) & 0xFF;
-    } else {
-      u_c = PU(r, k); v_c = PV(r, k); v1_c = PV(r + 1, k);
-      u_l = k ? PU(r, k - 1) : u_c;
-      v1_l = k ? PV(r + 1, k - 1) : v_c;
-      v1_0 = PV(r + 1, 0);
-      u_n = PU(r, k + 1); u1_c = PU(r + 1, k); u1_n = PU(r + 1, k + 1);
-      v_n = PV(r, k + 1); v1_n = PV(r + 1, k + 1);
-    }
-    const uint32_t su = u_c + u_l, s1v = v_c + v1_l, s2v = v1_c + v1_0;
-    const uint32_t a0 = px(ya & 0xFF, vtop(su, su), vtop(s1v, s2v)), b0 = px(yb & 0xFF, vbot(su, su), vbot(s1v, s2v));
-    const uint32_t s1u = u_c + u_n, s2u = u1_c + u1_n, s1w = v_c + v_n, s2w = v1_c + v1_n;
-    const uint32_t a1 = px(ya >> 8, vtop(s1u, s2u), vtop(s1w, s2w)), b1 = px(yb >> 8, vbot(s1u, s2u), vbot(s1w, s2w));
-    out(FlatCell<1>(), i, r, a0, a1, b0, b1);
-  } else {
-    // trailing row H - 1
-    const int i = H - 1, r = i >> 1;
-    // k2_walk.h's k2_trailing_pixels (rules g, h) in this kernel's own text
-    const int kp = k ? k - 1 : 0, kn = (k + 1 < hw) ? k + 1 : hw - 1;
-    const uint32_t yy = ld16(py + (size_t)i * P.ys + 2 * k), uk = PU(r, k), vk = PV(r, k);
-    uint32_t p0;
-    if (P.fix_edges) p0 = px(yy & 0xFF, (uk + PU(r, kp)) >> 1, (vk + PV(r, kp)) >> 1);
-    else {
-      const uint32_t tu = k ? PU(0, k) : PU(r, 0), tv = k ? PV(0, k) : PV(r, 0);
-      const uint32_t lu = (k >= 2) ? PU(0, k - 1) : PU(r, 0), lv = (k >= 2) ? PV(0, k - 1) : PV(r, 0);
-      p0 = px(py[2 * k], (tu + lu) >> 1, (tv + lv) >> 1);
-    }
-    const uint32_t p1 = px(yy >> 8, (uk + PU(r, kn)) >> 1, (vk + PV(r, kn)) >> 1);
-    out(FlatCell<2>(), i, r, p0, p1, 0u, 0u);
-  }
-}
-
-// one row's pixel pair of cell k of a 4:2:2 frame (the SRC policies of k_flat_yuv420 for layer 1, L2YUV - 1 for layer 2).
-// SRC == 1, planar (YUV422P): K2's 4:2:2 row (k2_walk.h, rules i and e); pb_quality and LGPU_YUV_FIX_EDGES change nothing in this walk.
-// SRC == 2, packed (UYVY / YUYV): K3's conversion (palette.hip k_yuv_to_rgb / k_uyvy_to_rgb_s, uyvy2rgb :2410-2415, yuyv2rgb :2418-2423): both pixels of a macropixel
-// under its own U and V, no interpolation and no chroma clamp (the host stages the tables with the identity index); one aligned dword per lane and row
-template <int SWAP, int SRC>
-__device__ __forceinline__ void flat_row422(const FlatPlanes &P, const FlatK2Lds &L, int sfmt, int i, int k, uint32_t &p0, uint32_t &p1) {
-  auto px = [&](uint32_t yv, uint32_t iu, uint32_t iv) -> uint32_t { return flat_px<SWAP>(L, yv, iu, iv); };
-  if constexpr (SRC == 2) {
-    const uint32_t m = *reinterpret_cast<const uint32_t *>(P.y + (size_t)i * P.ys + 4 * (size_t)k);
-    uint32_t y0, y1, u, v;
-    if (sfmt == 2) { u = m & 0xFF; y0 = (m >> 8) & 0xFF; v = (m >> 16) & 0xFF; y1 = m >> 24; }
-    else { y0 = m & 0xFF; u = (m >> 8) & 0xFF; y1 = (m >> 16) & 0xFF; v = m >> 24; }
-    p0 = px(y0, u, v); p1 = px(y1, u, v);
-  } else {
-    const uint8_t *pu = P.u, *pv = P.v;
-    auto PU = [&](int r, int kk) -> uint32_t { long q = (long)r * P.us + kk; return pu[q < (long)P.usize ? q : (long)P.usize - 1]; };
-    auto PV = [&](int r, int kk) -> uint32_t { long q = (long)r * P.vs + kk; return pv[q < (long)P.vsize ? q : (long)P.vsize - 1]; };
-    uint16_t yy;
-    __builtin_memcpy(&yy, P.y + (size_t)i * P.ys + 2 * k, 2);
-    const long ou = (long)i * P.us + k, ov = (long)i * P.vs + k;
-    K2Row<uint32_t> s;
-    if (k >= 2 && ou + 3 <= (long)P.usize && ov + 3 <= (long)P.vsize) {
-      // interior (no seeded sample from column 2 on): one 4-byte window (columns k - 1 .. k + 2, the last unused) per chroma plane
-      uint32_t wu, wv;
-      __builtin_memcpy(&wu, pu + (ou - 1), 4); __builtin_memcpy(&wv, pv + (ov - 1), 4);
-      s.lu = wu & 0xFF; s.tu = (wu >> 8) & 0xFF; s.nu = (wu >> 16) & 0xFF;
-      s.lv = wv & 0xFF; s.tv = (wv >> 8) & 0xFF; s.nv = (wv >> 16) & 0xFF;
-    } else {
-      // k2_walk.h's k2_row_422 (rules i and e) in this function's own text: through the header four instantiations take one more register
-      s.tu = k ? PU(i, k) : PU(i >> 1, 0); s.tv = k ? PV(i, k) : PV(i >> 1, 0);
-      s.lu = (k >= 2) ? PU(i, k - 1) : PU(i >> 1, 0); s.lv = (k >= 2) ? PV(i, k - 1) : PV(i >> 1, 0);
-      s.nu = PU(i, k + 1); s.nv = PV(i, k + 1);
-    }
-    k2_row_pixels(s, yy & 0xFFu, (uint32_t)yy >> 8, px, p0, p1);
-  }
-}
-
-// the unit walk of flat_cell over a 4:2:2 frame: the same cells go to out() -- row 0, a row pair, the trailing row -- each row converted on its own
-template <int SWAP, int SRC, class Out>
-__device__ __forceinline__ void flat_cell422(const FlatPlanes &P, const FlatK2Lds &L, int sfmt, int unit, int k, int H, int npairs, Out &&out) {
-  uint32_t a0, a1, b0, b1;
-  if (unit == 0) {
-    flat_row422<SWAP, SRC>(P, L, sfmt, 0, k, a0, a1);
-    out(FlatCell<0>(), 0, 0, a0, a1, 0u, 0u);
-  } else if (unit <= npairs) {
-    const int i = 2 * unit - 1;
-    flat_row422<SWAP, SRC>(P, L, sfmt, i, k, a0, a1);
-    flat_row422<SWAP, SRC>(P, L, sfmt, i + 1, k, b0, b1);
-    out(FlatCell<1>(), i, unit - 1, a0, a1, b0, b1);
-  } else {
-    flat_row422<SWAP, SRC>(P, L, sfmt, H - 1, k, a0, a1);
-    out(FlatCell<2>(), H - 1, (H - 1) >> 1, a0, a1, 0u, 0u);
-  }
-}
 
 // SINK: 0 RGBA, 1 packed 4:2:2 (UYVY / YUYV), 2 planar 4:2:0.  SWAP: the finished pixel is BGRA (src->out_order ^ params->swap_rb).  L2YUV: layer 2 is a decoded frame
 // of the same size (BLEND is 1; with a canvas, lgpu_chain_flat_yuv_mix_canvas, both layers sit at the same place on it) -- 1 planar 4:2:0, 2 planar 4:2:2, 3 packed 4:2:2 (T.sfmt2: UYVY / YUYV; T.y2 is the frame, T.u2 / T.v2 are not read): the

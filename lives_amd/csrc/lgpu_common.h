@@ -59,6 +59,13 @@ int blend_chroma_n(const FxFrames &X, int nframes, int irow1, int irow2, int oro
 int blend_luma_n(const FxFrames &X, int nframes, int type, int irow1, int irow2, int orow, int width, int height, int psize, int pal_order, const int *thresh, hipStream_t st);
 int blend_multi_n(const FxFrames &X, int nframes, int type, int irow1, int irow2, int orow, int width, int height, int is_bgr, const int *bf, hipStream_t st);
 int transition_n(const FxFrames &F, int nframes, int type, int irow1, int irow2, int orow, int width, int height, int psize, const double *amounts, hipStream_t st);
+// the geometric transitions (multi_transitions.c:129-150): what the frame's size decides (TransGeom) and what the transition amount decides on top of it (TransAmt),
+// derived on the host by the reference's own float / double mix (effects.hip).  lgpu_transition / lgpu_fx_batch and the select form of the one-launch tick
+// (flat_select.hip) both call these, so one amount gives one figure.  irow1 is read for type 2 (4 way split) only
+struct TransGeom { int wb, ihwidth, ihheight; float hwidth, hheight, maxradsq; };      // wb: bytes of a row (width * psize)
+struct TransAmt { int xx, yy; float bf, uthr; };      // type 0: rectangle insets (bytes, rows); type 1: uthr, the largest float u with sqrt((double)(u / maxradsq)) <= bf
+TransGeom transition_geometry(int type, int width, int height, int psize);
+TransAmt transition_amount(const TransGeom &g, int type, int psize, int irow1, double amount);
 int gauss5_colorkey_n(const FxFrames &F, int nframes, int irow0, int irow1, int orow, int width, int height, int psize, int is_bgr, double delta, double opac,
                       int col_r, int col_g, int col_b, hipStream_t st);
 int yuv411_to_rgb_n(const FxFrames &F, int nframes, int width_mp, int height, int orow, int out_order, int out_alpha, int clamping_unclamped, hipStream_t st);

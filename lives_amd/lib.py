@@ -18,6 +18,8 @@ u8p = ctypes.POINTER(ctypes.c_uint8)
 
 LGPU_CHAIN_MAX_TRACKS = 64
 LGPU_CHAIN_MIX_TRACKS = 32
+LGPU_CHAIN_SELECT_TRACKS = 32
+SELECT_IRIS_RECT, SELECT_IRIS_CIRCLE, SELECT_DISSOLVE = 0, 1, 3      # lgpu_select.kind: multi_transitions.c's `type`
 
 (SWAP3, SWAP4, SWAP3ADDPOST, SWAP3ADDPRE, SWAP3POSTALPHA, SWAP3PREALPHA, ADDPOST, ADDPRE, SWAP3DELPOST, DELPOST,
  DELPRE, SWAP3DELPRE, SWAPPREPOST) = range(13)
@@ -81,6 +83,11 @@ class Yuv422Source(ctypes.Structure):
 class YuvLayerSource(ctypes.Structure):
     """lgpu_yuv_layer_source"""
     _fields_ = [("in_fmt", ci), ("istrides", ci * 3), ("u_size", cl), ("v_size", cl), ("out_order", ci), ("which_tables", ci), ("pb_quality", ci), ("flags", ci)]
+
+
+class Select(ctypes.Structure):
+    """lgpu_select (include/lives_gpu_select.h)"""
+    _fields_ = [("kind", ci), ("amounts", ctypes.POINTER(cd)), ("mask_d", ctypes.POINTER(vp))]
 
 
 class Canvas(ctypes.Structure):
@@ -273,6 +280,11 @@ PROTOTYPES = {
     "lgpu_chain_timed": [ctypes.POINTER(ChainParams), ctypes.POINTER(ChainTrack), ci, ci, ctypes.POINTER(ctypes.c_float), vp],
 }
 
+# the entry points of include/lives_gpu_select.h, in a table of their own: PROTOTYPES is held to include/lives_gpu.h in both directions
+SELECT_PROTOTYPES = {
+    "lgpu_chain_flat_yuv_select": [vp, vp, vp, ctypes.POINTER(Select), vp, vp, vp, ci, vp],
+}
+
 _lib = None
 
 
@@ -284,7 +296,7 @@ def load():
             raise LgpuError("%s is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                             "(lives_amd/csrc/build.sh).  There is no CPU fallback." % SO_PATH)
         lib = ctypes.CDLL(SO_PATH)
-        for name, args in PROTOTYPES.items():
+        for name, args in list(PROTOTYPES.items()) + list(SELECT_PROTOTYPES.items()):
             fn = getattr(lib, name)
             fn.argtypes = args
             fn.restype = ci

@@ -633,6 +633,33 @@ def chain_flat_yuv_mix_canvas(params, src, src2, tracks, amounts, canvas=None, c
     return lib.call("lgpu_chain_flat_yuv_mix_canvas", *args)
 
 
+def select(kind, amounts, masks=None):
+    """lgpu_select: kind 0 iris rectangle / 1 iris circle / 3 dissolve, one amount (0..1) per track and, for the dissolve, one device tensor of (canvas or frame) width *
+    height floats per track.  The arrays it points to are kept alive on the returned struct"""
+    n = max(1, len(amounts) if amounts is not None else 0)
+    s = lib.Select()
+    s.kind = kind
+    s._amounts = (ctypes.c_double * n)(*[float(a) for a in amounts]) if amounts is not None else None
+    s.amounts = ctypes.cast(s._amounts, ctypes.POINTER(ctypes.c_double)) if s._amounts is not None else None
+    s._masks = (ctypes.c_void_p * max(1, len(masks)))(*[m if m is None or isinstance(m, int) else m.data_ptr() for m in masks]) if masks is not None else None
+    s.mask_d = ctypes.cast(s._masks, ctypes.POINTER(ctypes.c_void_p)) if s._masks is not None else None
+    return s
+
+
+def chain_flat_yuv_select(params, src, src2, tracks, kind, amounts, masks=None, sink=None, canvas=None, check=True):
+    """lgpu_chain_flat_yuv_select (include/lives_gpu_select.h): two decoded frames of the project's size, each YUV420P, YUV422P, UYVY or YUYV, through a select transition
+    -- kind 0 iris rectangle, 1 iris circle, 3 dissolve (masks: a device tensor of floats per track) -- in one launch that converts only the layer a pixel shows; to
+    RGBA (sink=None, rowstride params.orow; canvas = (nwidth, nheight, offs_x, offs_y) letterboxes both layers and the figure is the canvas's) or to a YUV sink.  src /
+    src2: yuv_layer_source; tracks: chain_yuv_mix_tracks; amounts: 0..1 per track.  check=False returns the library's code instead of raising (tests of the refusals)"""
+    sel = select(kind, amounts, masks)
+    cv = lib.Canvas(*canvas) if canvas is not None else None
+    args = (ctypes.byref(params), ctypes.byref(src), ctypes.byref(src2), ctypes.byref(sel), ctypes.byref(cv) if cv is not None else None,
+            ctypes.byref(sink) if sink is not None else None, tracks, len(tracks), stream_ptr())
+    if not check:
+        return lib.load().lgpu_chain_flat_yuv_select(*args)
+    return lib.call("lgpu_chain_flat_yuv_select", *args)
+
+
 def stream_probe(params, tracks, reps):
     """lgpu_debug_stream_probe: the chain's algorithmic bytes as a bare stream on the same frames, ms for `reps` launches (destinations left dirty)"""
     ms = ctypes.c_float()
