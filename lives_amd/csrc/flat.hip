@@ -20,9 +20,13 @@
 //
 // lgpu_chain_flat_yuv_mix: L2YUV is layer 2's source policy as SRC is layer 1's (1 planar 4:2:0, 2 YUV422P, 3 packed), and the two combine freely: a camera fading
 // into a decoded clip, two 4:2:2 clips in a transition, a 4:2:0 clip into a 4:2:2 one -- each one launch with no RGBA frame anywhere.
+//
+// Host side: every entry point describes its layers (flat_layer) and tracks (FlatTrack) and calls flat_run: the refusal sequence and the plan (flat_plan), FlatArgs
+// and the tracks struct filled from them, the launch shape, one dispatch point.  flat_plan.h declares what flat_select.hip's entry point shares; it is defined here.
 #include "lgpu_common.h"
 #include "k2_walk.h"
-#include "flat_walk.h"      // flat_cell, flat_row422, flat_cell422: the per-cell conversions, shared with flat_select.hip
+#include "flat_walk.h"      // flat_cell, flat_row422, flat_cell422, flat_stage_k2, flat_bar_xy: the device text shared with flat_select.hip
+#include "flat_plan.h"      // the host side shared with flat_select.hip (defined below): layer description, track record, refusal sequence, launch shape, dispatch
 #include <algorithm>
 #include <string.h>
 
@@ -75,8 +79,6 @@ template <> struct FlatTr<2, 0> { typedef FlatTracksT<kFlatPlanarTracks, 3> type
 template <int SINK> struct FlatTr<SINK, 3> { typedef FlatMixTracksPackedT<LGPU_CHAIN_MIX_TRACKS, SINK == 2 ? 3 : 1> type; };
 template <int SINK> struct FlatSinkLds { uint2 t[6 * 256]; };
 template <> struct FlatSinkLds<0> {};
-template <int NT, int NDST> static inline void set_sfmt2(FlatMixTracksT<NT, NDST> &, int) {}
-template <int NT, int NDST> static inline void set_sfmt2(FlatMixTracksPackedT<NT, NDST> &T, int sfmt2) { T.sfmt2 = sfmt2; }
 template <int L2YUV> struct FlatL2Lds { uint32_t ty[256]; uint2 rg[256], gb[256]; };      // layer 2's own K2 tables (5 KB), staged when its table set or index clamp differs
 template <> struct FlatL2Lds<0> {};
 static_assert(sizeof(FlatArgs) + sizeof(FlatTr<0>::type) + sizeof(Lut8) <= 4096 && sizeof(FlatArgs) + sizeof(FlatTr<2>::type) + sizeof(Lut8) <= 4096 &&
@@ -110,10 +112,8 @@ __global__ __launch_bounds__(256) void k_flat_yuv420(const FlatArgs A, const typ
       const int bb = ((int)blockIdx.y - A.gy_units) * (int)gridDim.x + (int)blockIdx.x, nbb = ((int)gridDim.y - A.gy_units) * (int)gridDim.x;
       const int top = A.oy * A.cw, bottom = (A.ch - A.oy - A.h) * A.cw, sw_ = A.cw - A.w, total = top + bottom + A.h * sw_;
       for (long p = (long)bb * 256 + tid; p < total; p += (long)nbb * 256) {
-        int q = (int)p, x, y;
-        if (q < top) { y = q / A.cw; x = q - y * A.cw; }
-        else if (q < top + bottom) { q -= top; y = q / A.cw; x = q - y * A.cw; y += A.oy + A.h; }
-        else { q -= top + bottom; y = q / sw_; x = q - y * sw_; y += A.oy; if (x >= A.ox) x += A.w; }
+        int x, y;
+        flat_bar_xy((int)p, top, bottom, sw_, A.cw, A.ox, A.oy, A.w, A.h, x, y);
         uint32_t c = 0xFF000000u;
         if constexpr (L2YUV) c = pb_chroma_opaque(c, 0xFF000000u, bf, nbf);
         else if (BLEND) c = pb_chroma_rgba(c, reinterpret_cast<const uint32_t *>(T.l2[z] + (size_t)y * A.irow2)[x], bf, nbf);
@@ -124,24 +124,13 @@ __global__ __launch_bounds__(256) void k_flat_yuv420(const FlatArgs A, const typ
     }
   }
   {
-    // K2's tables, paired: the entry of an UNCLAMPED blended chroma value e is tables[clamp(e)] (CLAMP16_240 is 16 below 16 and 240 from 0xF0 up on 0..255)
-    const int clo = A.clamped ? 16 : 0, chi = A.clamped ? 240 : 255;
-    const int ec = tid < clo ? clo : tid > chi ? chi : tid;
-    s_ty[tid] = (uint32_t)A.tables[tid];
-    s_rg[tid] = make_uint2((uint32_t)A.tables[256 + ec], (uint32_t)A.tables[768 + ec]);
-    s_gb[tid] = make_uint2((uint32_t)A.tables[512 + ec], (uint32_t)A.tables[1024 + ec]);
+    flat_stage_k2(tid, A.tables, A.clamped, s_ty, s_rg, s_gb);
     if constexpr (SINK != 0) {
 #pragma unroll
       for (int i = 0; i < 6; i++) s_sink.t[tid + 256 * i] = A.stab[tid + 256 * i];
     }
     if constexpr (L2YUV) {
-      if (T.tables2) {        // layer 2's own tables, its own chroma clamp in the index
-        const int clo2 = T.clamped2 ? 16 : 0, chi2 = T.clamped2 ? 240 : 255;
-        const int e2 = tid < clo2 ? clo2 : tid > chi2 ? chi2 : tid;
-        s_l2.ty[tid] = (uint32_t)T.tables2[tid];
-        s_l2.rg[tid] = make_uint2((uint32_t)T.tables2[256 + e2], (uint32_t)T.tables2[768 + e2]);
-        s_l2.gb[tid] = make_uint2((uint32_t)T.tables2[512 + e2], (uint32_t)T.tables2[1024 + e2]);
-      }
+      if (T.tables2) flat_stage_k2(tid, T.tables2, T.clamped2, s_l2.ty, s_l2.rg, s_l2.gb);        // layer 2's own tables, its own chroma clamp in the index
     }
   }
   __syncthreads();
@@ -229,160 +218,184 @@ __global__ __launch_bounds__(256) void k_flat_yuv420(const FlatArgs A, const typ
 
 using namespace lgpu;
 
-// all six entry points: tracks in the sink form's layout (the RGBA form's destination is dst_d[0]); cv or sk is null.  ys2 / mix: the second source and the
-// caller's tracks of the mix forms (layer 2's planes are read from them; tracks[].layer2_d is null then), null otherwise; with cv both layers are letterboxed onto it.  sfmt / sfmt2: each layer's format,
-// 4 planar 4:2:0, 5 planar 4:2:2, 2 UYVY, 3 YUYV (a packed frame is y_d / y2_d with rowstride istrides[0]; the entry points zero the rest of its source)
-static int flat_impl(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv_source *ys, const lgpu_canvas *cv, const lgpu_chain_sink *sk,
-                     const lgpu_chain_yuv_sink_track *tracks, int ntracks, const uint8_t *amounts, void *stream, const lgpu_yuv_source *ys2 = nullptr,
-                     const lgpu_chain_yuv_mix_track *mix = nullptr, int sfmt = 4, int sfmt2 = 4) {
-#define FLAT_REQUIRE(cond, msg) do { if (!(cond)) { set_error("%s: %s", fn, msg); return LGPU_E_BADARG; } } while (0)
-#define FLAT_REFUSE(msg) do { set_error("%s: %s", fn, msg); return LGPU_E_UNSUPPORTED; } while (0)
-  const bool noblend = (pr->interp & LGPU_INTERP_NOBLEND) != 0;
-  const bool l2rgba = !noblend && !ys2;      // layer 2 is an RGBA frame of rowstride params->irow2
-  FLAT_REQUIRE(pr->interp & LGPU_INTERP_PIXBUF, "the gdk-pixbuf arithmetic only (LGPU_INTERP_PIXBUF)");
-  FLAT_REQUIRE(!ys2 || !noblend, "LGPU_INTERP_NOBLEND leaves nothing to mix: lgpu_chain_flat_yuv420p[_to_yuv]");
-  FLAT_REQUIRE(amounts || noblend, "null amounts");
-  const bool packed = sfmt == 2 || sfmt == 3;
-  const int srcp = packed ? 2 : sfmt == 5 ? 1 : 0;      // the kernel's SRC policy
-  const bool packed2 = ys2 && (sfmt2 == 2 || sfmt2 == 3);
-  const int l2p = !ys2 ? 0 : packed2 ? 3 : sfmt2 == 5 ? 2 : 1;      // the kernel's L2YUV policy
-  const int hw = pr->sw >> 1, lys = ys->istrides[0], us = packed ? 0 : ys->istrides[1], vs = packed ? 0 : ys->istrides[2];
-  const long usz = packed ? 0 : ys->u_size, vsz = packed ? 0 : ys->v_size;
-  int rc;
-  if ((rc = check_yuv_source(fn, pr, ys, sfmt)) || (ys2 && (rc = check_yuv_source(fn, pr, ys2, sfmt2)))) return rc;
-  const int chain_order = (ys->out_order ^ (pr->swap_rb ? 1 : 0)) & 1;
-  FLAT_REQUIRE(!ys2 || ys2->out_order == chain_order, "src2->out_order must state the byte order the blend works in: src->out_order ^ params->swap_rb");
-  const bool planar = sk && sk->out_fmt >= 4;
-  const int nplanes = planar ? 3 : 1;
-  const int cw = cv && !sk ? cv->nwidth : pr->dw, ch = cv && !sk ? cv->nheight : pr->dh;
-  if ((rc = sk ? check_yuv_sink(fn, pr, sk, chain_order, l2rgba) : check_rgba_dest(fn, pr, cv, l2rgba))) return rc;
-  uintptr_t pb = 0, sb = 0, sb2 = 0;
+// ---- the plan of every lgpu_chain_flat_* entry point (flat_plan.h) ----
+static FlatLayer make_layer(int fmt, const int istrides[3], long u_size, long v_size, int out_order, int which_tables, int pb_quality, int flags) {
+  FlatLayer l;
+  memset(&l, 0, sizeof l);
+  l.fmt = fmt; l.packed = fmt == 2 || fmt == 3; l.policy = l.packed ? 2 : fmt == 5 ? 1 : 0;
+  l.ys.istrides[0] = istrides[0];
+  if (!l.packed) { l.ys.istrides[1] = istrides[1]; l.ys.istrides[2] = istrides[2]; l.ys.u_size = u_size; l.ys.v_size = v_size; }
+  l.ys.out_order = out_order; l.ys.which_tables = which_tables; l.ys.pb_quality = pb_quality; l.ys.flags = flags;
+  l.tables = device_tables()->yuv2rgb[which_tables & 3];
+  l.clamped = !l.packed && !(which_tables & 1);
+  l.lowq = pb_quality == 1; l.fix_edges = (flags & LGPU_YUV_FIX_EDGES) ? 1 : 0; l.sfmt = l.packed ? fmt : 0;
+  return l;
+}
+FlatLayer lgpu::flat_layer(const lgpu_yuv_source *s) { return make_layer(4, s->istrides, s->u_size, s->v_size, s->out_order, s->which_tables, s->pb_quality, s->flags); }
+FlatLayer lgpu::flat_layer(const lgpu_yuv422_source *s) { return make_layer(s->in_fmt, s->istrides, s->u_size, s->v_size, s->out_order, s->which_tables, s->pb_quality, 0); }
+FlatLayer lgpu::flat_layer(const lgpu_yuv_layer_source *s) {
+  return make_layer(s->in_fmt, s->istrides, s->u_size, s->v_size, s->out_order, s->which_tables, s->pb_quality, s->flags);
+}
+
+void lgpu::flat_tracks(FlatTrack *out, const lgpu_chain_yuv_mix_track *tracks, int ntracks, bool packed1) {
+  for (int i = 0; i < ntracks; i++) {
+    const lgpu_chain_yuv_mix_track &t = tracks[i];
+    out[i] = {t.y_d, packed1 ? nullptr : t.u_d, packed1 ? nullptr : t.v_d, nullptr, t.y2_d, t.u2_d, t.v2_d, {t.dst_d[0], t.dst_d[1], t.dst_d[2]}};
+  }
+}
+// from the sink forms' tracks (a packed layer 1's chroma pointers stay the caller's: a destination must not be one of them)
+static void flat_sink_tracks(FlatTrack *out, const lgpu_chain_yuv_sink_track *tracks, int ntracks) {
   for (int i = 0; i < ntracks; i++) {
     const lgpu_chain_yuv_sink_track &t = tracks[i];
-    const uint8_t *const planes[3] = {t.y_d, t.u_d, t.v_d};
-    if ((rc = check_track(fn, planes, packed ? 1 : 3, false, t.layer2_d, l2rgba, t.dst_d, nplanes, !sk))) return rc;
-    sb |= (uintptr_t)t.y_d;
-    if (mix) {
-      // a packed layer 2 is y2_d alone: its chroma pointers are not read, so they may be null and are no plane a destination could collide with
-      const uint8_t *const u2 = packed2 ? nullptr : mix[i].u2_d, *const v2 = packed2 ? nullptr : mix[i].v2_d;
-      FLAT_REQUIRE(mix[i].y2_d && (packed2 || (u2 && v2)), "null layer-2 plane");
-      for (int k = 0; k < nplanes; k++)
-        FLAT_REQUIRE((const uint8_t *)t.dst_d[k] != mix[i].y2_d && (const uint8_t *)t.dst_d[k] != u2 && (const uint8_t *)t.dst_d[k] != v2,
-                     "a destination plane is one of layer 2's planes");
-      sb2 |= (uintptr_t)mix[i].y2_d;
+    out[i] = {t.y_d, t.u_d, t.v_d, t.layer2_d, nullptr, nullptr, nullptr, {t.dst_d[0], t.dst_d[1], t.dst_d[2]}};
+  }
+}
+
+#define FLAT_REQUIRE(cond, msg) do { if (!(cond)) { set_error("%s: %s", fn, msg); return LGPU_E_BADARG; } } while (0)
+#define FLAT_REFUSE(msg) do { set_error("%s: %s", fn, msg); return LGPU_E_UNSUPPORTED; } while (0)
+int lgpu::flat_plan(const char *fn, bool select, const char *keep_size, const lgpu_chain_params *pr, const FlatLayer &l1, const FlatLayer *l2, const lgpu_canvas *cv,
+                    const lgpu_chain_sink *sk, const FlatTrack *tracks, int ntracks, const uint8_t *amounts, FlatPlan *plan) {
+  FlatPlan &p = *plan;
+  memset(&p, 0, sizeof p);
+  p.noblend = !select && (pr->interp & LGPU_INTERP_NOBLEND) != 0;
+  p.l2rgba = !select && !p.noblend && !l2;
+  FLAT_REQUIRE(pr->interp & LGPU_INTERP_PIXBUF, "the gdk-pixbuf arithmetic only (LGPU_INTERP_PIXBUF)");
+  if (!select) {
+    FLAT_REQUIRE(!l2 || !p.noblend, "LGPU_INTERP_NOBLEND leaves nothing to mix: lgpu_chain_flat_yuv420p[_to_yuv]");
+    FLAT_REQUIRE(amounts || p.noblend, "null amounts");
+  }
+  int rc;
+  if ((rc = check_yuv_source(fn, pr, &l1.ys, l1.fmt)) || (l2 && (rc = check_yuv_source(fn, pr, &l2->ys, l2->fmt)))) return rc;
+  p.chain_order = (l1.ys.out_order ^ (pr->swap_rb ? 1 : 0)) & 1;
+  FLAT_REQUIRE(!l2 || l2->ys.out_order == p.chain_order,
+               select ? "src2->out_order must state the byte order the select works in: src->out_order ^ params->swap_rb"
+                      : "src2->out_order must state the byte order the blend works in: src->out_order ^ params->swap_rb");
+  p.planar = sk && sk->out_fmt >= 4;
+  p.nplanes = p.planar ? 3 : 1; p.sink = p.planar ? 2 : sk ? 1 : 0;
+  p.fw = cv && !sk ? cv->nwidth : pr->dw; p.fh = cv && !sk ? cv->nheight : pr->dh;
+  if ((rc = sk ? check_yuv_sink(fn, pr, sk, p.chain_order, p.l2rgba) : check_rgba_dest(fn, pr, cv, p.l2rgba))) return rc;
+  const bool packed2 = l2 && l2->packed;
+  uintptr_t pb = 0, sb = 0, sb2 = 0;
+  for (int i = 0; i < ntracks; i++) {
+    const FlatTrack &t = tracks[i];
+    const uint8_t *const planes[3] = {t.y, t.u, t.v};
+    if ((rc = check_track(fn, planes, l1.packed ? 1 : 3, false, t.l2, p.l2rgba, t.dst, p.nplanes, !sk))) return rc;
+    if (l2) {
+      // a packed layer 2 is y2 alone: its chroma pointers are not read, so they may be null and are no plane a destination could collide with
+      const uint8_t *const u2 = packed2 ? nullptr : t.u2, *const v2 = packed2 ? nullptr : t.v2;
+      FLAT_REQUIRE(t.y2 && (packed2 || (u2 && v2)), "null layer-2 plane");
+      for (int k = 0; k < p.nplanes; k++)
+        FLAT_REQUIRE((const uint8_t *)t.dst[k] != t.y2 && (const uint8_t *)t.dst[k] != u2 && (const uint8_t *)t.dst[k] != v2, "a destination plane is one of layer 2's planes");
+      sb2 |= (uintptr_t)t.y2;
     }
-    pb |= (uintptr_t)t.dst_d[0];
+    sb |= (uintptr_t)t.y; pb |= (uintptr_t)t.dst[0];
   }
   // the one-launch form; anything else is refused, never run some other way
-  if (pr->sw != pr->dw || pr->sh != pr->dh)
-    FLAT_REFUSE(srcp ? "frames that keep their size only (sw == dw, sh == dh); convert with lgpu_yuv420p_to_rgb_batch (is_422) / lgpu_yuv_to_rgb_batch and run lgpu_chain_amounts"
-                : sk ? "frames that keep their size only (sw == dw, sh == dh); the exact 2:1 reduction is lgpu_chain_yuv420p_to_yuv"
-                   : "frames that keep their size only (sw == dw, sh == dh); the exact 2:1 reduction is lgpu_chain_yuv420p");
+  if (pr->sw != pr->dw || pr->sh != pr->dh) FLAT_REFUSE(keep_size);
   if (pr->do_blur) FLAT_REFUSE("the gaussian is not offered with a 4:2:0 or 4:2:2 source");
   // K3 reads a macropixel as one aligned dword; the reference divides that rowstride by 4 (docs/QUIRKS.md, K3-c): there is no behaviour to follow elsewhere
-  if (packed && !multiple_of(sb | (uintptr_t)lys, 4)) FLAT_REFUSE("a UYVY / YUYV source is read as 4-byte macropixels (plane and rowstride % 4 == 0)");
-  if (packed2 && !multiple_of(sb2 | (uintptr_t)ys2->istrides[0], 4)) FLAT_REFUSE("a UYVY / YUYV layer 2 is read as 4-byte macropixels (plane and rowstride % 4 == 0)");
+  if (l1.packed && !multiple_of(sb | (uintptr_t)l1.ys.istrides[0], 4)) FLAT_REFUSE("a UYVY / YUYV source is read as 4-byte macropixels (plane and rowstride % 4 == 0)");
+  if (packed2 && !multiple_of(sb2 | (uintptr_t)l2->ys.istrides[0], 4)) FLAT_REFUSE("a UYVY / YUYV layer 2 is read as 4-byte macropixels (plane and rowstride % 4 == 0)");
   if (sk) {
-    if (sk->out_fmt == 5) FLAT_REFUSE("YUV422P is not served (lgpu_chain_flat_yuv420p + lgpu_rgb_to_yuv_batch)");
-    if (planar && (pr->dh & 1)) FLAT_REFUSE("the 4:2:0 sink needs an even height");
+    if (sk->out_fmt == 5)
+      FLAT_REFUSE(select ? "YUV422P is not served (the RGBA form + lgpu_rgb_to_yuv_batch)" : "YUV422P is not served (lgpu_chain_flat_yuv420p + lgpu_rgb_to_yuv_batch)");
+    if (p.planar && (pr->dh & 1)) FLAT_REFUSE("the 4:2:0 sink needs an even height");
     // a lane stores one macropixel (4 bytes) or one luma pair (2 bytes) per row; chroma samples are single bytes
-    if (!multiple_of(pb | (uintptr_t)sk->orow[0], planar ? 2 : 4))
+    if (!multiple_of(pb | (uintptr_t)sk->orow[0], p.planar ? 2 : 4))
       FLAT_REFUSE("packed sinks are stored as 4-byte macropixels (plane and rowstride % 4 == 0), the 4:2:0 luma plane as 2-byte pairs (plane and rowstride % 2 == 0)");
   }
-  const int drow = sk ? sk->orow[0] : pr->orow;
-  if ((rc = check_plane_sizes(fn, {(long long)pr->sh * lys, usz, vsz, (long long)ch * drow, l2rgba ? (long long)ch * pr->irow2 : 0,
-                                   ys2 ? (long long)pr->sh * ys2->istrides[0] : 0, ys2 ? ys2->u_size : 0, ys2 ? ys2->v_size : 0,
-                                   planar ? (long long)(pr->dh >> 1) * sk->orow[1] : 0, planar ? (long long)(pr->dh >> 1) * sk->orow[2] : 0}))) return rc;
+  p.drow = sk ? sk->orow[0] : pr->orow; p.irow2 = p.l2rgba ? pr->irow2 : 0;
+  p.urow = p.planar ? sk->orow[1] : 0; p.vrow = p.planar ? sk->orow[2] : 0;
+  if ((rc = check_plane_sizes(fn, {(long long)pr->sh * l1.ys.istrides[0], l1.ys.u_size, l1.ys.v_size, (long long)p.fh * p.drow, (long long)p.fh * p.irow2,
+                                   l2 ? (long long)pr->sh * l2->ys.istrides[0] : 0, l2 ? l2->ys.u_size : 0, l2 ? l2->ys.v_size : 0,
+                                   (long long)(pr->dh >> 1) * p.urow, (long long)(pr->dh >> 1) * p.vrow}))) return rc;
+  if (p.planar && (rc = cavg_forms_checked())) return rc;
+  if (sk && (rc = get_sink_tables(sk->which_tables, sk->in_order, &p.stab))) return rc;
+  p.w = pr->sw; p.h = pr->sh;
+  if (cv) { p.cw = cv->nwidth; p.ch = cv->nheight; p.ox = cv->offs_x; p.oy = cv->offs_y; }
+  p.fmt = sk ? sk->out_fmt : 0; p.unclamped = sk ? (sk->which_tables & 1) : 0; p.use_lut = pr->use_lut ? 1 : 0;
+  p.lut = pack_lut(pr->use_lut ? pr->lut8 : nullptr);
+  p.hw = pr->sw >> 1; p.nunits = pr->sh / 2 + 1;
+  p.gx = cdiv((unsigned)p.hw, 256u);
+  p.bar_px = cv ? (long long)p.fw * p.fh - (long long)pr->sw * pr->sh : 0;
+  return LGPU_OK;
+}
+#undef FLAT_REQUIRE
+#undef FLAT_REFUSE
+
+FlatShape lgpu::flat_launch_shape(const FlatPlan &p, int n) {
+  FlatShape s;
+  const int cap = std::max(1, (int)(kFlatWgTarget / ((long long)p.gx * n)));
+  int gy = std::min(p.nunits, cap);
+  s.per = (p.nunits + gy - 1) / gy;
+  s.gy_units = (p.nunits + s.per - 1) / s.per;
+  const unsigned bar_gy = p.bar_px > 0 ? (unsigned)std::min<long long>(64, (p.bar_px + 1024ll * p.gx - 1) / (1024ll * p.gx)) : 0u;
+  s.grid = dim3(p.gx, (unsigned)s.gy_units + bar_gy, (unsigned)n);
+  return s;
+}
+
+// ---- k_flat_yuv420's arguments from the plan: one function per struct ----
+static FlatArgs flat_args(const FlatPlan &p, const FlatLayer &l1) {
   FlatArgs a;
   memset(&a, 0, sizeof a);
-  if (planar && (rc = cavg_forms_checked())) return rc;
-  if (sk && (rc = get_sink_tables(sk->which_tables, sk->in_order, &a.stab))) return rc;
-  a.tables = device_tables()->yuv2rgb[ys->which_tables & 3];
-  a.usize = (uint32_t)usz; a.vsize = (uint32_t)vsz; a.ys = lys; a.us = us; a.vs = vs; a.w = pr->sw; a.h = pr->sh;
-  a.orow = drow; a.irow2 = l2rgba ? pr->irow2 : 0;
-  a.urow = planar ? sk->orow[1] : 0; a.vrow = planar ? sk->orow[2] : 0;
-  if (cv) { a.cw = cv->nwidth; a.ch = cv->nheight; a.ox = cv->offs_x; a.oy = cv->offs_y; }
-  a.clamped = !packed && !(ys->which_tables & 1);      // K3 indexes its tables with the sample itself
-  a.sfmt = packed ? sfmt : 0;
-  a.lowq = ys->pb_quality == 1; a.fix_edges = (ys->flags & LGPU_YUV_FIX_EDGES) ? 1 : 0; a.use_lut = pr->use_lut ? 1 : 0;
-  a.fmt = sk ? sk->out_fmt : 0; a.unclamped = sk ? (sk->which_tables & 1) : 0;
-  const Lut8 l = pack_lut(pr->use_lut ? pr->lut8 : nullptr);
-  const int nunits = pr->sh / 2 + 1;
-  const unsigned gx = cdiv((unsigned)hw, 256u);
-  const long long bar_px = cv ? (long long)cw * ch - (long long)pr->sw * pr->sh : 0;
-  const int per_launch = ys2 ? LGPU_CHAIN_MIX_TRACKS : planar ? kFlatPlanarTracks : LGPU_CHAIN_MAX_TRACKS;
+  flat_fill_layer(a, l1);
+  flat_fill_frame(a, p);
+  a.irow2 = p.irow2;
+  return a;
+}
+template <int NT, int NDST>
+static void flat_fill_tracks(FlatTracksT<NT, NDST> &T, const FlatPlan &p, const FlatLayer &, const FlatLayer *, const FlatTrack *tr, const uint8_t *amounts, int n) {
+  for (int i = 0; i < n; i++) {
+    T.y[i] = tr[i].y; T.u[i] = tr[i].u; T.v[i] = tr[i].v; T.l2[i] = p.noblend ? nullptr : tr[i].l2; T.bf[i] = amounts ? amounts[i] : 0;
+    for (int k = 0; k < p.nplanes; k++) T.dst[k][i] = tr[i].dst[k];
+  }
+}
+template <int NT, int NDST>
+static void flat_fill_tracks(FlatMixTracksT<NT, NDST> &T, const FlatPlan &p, const FlatLayer &l1, const FlatLayer *l2, const FlatTrack *tr, const uint8_t *amounts, int n) {
+  for (int i = 0; i < n; i++) {
+    T.y[i] = tr[i].y; T.u[i] = tr[i].u; T.v[i] = tr[i].v; T.y2[i] = tr[i].y2; T.u2[i] = tr[i].u2; T.v2[i] = tr[i].v2; T.bf[i] = amounts[i];
+    for (int k = 0; k < p.nplanes; k++) T.dst[k][i] = tr[i].dst[k];
+  }
+  T.tables2 = flat_tables_shared(l1, *l2) ? nullptr : l2->tables;
+  T.usize2 = (uint32_t)l2->ys.u_size; T.vsize2 = (uint32_t)l2->ys.v_size; T.ys2 = l2->ys.istrides[0]; T.us2 = l2->ys.istrides[1]; T.vs2 = l2->ys.istrides[2];
+  T.clamped2 = l2->clamped; T.lowq2 = l2->lowq; T.fix_edges2 = l2->fix_edges;
+}
+template <int NT, int NDST>
+static void flat_fill_tracks(FlatMixTracksPackedT<NT, NDST> &T, const FlatPlan &p, const FlatLayer &l1, const FlatLayer *l2, const FlatTrack *tr, const uint8_t *amounts, int n) {
+  flat_fill_tracks(static_cast<FlatMixTracksT<NT, NDST> &>(T), p, l1, l2, tr, amounts, n);
+  T.sfmt2 = l2->sfmt;
+}
+
+// the six entry points of this file behind their own null checks: the plan, then one launch per 64 tracks (32 with a decoded layer 2 or the 4:2:0 sink).  l2: the mix forms'
+// decoded layer 2 (both layers are letterboxed onto cv then), null otherwise
+static int flat_run(const char *fn, const lgpu_chain_params *pr, const FlatLayer &l1, const FlatLayer *l2, const lgpu_canvas *cv, const lgpu_chain_sink *sk,
+                    const FlatTrack *tr, int ntracks, const uint8_t *amounts, void *stream) {
+  FlatPlan p;
+  const int rc = flat_plan(fn, false,
+                           l1.policy ? "frames that keep their size only (sw == dw, sh == dh); convert with lgpu_yuv420p_to_rgb_batch (is_422) / lgpu_yuv_to_rgb_batch and run lgpu_chain_amounts"
+                           : sk ? "frames that keep their size only (sw == dw, sh == dh); the exact 2:1 reduction is lgpu_chain_yuv420p_to_yuv"
+                                : "frames that keep their size only (sw == dw, sh == dh); the exact 2:1 reduction is lgpu_chain_yuv420p",
+                           pr, l1, l2, cv, sk, tr, ntracks, amounts, &p);
+  if (rc) return rc;
+  FlatArgs a = flat_args(p, l1);
+  const int per_launch = l2 ? LGPU_CHAIN_MIX_TRACKS : p.planar ? kFlatPlanarTracks : LGPU_CHAIN_MAX_TRACKS;
+  const int blend = l2 ? 2 + l2->policy : p.noblend ? 0 : 1;      // 0 none, 1 with an RGBA layer 2, 2.. with a decoded one: L2YUV + 1
   hipStream_t st = (hipStream_t)stream;
-#define FLAT_LAUNCH_SRC(SK, SR) do {                                                                                                                     \
-    if (noblend) { if (chain_order) hipLaunchKernelGGL((k_flat_yuv420<0, 1, SK, 0, SR>), grid, dim3(256), 0, st, a, T, l); else hipLaunchKernelGGL((k_flat_yuv420<0, 0, SK, 0, SR>), grid, dim3(256), 0, st, a, T, l); } \
-    else { if (chain_order) hipLaunchKernelGGL((k_flat_yuv420<1, 1, SK, 0, SR>), grid, dim3(256), 0, st, a, T, l); else hipLaunchKernelGGL((k_flat_yuv420<1, 0, SK, 0, SR>), grid, dim3(256), 0, st, a, T, l); }     \
-  } while (0)
-#define FLAT_LAUNCH(SK) do { if (srcp == 2) FLAT_LAUNCH_SRC(SK, 2); else if (srcp == 1) FLAT_LAUNCH_SRC(SK, 1); else FLAT_LAUNCH_SRC(SK, 0); } while (0)
   for (int t0 = 0; t0 < ntracks; t0 += per_launch) {
     const int n = std::min(per_launch, ntracks - t0);
-    // about kFlatWgTarget workgroups per launch, each walking a run of consecutive units on one staging of the tables
-    const int cap = std::max(1, (int)(kFlatWgTarget / ((long long)gx * n)));
-    int gy = std::min(nunits, cap);
-    a.per = (nunits + gy - 1) / gy;
-    gy = (nunits + a.per - 1) / a.per;
-    a.gy_units = gy;
-    const unsigned bar_gy = bar_px > 0 ? (unsigned)std::min<long long>(64, (bar_px + 1024ll * gx - 1) / (1024ll * gx)) : 0u;
-    const dim3 grid(gx, (unsigned)gy + bar_gy, (unsigned)n);
-    if (ys2) {
-      // L2YUV: one staged copy of the K2 tables serves both layers when they index the same set the same way.  A planar layer with clamped tables indexes rg / gb
-      // through the 16..240 clamp that staging folds into the index, a packed layer with the sample itself: UYVY over YUV420P, both with which_tables 0, needs two copies
-      const int clamped2 = !packed2 && !(ys2->which_tables & 1);
-      const bool own = (ys2->which_tables & 3) != (ys->which_tables & 3) || clamped2 != a.clamped;
-      auto fill = [&](auto &T) {
-        for (int i = 0; i < n; i++) {
-          const lgpu_chain_yuv_mix_track &t = mix[t0 + i];
-          T.y[i] = t.y_d; T.u[i] = t.u_d; T.v[i] = t.v_d; T.y2[i] = t.y2_d; T.u2[i] = t.u2_d; T.v2[i] = t.v2_d; T.bf[i] = amounts[t0 + i];
-          for (int k = 0; k < nplanes; k++) T.dst[k][i] = t.dst_d[k];
-        }
-        T.tables2 = own ? device_tables()->yuv2rgb[ys2->which_tables & 3] : nullptr;
-        T.usize2 = (uint32_t)ys2->u_size; T.vsize2 = (uint32_t)ys2->v_size; T.ys2 = ys2->istrides[0]; T.us2 = ys2->istrides[1]; T.vs2 = ys2->istrides[2];
-        T.clamped2 = clamped2; T.lowq2 = ys2->pb_quality == 1; T.fix_edges2 = (ys2->flags & LGPU_YUV_FIX_EDGES) ? 1 : 0;
-      };
-      // THE dispatch point of the mix forms: 3 sinks x SRC x L2YUV x SWAP, the six of lgpu_chain_flat_yuv420p_mix (SRC 0, L2YUV 1) among them
-#define FLAT_MIX_LAUNCH_L2(SK, SR, L2) do {                                                                                                  \
-        FlatTr<SK, L2>::type T;                                                                                                              \
-        memset(&T, 0, sizeof T);                                                                                                             \
-        fill(T);                                                                                                                             \
-        set_sfmt2(T, sfmt2);                                                                                                                 \
-        if (chain_order) hipLaunchKernelGGL((k_flat_yuv420<1, 1, SK, L2, SR>), grid, dim3(256), 0, st, a, T, l);                            \
-        else hipLaunchKernelGGL((k_flat_yuv420<1, 0, SK, L2, SR>), grid, dim3(256), 0, st, a, T, l);                                        \
-      } while (0)
-#define FLAT_MIX_LAUNCH_SRC(SK, SR) do {                                                                                                     \
-        if (l2p == 3) FLAT_MIX_LAUNCH_L2(SK, SR, 3); else if (l2p == 2) FLAT_MIX_LAUNCH_L2(SK, SR, 2); else FLAT_MIX_LAUNCH_L2(SK, SR, 1);   \
-      } while (0)
-#define FLAT_MIX_LAUNCH(SK) do { if (srcp == 2) FLAT_MIX_LAUNCH_SRC(SK, 2); else if (srcp == 1) FLAT_MIX_LAUNCH_SRC(SK, 1); else FLAT_MIX_LAUNCH_SRC(SK, 0); } while (0)
-      if (planar) FLAT_MIX_LAUNCH(2); else if (sk) FLAT_MIX_LAUNCH(1); else FLAT_MIX_LAUNCH(0);
-#undef FLAT_MIX_LAUNCH
-#undef FLAT_MIX_LAUNCH_SRC
-#undef FLAT_MIX_LAUNCH_L2
-    } else if (planar) {
-      FlatTr<2>::type T;
-      for (int i = 0; i < n; i++) {
-        const lgpu_chain_yuv_sink_track &t = tracks[t0 + i];
-        T.y[i] = t.y_d; T.u[i] = t.u_d; T.v[i] = t.v_d; T.l2[i] = noblend ? nullptr : t.layer2_d; T.bf[i] = amounts ? amounts[t0 + i] : 0;
-        for (int k = 0; k < 3; k++) T.dst[k][i] = t.dst_d[k];
-      }
-      FLAT_LAUNCH(2);
-    } else {
-      FlatTr<0>::type T;
-      for (int i = 0; i < n; i++) {
-        const lgpu_chain_yuv_sink_track &t = tracks[t0 + i];
-        T.y[i] = t.y_d; T.u[i] = t.u_d; T.v[i] = t.v_d; T.l2[i] = noblend ? nullptr : t.layer2_d; T.bf[i] = amounts ? amounts[t0 + i] : 0;
-        T.dst[0][i] = t.dst_d[0];
-      }
-      if (sk) FLAT_LAUNCH(1); else FLAT_LAUNCH(0);
-    }
+    const FlatShape s = flat_launch_shape(p, n);
+    a.per = s.per; a.gy_units = s.gy_units;
+    // THE dispatch point: 3 sinks x SRC x {no blend, RGBA layer 2, L2YUV 1..3} x SWAP, the six of lgpu_chain_flat_yuv420p_mix (SRC 0, L2YUV 1) among them
+    with_constant<3>(p.sink, [&](auto sink) { with_constant<3>(l1.policy, [&](auto src) { with_constant<5>(blend, [&](auto bl) { with_constant<2>(p.chain_order, [&](auto swap) {
+      constexpr int SK = decltype(sink)::value, SR = decltype(src)::value, BL = decltype(bl)::value, L2 = BL > 1 ? BL - 1 : 0, SW = decltype(swap)::value;
+      typename FlatTr<SK, L2>::type T;
+      memset(&T, 0, sizeof T);
+      flat_fill_tracks(T, p, l1, l2, tr + t0, amounts ? amounts + t0 : nullptr, n);
+      hipLaunchKernelGGL((k_flat_yuv420<(BL > 0 ? 1 : 0), SW, SK, L2, SR>), s.grid, dim3(256), 0, st, a, T, p.lut);
+    }); }); }); });
     LGPU_CHECK_LAUNCH();
   }
   return LGPU_OK;
-#undef FLAT_LAUNCH
-#undef FLAT_LAUNCH_SRC
-#undef FLAT_REQUIRE
-#undef FLAT_REFUSE
 }
 
 // lgpu_chain_flat_yuv420p: lgpu_yuv420p_to_rgb (opsize 4, src->out_order, no LUT) + lgpu_chain_amounts with sw == dw, sh == dh, as ONE launch (the canvas's bars
@@ -392,12 +405,9 @@ extern "C" int lgpu_chain_flat_yuv420p(const lgpu_chain_params *pr, const lgpu_y
   int rc = ensure_init();
   if (rc) return rc;
   LGPU_REQUIRE(pr && ys && tracks && ntracks > 0 && ntracks <= LGPU_CHAIN_MAX_TRACKS, "params, source and 1..64 tracks required");
-  lgpu_chain_yuv_sink_track tr[LGPU_CHAIN_MAX_TRACKS];
-  for (int i = 0; i < ntracks; i++) {
-    tr[i].y_d = tracks[i].y_d; tr[i].u_d = tracks[i].u_d; tr[i].v_d = tracks[i].v_d; tr[i].layer2_d = tracks[i].layer2_d;
-    tr[i].dst_d[0] = tracks[i].dst_d; tr[i].dst_d[1] = tr[i].dst_d[2] = nullptr;
-  }
-  return flat_impl("lgpu_chain_flat_yuv420p", pr, ys, cv, nullptr, tr, ntracks, amounts, stream);
+  FlatTrack tr[LGPU_CHAIN_MAX_TRACKS];
+  for (int i = 0; i < ntracks; i++) tr[i] = {tracks[i].y_d, tracks[i].u_d, tracks[i].v_d, tracks[i].layer2_d, nullptr, nullptr, nullptr, {tracks[i].dst_d, nullptr, nullptr}};
+  return flat_run("lgpu_chain_flat_yuv420p", pr, flat_layer(ys), nullptr, cv, nullptr, tr, ntracks, amounts, stream);
 }
 
 // lgpu_chain_flat_yuv420p_to_yuv: the same without a canvas, ending in lgpu_rgb_to_yuv(.., sink->in_order, 1, .., sink->out_fmt, 0, sink->which_tables); neither RGBA
@@ -407,7 +417,9 @@ extern "C" int lgpu_chain_flat_yuv420p_to_yuv(const lgpu_chain_params *pr, const
   int rc = ensure_init();
   if (rc) return rc;
   LGPU_REQUIRE(pr && ys && sk && tracks && ntracks > 0 && ntracks <= LGPU_CHAIN_MAX_TRACKS, "params, source, sink and 1..64 tracks required");
-  return flat_impl("lgpu_chain_flat_yuv420p_to_yuv", pr, ys, nullptr, sk, tracks, ntracks, amounts, stream);
+  FlatTrack tr[LGPU_CHAIN_MAX_TRACKS];
+  flat_sink_tracks(tr, tracks, ntracks);
+  return flat_run("lgpu_chain_flat_yuv420p_to_yuv", pr, flat_layer(ys), nullptr, nullptr, sk, tr, ntracks, amounts, stream);
 }
 
 // lgpu_chain_flat_yuv420p_mix: lgpu_yuv420p_to_rgb on each track's layer-2 planes (opsize 4, src2's settings, no LUT) + lgpu_chain_flat_yuv420p[_to_yuv] with that
@@ -417,12 +429,10 @@ extern "C" int lgpu_chain_flat_yuv420p_mix(const lgpu_chain_params *pr, const lg
   int rc = ensure_init();
   if (rc) return rc;
   LGPU_REQUIRE(pr && ys && ys2 && tracks && ntracks > 0 && ntracks <= LGPU_CHAIN_MAX_TRACKS, "params, both sources and 1..64 tracks required");
-  lgpu_chain_yuv_sink_track tr[LGPU_CHAIN_MAX_TRACKS];
-  for (int i = 0; i < ntracks; i++) {
-    tr[i].y_d = tracks[i].y_d; tr[i].u_d = tracks[i].u_d; tr[i].v_d = tracks[i].v_d; tr[i].layer2_d = nullptr;
-    for (int k = 0; k < 3; k++) tr[i].dst_d[k] = tracks[i].dst_d[k];
-  }
-  return flat_impl("lgpu_chain_flat_yuv420p_mix", pr, ys, nullptr, sk, tr, ntracks, amounts, stream, ys2, tracks);
+  FlatTrack tr[LGPU_CHAIN_MAX_TRACKS];
+  flat_tracks(tr, tracks, ntracks, false);
+  const FlatLayer l2 = flat_layer(ys2);
+  return flat_run("lgpu_chain_flat_yuv420p_mix", pr, flat_layer(ys), &l2, nullptr, sk, tr, ntracks, amounts, stream);
 }
 
 // lgpu_chain_flat_yuv422: lgpu_yuv420p_to_rgb (is_422) or lgpu_yuv_to_rgb (UYVY / YUYV) + lgpu_chain_amounts with sw == dw, sh == dh [+ lgpu_rgb_to_yuv] as ONE launch
@@ -434,13 +444,9 @@ extern "C" int lgpu_chain_flat_yuv422(const lgpu_chain_params *pr, const lgpu_yu
   LGPU_REQUIRE(pr && s4 && tracks && ntracks > 0 && ntracks <= LGPU_CHAIN_MAX_TRACKS, "params, source and 1..64 tracks required");
   LGPU_REQUIRE(s4->in_fmt == 2 || s4->in_fmt == 3 || s4->in_fmt == 5, "in_fmt must be 2 (UYVY), 3 (YUYV) or 5 (YUV422P); YUV420P: lgpu_chain_flat_yuv420p[_to_yuv]");
   LGPU_REQUIRE(!(cv && sk), "a canvas and a sink together: chroma rows would straddle the bar / frame edge");
-  lgpu_yuv_source ys;
-  memset(&ys, 0, sizeof ys);
-  const bool packed = s4->in_fmt != 5;
-  ys.istrides[0] = s4->istrides[0]; ys.istrides[1] = packed ? 0 : s4->istrides[1]; ys.istrides[2] = packed ? 0 : s4->istrides[2];
-  ys.u_size = packed ? 0 : s4->u_size; ys.v_size = packed ? 0 : s4->v_size;
-  ys.out_order = s4->out_order; ys.which_tables = s4->which_tables; ys.pb_quality = s4->pb_quality;
-  return flat_impl("lgpu_chain_flat_yuv422", pr, &ys, cv, sk, tracks, ntracks, amounts, stream, nullptr, nullptr, s4->in_fmt);
+  FlatTrack tr[LGPU_CHAIN_MAX_TRACKS];
+  flat_sink_tracks(tr, tracks, ntracks);
+  return flat_run("lgpu_chain_flat_yuv422", pr, flat_layer(s4), nullptr, cv, sk, tr, ntracks, amounts, stream);
 }
 
 // lgpu_chain_flat_yuv_mix: each track's layer 2 converted by the single-frame call of ITS format (lgpu_yuv420p_to_rgb with is_422 0 / 1, lgpu_yuv_to_rgb) into a tight
@@ -455,24 +461,10 @@ static int flat_mix(const char *fn, const lgpu_chain_params *pr, const lgpu_yuv_
   MIX_REQUIRE(pr && s1 && s2 && tracks && ntracks > 0 && ntracks <= LGPU_CHAIN_MAX_TRACKS, "params, both sources and 1..64 tracks required");
   MIX_REQUIRE(s1->in_fmt >= 2 && s1->in_fmt <= 5 && s2->in_fmt >= 2 && s2->in_fmt <= 5, "in_fmt must be 2 (UYVY), 3 (YUYV), 4 (YUV420P) or 5 (YUV422P) on either layer");
 #undef MIX_REQUIRE
-  // one layer's description as flat_impl reads it; what a packed layer does not have is zero
-  auto source_of = [](const lgpu_yuv_layer_source *s) {
-    lgpu_yuv_source ys;
-    memset(&ys, 0, sizeof ys);
-    const bool packed = s->in_fmt < 4;
-    ys.istrides[0] = s->istrides[0]; ys.istrides[1] = packed ? 0 : s->istrides[1]; ys.istrides[2] = packed ? 0 : s->istrides[2];
-    ys.u_size = packed ? 0 : s->u_size; ys.v_size = packed ? 0 : s->v_size;
-    ys.out_order = s->out_order; ys.which_tables = s->which_tables; ys.pb_quality = s->pb_quality; ys.flags = s->flags;
-    return ys;
-  };
-  const lgpu_yuv_source ys = source_of(s1), ys2 = source_of(s2);
-  const bool packed1 = s1->in_fmt < 4;
-  lgpu_chain_yuv_sink_track tr[LGPU_CHAIN_MAX_TRACKS];
-  for (int i = 0; i < ntracks; i++) {
-    tr[i].y_d = tracks[i].y_d; tr[i].u_d = packed1 ? nullptr : tracks[i].u_d; tr[i].v_d = packed1 ? nullptr : tracks[i].v_d; tr[i].layer2_d = nullptr;
-    for (int k = 0; k < 3; k++) tr[i].dst_d[k] = tracks[i].dst_d[k];
-  }
-  return flat_impl(fn, pr, &ys, cv, sk, tr, ntracks, amounts, stream, &ys2, tracks, s1->in_fmt, s2->in_fmt);
+  const FlatLayer l1 = flat_layer(s1), l2 = flat_layer(s2);
+  FlatTrack tr[LGPU_CHAIN_MAX_TRACKS];
+  flat_tracks(tr, tracks, ntracks, l1.packed);
+  return flat_run(fn, pr, l1, &l2, cv, sk, tr, ntracks, amounts, stream);
 }
 extern "C" int lgpu_chain_flat_yuv_mix(const lgpu_chain_params *pr, const lgpu_yuv_layer_source *s1, const lgpu_yuv_layer_source *s2, const lgpu_chain_sink *sk,
                                        const lgpu_chain_yuv_mix_track *tracks, int ntracks, const uint8_t *amounts, void *stream) {

@@ -9,6 +9,8 @@
 // pixel, layer 1's only if some lane shows a layer-1 pixel.  A wave wholly inside or wholly outside the figure issues no load of the hidden layer's planes and none
 // of its table gathers; at amount 0 or 1 no wave of the launch does.  Waves on the outline, and every wave of a dissolve strictly between 0 and 1, convert both and
 // select per pixel.  The finished pixel takes flat.hip's path: LUT, store or K4; the 4:2:0 sink's chroma comes from whichever layers' pixels the row pair shows.
+// Table staging and the bar pixels' decode are flat_walk.h's too; the host side -- layer description, track record, refusal sequence, launch shape, dispatch -- is
+// flat_plan.h's, behind the select's own checks (kind, amounts, masks).
 //
 // The figure is the CANVAS's where there is one: the predicate takes (x + offs_x, y + offs_y) in an nwidth x nheight frame of 4-byte pixels, the dissolve mask is
 // nwidth * nheight floats, and the bars are select(black, black) = opaque black [-> LUT], written by the same launch with nothing read for them.
@@ -19,13 +21,11 @@
 #include "../../include/lives_gpu_select.h"
 #include "k2_walk.h"
 #include "flat_walk.h"
+#include "flat_plan.h"      // the host side every unscaled form shares: layer description, track record, refusal sequence, launch shape, dispatch
 #include "select_pred.h"
 #include <algorithm>
 #include <cmath>
 #include <string.h>
-
-namespace lgpu { int cavg_forms_checked(); }      // palette.hip
-int get_sink_tables(int which_tables, int in_order, const uint2 **out);      // pixbuf.hip
 
 namespace lgpu {
 
@@ -80,27 +80,17 @@ __global__ __launch_bounds__(256) void k_flat_select(const SelArgs A, const SelT
       uint32_t c = 0xFF000000u;
       if (A.use_lut) c = lut3_rgba(s_lut, c);
       for (long p = (long)bb * 256 + tid; p < total; p += (long)nbb * 256) {
-        int q = (int)p, x, y;
-        if (q < top) { y = q / A.cw; x = q - y * A.cw; }
-        else if (q < top + bottom) { q -= top; y = q / A.cw; x = q - y * A.cw; y += A.oy + A.h; }
-        else { q -= top + bottom; y = q / sw_; x = q - y * sw_; y += A.oy; if (x >= A.ox) x += A.w; }
+        int x, y;
+        flat_bar_xy((int)p, top, bottom, sw_, A.cw, A.ox, A.oy, A.w, A.h, x, y);
         reinterpret_cast<uint32_t *>(T.dst[0][z] + (size_t)y * A.orow)[x] = c;
       }
       return;
     }
   }
   {
-    // K2's tables, paired, as k_flat_yuv420 stages them: the entry of an UNCLAMPED chroma value e is tables[clamp(e)].  Layer 2's own copy when its table set or its
-    // index clamp differs (a packed layer indexes with the sample itself)
-    auto stage = [&](int s, const SelLayer &L) {
-      const int clo = L.clamped ? 16 : 0, chi = L.clamped ? 240 : 255;
-      const int ec = tid < clo ? clo : tid > chi ? chi : tid;
-      s_ty[s][tid] = (uint32_t)L.tables[tid];
-      s_rg[s][tid] = make_uint2((uint32_t)L.tables[256 + ec], (uint32_t)L.tables[768 + ec]);
-      s_gb[s][tid] = make_uint2((uint32_t)L.tables[512 + ec], (uint32_t)L.tables[1024 + ec]);
-    };
-    stage(0, A.l1);
-    if (A.l2.tables) stage(1, A.l2);
+    // K2's tables, paired (flat_walk.h).  Layer 2's own copy when its table set or its index clamp differs (a packed layer indexes with the sample itself)
+    flat_stage_k2(tid, A.l1.tables, A.l1.clamped, s_ty[0], s_rg[0], s_gb[0]);
+    if (A.l2.tables) flat_stage_k2(tid, A.l2.tables, A.l2.clamped, s_ty[1], s_rg[1], s_gb[1]);
     if constexpr (SINK != 0) {
 #pragma unroll
       for (int i = 0; i < 6; i++) s_sink.t[tid + 256 * i] = A.stab[tid + 256 * i];
@@ -193,142 +183,70 @@ __global__ __launch_bounds__(256) void k_flat_select(const SelArgs A, const SelT
 
 using namespace lgpu;
 
-// lgpu_chain_flat_yuv_select (include/lives_gpu_select.h): the checks are the mix form's -- check_yuv_source, check_yuv_sink, check_rgba_dest, check_track,
-// check_plane_sizes (lgpu_common.h), its alignment rules and its order: LGPU_E_BADARG before LGPU_E_UNSUPPORTED, everything before anything is allocated or enqueued
-extern "C" int lgpu_chain_flat_yuv_select(const lgpu_chain_params *pr, const lgpu_yuv_layer_source *s1, const lgpu_yuv_layer_source *s2, const lgpu_select *sel,
-                                          const lgpu_canvas *cv, const lgpu_chain_sink *sk, const lgpu_chain_yuv_mix_track *tracks, int ntracks, void *stream) {
-  static const char fn[] = "lgpu_chain_flat_yuv_select";
-  int rc = ensure_init();
-  if (rc) return rc;
-#define SEL_REQUIRE(cond, msg) do { if (!(cond)) { set_error("%s: %s", fn, msg); return LGPU_E_BADARG; } } while (0)
-#define SEL_REFUSE(msg) do { set_error("%s: %s", fn, msg); return LGPU_E_UNSUPPORTED; } while (0)
-  SEL_REQUIRE(pr && s1 && s2 && sel && tracks && ntracks > 0 && ntracks <= LGPU_CHAIN_MAX_TRACKS, "params, both sources, the select and 1..64 tracks required");
-  SEL_REQUIRE(s1->in_fmt >= 2 && s1->in_fmt <= 5 && s2->in_fmt >= 2 && s2->in_fmt <= 5, "in_fmt must be 2 (UYVY), 3 (YUYV), 4 (YUV420P) or 5 (YUV422P) on either layer");
-  SEL_REQUIRE(!(cv && sk), "a canvas and a sink together: chroma rows would straddle the bar / frame edge");
-  SEL_REQUIRE(pr->interp & LGPU_INTERP_PIXBUF, "the gdk-pixbuf arithmetic only (LGPU_INTERP_PIXBUF)");
-  const int kind = sel->kind;
-  SEL_REQUIRE(kind == LGPU_SELECT_IRIS_RECT || kind == LGPU_SELECT_IRIS_CIRCLE || kind == LGPU_SELECT_DISSOLVE,
-              "kind must be 0 (iris rectangle), 1 (iris circle) or 3 (dissolve); the other transitions show layer 1 at a shifted position or need both layers");
-  SEL_REQUIRE(sel->amounts, "null amounts");
-  for (int i = 0; i < ntracks; i++) SEL_REQUIRE(std::isfinite(sel->amounts[i]) && sel->amounts[i] >= 0. && sel->amounts[i] <= 1., "a transition amount is a finite number in 0..1");
-  if (kind == LGPU_SELECT_DISSOLVE) {
-    SEL_REQUIRE(sel->mask_d, "dissolve needs the table of mask pointers");
-    for (int i = 0; i < ntracks; i++) {
-      SEL_REQUIRE(sel->mask_d[i], "null dissolve mask");
-      SEL_REQUIRE(multiple_of((uintptr_t)sel->mask_d[i], 4), "a dissolve mask is read as floats (address % 4 == 0)");
-    }
-  }
-  // one layer's description as the shared checks read it; what a packed layer does not have is zero
-  auto source_of = [](const lgpu_yuv_layer_source *s) {
-    lgpu_yuv_source ys;
-    memset(&ys, 0, sizeof ys);
-    const bool packed = s->in_fmt < 4;
-    ys.istrides[0] = s->istrides[0]; ys.istrides[1] = packed ? 0 : s->istrides[1]; ys.istrides[2] = packed ? 0 : s->istrides[2];
-    ys.u_size = packed ? 0 : s->u_size; ys.v_size = packed ? 0 : s->v_size;
-    ys.out_order = s->out_order; ys.which_tables = s->which_tables; ys.pb_quality = s->pb_quality; ys.flags = s->flags;
-    return ys;
-  };
-  const lgpu_yuv_source ys = source_of(s1), ys2 = source_of(s2);
-  const bool packed1 = s1->in_fmt < 4, packed2 = s2->in_fmt < 4;
-  const int srcp = packed1 ? 2 : s1->in_fmt == 5 ? 1 : 0, srcp2 = packed2 ? 2 : s2->in_fmt == 5 ? 1 : 0;      // the kernel's SRC / SRC2 policies
-  if ((rc = check_yuv_source(fn, pr, &ys, s1->in_fmt)) || (rc = check_yuv_source(fn, pr, &ys2, s2->in_fmt))) return rc;
-  const int chain_order = (ys.out_order ^ (pr->swap_rb ? 1 : 0)) & 1;
-  SEL_REQUIRE(ys2.out_order == chain_order, "src2->out_order must state the byte order the select works in: src->out_order ^ params->swap_rb");
-  const bool planar = sk && sk->out_fmt >= 4;
-  const int nplanes = planar ? 3 : 1;
-  if ((rc = sk ? check_yuv_sink(fn, pr, sk, chain_order, false) : check_rgba_dest(fn, pr, cv, false))) return rc;
-  const int fw = cv ? cv->nwidth : pr->dw, fh = cv ? cv->nheight : pr->dh;      // the figure's frame, and the RGBA destination's
-  uintptr_t pb = 0, sb = 0, sb2 = 0;
-  for (int i = 0; i < ntracks; i++) {
-    const lgpu_chain_yuv_mix_track &t = tracks[i];
-    // a packed layer is its y plane alone: its chroma pointers are not read, so they may be null and are no plane a destination could collide with
-    const uint8_t *const planes[3] = {t.y_d, packed1 ? nullptr : t.u_d, packed1 ? nullptr : t.v_d};
-    const uint8_t *const u2 = packed2 ? nullptr : t.u2_d, *const v2 = packed2 ? nullptr : t.v2_d;
-    if ((rc = check_track(fn, planes, packed1 ? 1 : 3, false, nullptr, false, t.dst_d, nplanes, !sk))) return rc;
-    SEL_REQUIRE(t.y2_d && (packed2 || (u2 && v2)), "null layer-2 plane");
-    for (int k = 0; k < nplanes; k++)
-      SEL_REQUIRE((const uint8_t *)t.dst_d[k] != t.y2_d && (const uint8_t *)t.dst_d[k] != u2 && (const uint8_t *)t.dst_d[k] != v2, "a destination plane is one of layer 2's planes");
-    sb |= (uintptr_t)t.y_d; sb2 |= (uintptr_t)t.y2_d; pb |= (uintptr_t)t.dst_d[0];
-  }
-  // the one-launch form; anything else is refused, never run some other way
-  if (pr->sw != pr->dw || pr->sh != pr->dh) SEL_REFUSE("frames that keep their size only (sw == dw, sh == dh)");
-  if (pr->do_blur) SEL_REFUSE("the gaussian is not offered with a 4:2:0 or 4:2:2 source");
-  // K3 reads a macropixel as one aligned dword; the reference divides that rowstride by 4 (docs/QUIRKS.md, K3-c): there is no behaviour to follow elsewhere
-  if (packed1 && !multiple_of(sb | (uintptr_t)ys.istrides[0], 4)) SEL_REFUSE("a UYVY / YUYV source is read as 4-byte macropixels (plane and rowstride % 4 == 0)");
-  if (packed2 && !multiple_of(sb2 | (uintptr_t)ys2.istrides[0], 4)) SEL_REFUSE("a UYVY / YUYV layer 2 is read as 4-byte macropixels (plane and rowstride % 4 == 0)");
-  if (sk) {
-    if (sk->out_fmt == 5) SEL_REFUSE("YUV422P is not served (the RGBA form + lgpu_rgb_to_yuv_batch)");
-    if (planar && (pr->dh & 1)) SEL_REFUSE("the 4:2:0 sink needs an even height");
-    // a lane stores one macropixel (4 bytes) or one luma pair (2 bytes) per row; chroma samples are single bytes
-    if (!multiple_of(pb | (uintptr_t)sk->orow[0], planar ? 2 : 4))
-      SEL_REFUSE("packed sinks are stored as 4-byte macropixels (plane and rowstride % 4 == 0), the 4:2:0 luma plane as 2-byte pairs (plane and rowstride % 2 == 0)");
-  }
-  const int drow = sk ? sk->orow[0] : pr->orow;
-  if ((rc = check_plane_sizes(fn, {(long long)pr->sh * ys.istrides[0], ys.u_size, ys.v_size, (long long)fh * drow, (long long)pr->sh * ys2.istrides[0], ys2.u_size, ys2.v_size,
-                                   planar ? (long long)(pr->dh >> 1) * sk->orow[1] : 0, planar ? (long long)(pr->dh >> 1) * sk->orow[2] : 0}))) return rc;
+// k_flat_select's arguments from the plan (flat_plan.h): one function per struct
+static SelArgs sel_args(const FlatPlan &p, const FlatLayer &l1, const FlatLayer &l2, int kind, const TransGeom &g) {
   SelArgs a;
   memset(&a, 0, sizeof a);
-  if (planar && (rc = cavg_forms_checked())) return rc;
-  if (sk && (rc = get_sink_tables(sk->which_tables, sk->in_order, &a.stab))) return rc;
-  auto layer_of = [](const lgpu_yuv_source &y, bool packed, int in_fmt) {
-    SelLayer L;
-    L.tables = device_tables()->yuv2rgb[y.which_tables & 3];
-    L.usize = (uint32_t)y.u_size; L.vsize = (uint32_t)y.v_size; L.ys = y.istrides[0]; L.us = y.istrides[1]; L.vs = y.istrides[2];
-    L.clamped = !packed && !(y.which_tables & 1);      // K3 indexes its tables with the sample itself
-    L.lowq = y.pb_quality == 1; L.fix_edges = (y.flags & LGPU_YUV_FIX_EDGES) ? 1 : 0; L.sfmt = packed ? in_fmt : 0;
-    return L;
-  };
-  a.l1 = layer_of(ys, packed1, s1->in_fmt); a.l2 = layer_of(ys2, packed2, s2->in_fmt);
-  // one staged copy of the K2 tables serves both layers when they index the same set the same way (flat.hip's rule for the mix forms)
-  if (a.l2.tables == a.l1.tables && a.l2.clamped == a.l1.clamped) a.l2.tables = nullptr;
-  a.w = pr->sw; a.h = pr->sh; a.orow = drow;
-  a.urow = planar ? sk->orow[1] : 0; a.vrow = planar ? sk->orow[2] : 0;
-  if (cv) { a.cw = cv->nwidth; a.ch = cv->nheight; a.ox = cv->offs_x; a.oy = cv->offs_y; }
-  a.use_lut = pr->use_lut ? 1 : 0; a.fmt = sk ? sk->out_fmt : 0; a.unclamped = sk ? (sk->which_tables & 1) : 0;
+  flat_fill_layer(a.l1, l1);
+  flat_fill_layer(a.l2, l2);
+  if (flat_tables_shared(l1, l2)) a.l2.tables = nullptr;
+  flat_fill_frame(a, p);
+  a.kind = kind; a.fw = p.fw; a.fh = p.fh; a.wb = g.wb; a.ihwidth = g.ihwidth; a.ihheight = g.ihheight;
+  return a;
+}
+template <int NDST> static void sel_fill_tracks(SelTracksT<NDST> &T, const FlatPlan &p, const FlatTrack *tr, const lgpu_select *sel, int t0, int n, const TransGeom &g) {
+  memset(&T, 0, sizeof T);
+  for (int i = 0; i < n; i++) {
+    const FlatTrack &t = tr[t0 + i];
+    T.y[i] = t.y; T.u[i] = t.u; T.v[i] = t.v; T.y2[i] = t.y2; T.u2[i] = t.u2; T.v2[i] = t.v2;
+    for (int k = 0; k < p.nplanes; k++) T.dst[k][i] = t.dst[k];
+    T.mask[i] = sel->kind == LGPU_SELECT_DISSOLVE ? sel->mask_d[t0 + i] : nullptr;
+    T.amt[i] = transition_amount(g, sel->kind, 4, 0, sel->amounts[t0 + i]);
+  }
+}
+
+// lgpu_chain_flat_yuv_select (include/lives_gpu_select.h): the select's own checks -- kind, amounts, masks -- then the refusal sequence of every unscaled form
+// (flat_plan): LGPU_E_BADARG before LGPU_E_UNSUPPORTED, everything before anything is allocated or enqueued
+extern "C" int lgpu_chain_flat_yuv_select(const lgpu_chain_params *pr, const lgpu_yuv_layer_source *s1, const lgpu_yuv_layer_source *s2, const lgpu_select *sel,
+                                          const lgpu_canvas *cv, const lgpu_chain_sink *sk, const lgpu_chain_yuv_mix_track *tracks, int ntracks, void *stream) {
+  int rc = ensure_init();
+  if (rc) return rc;
+  LGPU_REQUIRE(pr && s1 && s2 && sel && tracks && ntracks > 0 && ntracks <= LGPU_CHAIN_MAX_TRACKS, "params, both sources, the select and 1..64 tracks required");
+  LGPU_REQUIRE(s1->in_fmt >= 2 && s1->in_fmt <= 5 && s2->in_fmt >= 2 && s2->in_fmt <= 5, "in_fmt must be 2 (UYVY), 3 (YUYV), 4 (YUV420P) or 5 (YUV422P) on either layer");
+  LGPU_REQUIRE(!(cv && sk), "a canvas and a sink together: chroma rows would straddle the bar / frame edge");
+  const int kind = sel->kind;
+  LGPU_REQUIRE(kind == LGPU_SELECT_IRIS_RECT || kind == LGPU_SELECT_IRIS_CIRCLE || kind == LGPU_SELECT_DISSOLVE,
+               "kind must be 0 (iris rectangle), 1 (iris circle) or 3 (dissolve); the other transitions show layer 1 at a shifted position or need both layers");
+  LGPU_REQUIRE(sel->amounts, "null amounts");
+  for (int i = 0; i < ntracks; i++) LGPU_REQUIRE(std::isfinite(sel->amounts[i]) && sel->amounts[i] >= 0. && sel->amounts[i] <= 1., "a transition amount is a finite number in 0..1");
+  if (kind == LGPU_SELECT_DISSOLVE) {
+    LGPU_REQUIRE(sel->mask_d, "dissolve needs the table of mask pointers");
+    for (int i = 0; i < ntracks; i++) {
+      LGPU_REQUIRE(sel->mask_d[i], "null dissolve mask");
+      LGPU_REQUIRE(multiple_of((uintptr_t)sel->mask_d[i], 4), "a dissolve mask is read as floats (address % 4 == 0)");
+    }
+  }
+  const FlatLayer l1 = flat_layer(s1), l2 = flat_layer(s2);
+  FlatTrack tr[LGPU_CHAIN_MAX_TRACKS];
+  flat_tracks(tr, tracks, ntracks, l1.packed);
+  FlatPlan p;
+  if ((rc = flat_plan("lgpu_chain_flat_yuv_select", true, "frames that keep their size only (sw == dw, sh == dh)", pr, l1, &l2, cv, sk, tr, ntracks, nullptr, &p))) return rc;
   // the figure, on the frame lgpu_transition / lgpu_dissolve would be run on: 4-byte pixels at the canvas's size
-  const TransGeom g = transition_geometry(kind, fw, fh, 4);
-  a.kind = kind; a.fw = fw; a.fh = fh; a.wb = g.wb; a.ihwidth = g.ihwidth; a.ihheight = g.ihheight;
-  const Lut8 l = pack_lut(pr->use_lut ? pr->lut8 : nullptr);
-  const int hw = pr->sw >> 1, nunits = pr->sh / 2 + 1;
-  const unsigned gx = cdiv((unsigned)hw, 256u);
-  const long long bar_px = cv ? (long long)fw * fh - (long long)pr->sw * pr->sh : 0;
+  const TransGeom g = transition_geometry(kind, p.fw, p.fh, 4);
+  SelArgs a = sel_args(p, l1, l2, kind, g);
   hipStream_t st = (hipStream_t)stream;
   for (int t0 = 0; t0 < ntracks; t0 += LGPU_CHAIN_SELECT_TRACKS) {
     const int n = std::min(LGPU_CHAIN_SELECT_TRACKS, ntracks - t0);
-    // about kFlatWgTarget workgroups per launch, each walking a run of consecutive units on one staging of the tables (flat.hip's launch shape)
-    const int cap = std::max(1, (int)(kFlatWgTarget / ((long long)gx * n)));
-    int gy = std::min(nunits, cap);
-    a.per = (nunits + gy - 1) / gy;
-    gy = (nunits + a.per - 1) / a.per;
-    a.gy_units = gy;
-    const unsigned bar_gy = bar_px > 0 ? (unsigned)std::min<long long>(64, (bar_px + 1024ll * gx - 1) / (1024ll * gx)) : 0u;
-    const dim3 grid(gx, (unsigned)gy + bar_gy, (unsigned)n);
-    auto fill = [&](auto &T) {
-      memset(&T, 0, sizeof T);
-      for (int i = 0; i < n; i++) {
-        const lgpu_chain_yuv_mix_track &t = tracks[t0 + i];
-        T.y[i] = t.y_d; T.u[i] = t.u_d; T.v[i] = t.v_d; T.y2[i] = t.y2_d; T.u2[i] = t.u2_d; T.v2[i] = t.v2_d;
-        for (int k = 0; k < nplanes; k++) T.dst[k][i] = t.dst_d[k];
-        T.mask[i] = kind == LGPU_SELECT_DISSOLVE ? sel->mask_d[t0 + i] : nullptr;
-        T.amt[i] = transition_amount(g, kind, 4, 0, sel->amounts[t0 + i]);
-      }
-    };
+    const FlatShape s = flat_launch_shape(p, n);
+    a.per = s.per; a.gy_units = s.gy_units;
     // THE dispatch point: 3 sinks x SRC x SRC2 x SWAP
-#define SEL_LAUNCH_L2(SK, SR, S2) do {                                                                                               \
-      SelTracksT<SK == 2 ? 3 : 1> T;                                                                                                 \
-      fill(T);                                                                                                                       \
-      if (chain_order) hipLaunchKernelGGL((k_flat_select<1, SK, SR, S2>), grid, dim3(256), 0, st, a, T, l);                         \
-      else hipLaunchKernelGGL((k_flat_select<0, SK, SR, S2>), grid, dim3(256), 0, st, a, T, l);                                     \
-    } while (0)
-#define SEL_LAUNCH_SRC(SK, SR) do { if (srcp2 == 2) SEL_LAUNCH_L2(SK, SR, 2); else if (srcp2 == 1) SEL_LAUNCH_L2(SK, SR, 1); else SEL_LAUNCH_L2(SK, SR, 0); } while (0)
-#define SEL_LAUNCH(SK) do { if (srcp == 2) SEL_LAUNCH_SRC(SK, 2); else if (srcp == 1) SEL_LAUNCH_SRC(SK, 1); else SEL_LAUNCH_SRC(SK, 0); } while (0)
-    if (planar) SEL_LAUNCH(2); else if (sk) SEL_LAUNCH(1); else SEL_LAUNCH(0);
-#undef SEL_LAUNCH
-#undef SEL_LAUNCH_SRC
-#undef SEL_LAUNCH_L2
+    with_constant<3>(p.sink, [&](auto sink) { with_constant<3>(l1.policy, [&](auto src) { with_constant<3>(l2.policy, [&](auto src2) { with_constant<2>(p.chain_order, [&](auto swap) {
+      constexpr int SK = decltype(sink)::value;
+      SelTracksT<SK == 2 ? 3 : 1> T;
+      sel_fill_tracks(T, p, tr, sel, t0, n, g);
+      hipLaunchKernelGGL((k_flat_select<decltype(swap)::value, SK, decltype(src)::value, decltype(src2)::value>), s.grid, dim3(256), 0, st, a, T, p.lut);
+    }); }); }); });
     LGPU_CHECK_LAUNCH();
   }
   return LGPU_OK;
-#undef SEL_REQUIRE
-#undef SEL_REFUSE
 }

@@ -1,13 +1,12 @@
 // flat_walk.h -- the per-cell conversions of the unscaled one-launch forms: a lane's cell (unit, chroma column k) of a decoded YUV420P / YUV422P / UYVY / YUYV frame as
 // two or four finished RGBA pixels.  flat.hip's k_flat_yuv420 (one layer, or both layers at every cell: the chroma blend) and flat_select.hip's k_flat_select (the layer
-// a pixel SHOWS, decided before anything is loaded) walk the same cells through these functions, so the two forms cannot drift apart.
+// a pixel SHOWS, decided before anything is loaded) walk the same cells through these functions, so the two forms cannot drift apart.  The staging of K2's paired
+// tables (flat_stage_k2) and the decode of a bar pixel (flat_bar_xy) are here for the same reason.  The kernels' host side is flat_plan.h.
 #pragma once
 #include "lgpu_common.h"
 #include "k2_walk.h"
 
 namespace lgpu {
-
-constexpr int kFlatWgTarget = 2048;       // workgroups a launch aims at: each walks nunits * gx * ntracks / 2048 units (at least one) on one staging of the tables
 
 // an address or pitch as a multiple of n (a power of two).  Every alignment decision of flat.hip and flat_select.hip goes through it, in the kernel and in the entry points;
 // tests/test_chain_flat.py walks each class they tell apart (test_chain_flat_addresses, test_chain_flat_refusals)
@@ -22,6 +21,25 @@ struct FlatPlanes {
 };
 struct FlatK2Lds { const uint32_t *ty; const uint2 *rg, *gb; };
 template <int KIND> struct FlatCell { static constexpr int value = KIND; };      // 0: row 0, 1: a row pair, 2: the trailing row
+
+// K2's tables, paired, staged into LDS by the workgroup's 256 lanes: the entry of an UNCLAMPED blended chroma value e is tables[clamp(e)] (CLAMP16_240 is 16 below 16
+// and 240 from 0xF0 up on 0..255).  clamped: the layer's own chroma clamp in the index (a packed layer indexes with the sample itself).  Every layer of both kernels
+// is staged here: layer 2 has its own copy when its table set or its index clamp differs (flat_plan.h, flat_tables_shared)
+__device__ __forceinline__ void flat_stage_k2(int tid, const int32_t *tables, int clamped, uint32_t *ty, uint2 *rg, uint2 *gb) {
+  const int clo = clamped ? 16 : 0, chi = clamped ? 240 : 255;
+  const int ec = tid < clo ? clo : tid > chi ? chi : tid;
+  ty[tid] = (uint32_t)tables[tid];
+  rg[tid] = make_uint2((uint32_t)tables[256 + ec], (uint32_t)tables[768 + ec]);
+  gb[tid] = make_uint2((uint32_t)tables[512 + ec], (uint32_t)tables[1024 + ec]);
+}
+
+// pixel q of the canvas's bars as (x, y) on the canvas: the `top` pixels above the frame, the `bottom` ones below it, then the sw = cw - w of each of the frame's h
+// rows, left bar and right.  The w x h frame sits at (ox, oy) on a canvas cw wide
+__device__ __forceinline__ void flat_bar_xy(int q, int top, int bottom, int sw, int cw, int ox, int oy, int w, int h, int &x, int &y) {
+  if (q < top) { y = q / cw; x = q - y * cw; }
+  else if (q < top + bottom) { q -= top; y = q / cw; x = q - y * cw; y += oy + h; }
+  else { q -= top + bottom; y = q / sw; x = q - y * sw; y += oy; if (x >= ox) x += w; }
+}
 
 // xyuv2rgb on the paired tables; the chroma index is the blended value itself.  SWAP & 1: the pixel is BGRA.
 // SWAP & 2 (k_flat_select passes SWAP | 2 to the walks below): the same pixel packed with two byte permutes (selector 0x0C = 0x00, 0x0D = 0xFF), as palette.hip's

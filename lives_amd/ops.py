@@ -412,6 +412,21 @@ class RgbDelay:
             self.h = None
 
 
+def _amounts(amounts, ntracks):
+    """a blend amount per track as the c_uint8[] the chain_* entry points take; None (with LGPU_INTERP_NOBLEND, 0x400, in params.interp) stays None"""
+    return (ctypes.c_uint8 * max(1, ntracks))(*[int(a) & 0xFF for a in amounts]) if amounts is not None else None
+
+
+def _ref(struct):
+    """byref of an optional argument struct (canvas, sink); None is the null pointer"""
+    return ctypes.byref(struct) if struct is not None else None
+
+
+def _call(name, args, check):
+    """check=False returns the library's code instead of raising (tests of the refusals)"""
+    return lib.call(name, *args) if check else getattr(lib.load(), name)(*args)
+
+
 def chain_params(sw, sh, irow, dw, dh, irow2, orow, swap_rb=1, interp=3, do_blur=0, bf=128, lut=None, param_block=None):
     p = lib.ChainParams()
     p.param_block_d = param_block.data_ptr() if param_block is not None else None
@@ -442,9 +457,9 @@ def chain_canvas(params, tracks, nwidth, nheight, offs_x, offs_y):
 
 def chain_amounts(params, tracks, amounts, canvas=None):
     """lgpu_chain_amounts: the chain with a blend amount per track; canvas = (nwidth, nheight, offs_x, offs_y) or None"""
-    am = (ctypes.c_uint8 * len(tracks))(*[int(a) & 0xFF for a in amounts]) if amounts is not None else None      # None: with LGPU_INTERP_NOBLEND (0x400) in params.interp
+    am = _amounts(amounts, len(tracks))
     cv = lib.Canvas(*canvas) if canvas is not None else None
-    lib.call("lgpu_chain_amounts", ctypes.byref(params), ctypes.byref(cv) if cv is not None else None, tracks, len(tracks), am, stream_ptr())
+    lib.call("lgpu_chain_amounts", ctypes.byref(params), _ref(cv), tracks, len(tracks), am, stream_ptr())
 
 
 def chain_yuv_tracks(ys, us, vs, layer2s, dsts):
@@ -468,12 +483,10 @@ def yuv_source(istrides, u_size, v_size, out_order=0, which_tables=0, pb_quality
 def chain_yuv420p(params, src, tracks, amounts, canvas=None, check=True):
     """lgpu_chain_yuv420p: the chain of lgpu_chain_amounts starting at 4:2:0 frames, one launch; canvas = (nwidth, nheight, offs_x, offs_y) or None.
     check=False returns the library's code instead of raising (tests of the refusals)"""
-    am = (ctypes.c_uint8 * len(tracks))(*[int(a) & 0xFF for a in amounts]) if amounts is not None else None      # None: with LGPU_INTERP_NOBLEND (0x400) in params.interp
+    am = _amounts(amounts, len(tracks))
     cv = lib.Canvas(*canvas) if canvas is not None else None
-    args = (ctypes.byref(params), ctypes.byref(src), ctypes.byref(cv) if cv is not None else None, tracks, len(tracks), am, stream_ptr())
-    if not check:
-        return lib.load().lgpu_chain_yuv420p(*args)
-    return lib.call("lgpu_chain_yuv420p", *args)
+    args = (ctypes.byref(params), ctypes.byref(src), _ref(cv), tracks, len(tracks), am, stream_ptr())
+    return _call("lgpu_chain_yuv420p", args, check)
 
 
 def chain_sink(out_fmt, orow, which_tables=0, in_order=0):
@@ -500,11 +513,9 @@ def chain_sink_tracks(srcs, layer2s, dst_planes):
 def chain_to_yuv(params, sink, tracks, amounts, check=True):
     """lgpu_chain_to_yuv: the chain of lgpu_chain_amounts ending at a YUV sink, one launch and no RGBA frame.  check=False returns the library's code instead of
     raising (tests of the refusals)"""
-    am = (ctypes.c_uint8 * max(1, len(tracks)))(*[int(a) & 0xFF for a in amounts]) if amounts is not None else None      # None: with LGPU_INTERP_NOBLEND (0x400) in params.interp
+    am = _amounts(amounts, len(tracks))
     args = (ctypes.byref(params), ctypes.byref(sink), tracks, len(tracks), am, stream_ptr())
-    if not check:
-        return lib.load().lgpu_chain_to_yuv(*args)
-    return lib.call("lgpu_chain_to_yuv", *args)
+    return _call("lgpu_chain_to_yuv", args, check)
 
 
 def chain_yuv_sink_tracks(ys, us, vs, layer2s, dst_planes):
@@ -524,32 +535,26 @@ def chain_yuv_sink_tracks(ys, us, vs, layer2s, dst_planes):
 def chain_yuv420p_to_yuv(params, src, sink, tracks, amounts, check=True):
     """lgpu_chain_yuv420p_to_yuv: the chain of lgpu_chain_amounts from 4:2:0 frames to a YUV sink, one launch and no RGBA frame at either end.  check=False returns
     the library's code instead of raising (tests of the refusals)"""
-    am = (ctypes.c_uint8 * max(1, len(tracks)))(*[int(a) & 0xFF for a in amounts]) if amounts is not None else None      # None: with LGPU_INTERP_NOBLEND (0x400) in params.interp
+    am = _amounts(amounts, len(tracks))
     args = (ctypes.byref(params), ctypes.byref(src), ctypes.byref(sink), tracks, len(tracks), am, stream_ptr())
-    if not check:
-        return lib.load().lgpu_chain_yuv420p_to_yuv(*args)
-    return lib.call("lgpu_chain_yuv420p_to_yuv", *args)
+    return _call("lgpu_chain_yuv420p_to_yuv", args, check)
 
 
 def chain_flat_yuv420p(params, src, tracks, amounts, canvas=None, check=True):
     """lgpu_chain_flat_yuv420p: lgpu_yuv420p_to_rgb + lgpu_chain_amounts on frames that keep their size (sw == dw, sh == dh), one launch and no converted frame;
     arguments as chain_yuv420p.  check=False returns the library's code instead of raising (tests of the refusals)"""
-    am = (ctypes.c_uint8 * max(1, len(tracks)))(*[int(a) & 0xFF for a in amounts]) if amounts is not None else None      # None: with LGPU_INTERP_NOBLEND (0x400) in params.interp
+    am = _amounts(amounts, len(tracks))
     cv = lib.Canvas(*canvas) if canvas is not None else None
-    args = (ctypes.byref(params), ctypes.byref(src), ctypes.byref(cv) if cv is not None else None, tracks, len(tracks), am, stream_ptr())
-    if not check:
-        return lib.load().lgpu_chain_flat_yuv420p(*args)
-    return lib.call("lgpu_chain_flat_yuv420p", *args)
+    args = (ctypes.byref(params), ctypes.byref(src), _ref(cv), tracks, len(tracks), am, stream_ptr())
+    return _call("lgpu_chain_flat_yuv420p", args, check)
 
 
 def chain_flat_yuv420p_to_yuv(params, src, sink, tracks, amounts, check=True):
     """lgpu_chain_flat_yuv420p_to_yuv: the same frames to a YUV sink (UYVY / YUYV / YUV420P), one launch and no RGBA frame at either end; arguments as
     chain_yuv420p_to_yuv.  check=False returns the library's code instead of raising (tests of the refusals)"""
-    am = (ctypes.c_uint8 * max(1, len(tracks)))(*[int(a) & 0xFF for a in amounts]) if amounts is not None else None      # None: with LGPU_INTERP_NOBLEND (0x400) in params.interp
+    am = _amounts(amounts, len(tracks))
     args = (ctypes.byref(params), ctypes.byref(src), ctypes.byref(sink), tracks, len(tracks), am, stream_ptr())
-    if not check:
-        return lib.load().lgpu_chain_flat_yuv420p_to_yuv(*args)
-    return lib.call("lgpu_chain_flat_yuv420p_to_yuv", *args)
+    return _call("lgpu_chain_flat_yuv420p_to_yuv", args, check)
 
 
 def yuv422_source(in_fmt, istrides, u_size=0, v_size=0, out_order=0, which_tables=0, pb_quality=2):
@@ -566,13 +571,10 @@ def chain_flat_yuv422(params, src, tracks, amounts, sink=None, canvas=None, chec
     """lgpu_chain_flat_yuv422: the unscaled tick from YUV422P / UYVY / YUYV frames, one launch and no converted frame, to RGBA (sink=None, rowstride params.orow,
     optionally into canvas = (nwidth, nheight, offs_x, offs_y)) or to a YUV sink.  tracks: chain_yuv_sink_tracks (a packed frame is the y plane; u / v None).
     check=False returns the library's code instead of raising (tests of the refusals)"""
-    am = (ctypes.c_uint8 * max(1, len(tracks)))(*[int(a) & 0xFF for a in amounts]) if amounts is not None else None      # None: with LGPU_INTERP_NOBLEND (0x400) in params.interp
+    am = _amounts(amounts, len(tracks))
     cv = lib.Canvas(*canvas) if canvas is not None else None
-    args = (ctypes.byref(params), ctypes.byref(src), ctypes.byref(cv) if cv is not None else None, ctypes.byref(sink) if sink is not None else None, tracks, len(tracks),
-            am, stream_ptr())
-    if not check:
-        return lib.load().lgpu_chain_flat_yuv422(*args)
-    return lib.call("lgpu_chain_flat_yuv422", *args)
+    args = (ctypes.byref(params), ctypes.byref(src), _ref(cv), _ref(sink), tracks, len(tracks), am, stream_ptr())
+    return _call("lgpu_chain_flat_yuv422", args, check)
 
 
 def chain_yuv_mix_tracks(ys, us, vs, y2s, u2s, v2s, dst_planes):
@@ -593,11 +595,9 @@ def chain_flat_yuv420p_mix(params, src, src2, tracks, amounts, sink=None, check=
     """lgpu_chain_flat_yuv420p_mix: two decoded 4:2:0 frames of the project's size mixed in one launch, to RGBA (sink=None, rowstride params.orow) or to a YUV sink; no
     RGBA frame anywhere.  src2 describes layer 2 (its out_order is src.out_order ^ params.swap_rb).  check=False returns the library's code instead of raising (tests
     of the refusals)"""
-    am = (ctypes.c_uint8 * max(1, len(tracks)))(*[int(a) & 0xFF for a in amounts]) if amounts is not None else None
-    args = (ctypes.byref(params), ctypes.byref(src), ctypes.byref(src2), ctypes.byref(sink) if sink is not None else None, tracks, len(tracks), am, stream_ptr())
-    if not check:
-        return lib.load().lgpu_chain_flat_yuv420p_mix(*args)
-    return lib.call("lgpu_chain_flat_yuv420p_mix", *args)
+    am = _amounts(amounts, len(tracks))
+    args = (ctypes.byref(params), ctypes.byref(src), ctypes.byref(src2), _ref(sink), tracks, len(tracks), am, stream_ptr())
+    return _call("lgpu_chain_flat_yuv420p_mix", args, check)
 
 
 def yuv_layer_source(in_fmt, istrides, u_size=0, v_size=0, out_order=0, which_tables=0, pb_quality=2, flags=0):
@@ -614,23 +614,19 @@ def chain_flat_yuv_mix(params, src, src2, tracks, amounts, sink=None, check=True
     """lgpu_chain_flat_yuv_mix: two decoded frames of the project's size, each YUV420P, YUV422P, UYVY or YUYV, mixed in one launch, to RGBA (sink=None, rowstride
     params.orow) or to a YUV sink; no RGBA frame anywhere.  src / src2: yuv_layer_source (src2.out_order is src.out_order ^ params.swap_rb); tracks:
     chain_yuv_mix_tracks (a packed frame is the y plane; u / v None).  check=False returns the library's code instead of raising (tests of the refusals)"""
-    am = (ctypes.c_uint8 * max(1, len(tracks)))(*[int(a) & 0xFF for a in amounts]) if amounts is not None else None
-    args = (ctypes.byref(params), ctypes.byref(src), ctypes.byref(src2), ctypes.byref(sink) if sink is not None else None, tracks, len(tracks), am, stream_ptr())
-    if not check:
-        return lib.load().lgpu_chain_flat_yuv_mix(*args)
-    return lib.call("lgpu_chain_flat_yuv_mix", *args)
+    am = _amounts(amounts, len(tracks))
+    args = (ctypes.byref(params), ctypes.byref(src), ctypes.byref(src2), _ref(sink), tracks, len(tracks), am, stream_ptr())
+    return _call("lgpu_chain_flat_yuv_mix", args, check)
 
 
 def chain_flat_yuv_mix_canvas(params, src, src2, tracks, amounts, canvas=None, check=True):
     """lgpu_chain_flat_yuv_mix_canvas: chain_flat_yuv_mix to RGBA with both layers letterboxed onto one canvas = (nwidth, nheight, offs_x, offs_y) of opaque black, the
     bars written by the same launch (rowstride params.orow, canvas-sized).  canvas=None: the bytes of chain_flat_yuv_mix without a sink.  check=False returns the
     library's code instead of raising (tests of the refusals)"""
-    am = (ctypes.c_uint8 * max(1, len(tracks)))(*[int(a) & 0xFF for a in amounts]) if amounts is not None else None
+    am = _amounts(amounts, len(tracks))
     cv = lib.Canvas(*canvas) if canvas is not None else None
-    args = (ctypes.byref(params), ctypes.byref(src), ctypes.byref(src2), ctypes.byref(cv) if cv is not None else None, tracks, len(tracks), am, stream_ptr())
-    if not check:
-        return lib.load().lgpu_chain_flat_yuv_mix_canvas(*args)
-    return lib.call("lgpu_chain_flat_yuv_mix_canvas", *args)
+    args = (ctypes.byref(params), ctypes.byref(src), ctypes.byref(src2), _ref(cv), tracks, len(tracks), am, stream_ptr())
+    return _call("lgpu_chain_flat_yuv_mix_canvas", args, check)
 
 
 def select(kind, amounts, masks=None):
@@ -653,11 +649,8 @@ def chain_flat_yuv_select(params, src, src2, tracks, kind, amounts, masks=None, 
     src2: yuv_layer_source; tracks: chain_yuv_mix_tracks; amounts: 0..1 per track.  check=False returns the library's code instead of raising (tests of the refusals)"""
     sel = select(kind, amounts, masks)
     cv = lib.Canvas(*canvas) if canvas is not None else None
-    args = (ctypes.byref(params), ctypes.byref(src), ctypes.byref(src2), ctypes.byref(sel), ctypes.byref(cv) if cv is not None else None,
-            ctypes.byref(sink) if sink is not None else None, tracks, len(tracks), stream_ptr())
-    if not check:
-        return lib.load().lgpu_chain_flat_yuv_select(*args)
-    return lib.call("lgpu_chain_flat_yuv_select", *args)
+    args = (ctypes.byref(params), ctypes.byref(src), ctypes.byref(src2), ctypes.byref(sel), _ref(cv), _ref(sink), tracks, len(tracks), stream_ptr())
+    return _call("lgpu_chain_flat_yuv_select", args, check)
 
 
 def stream_probe(params, tracks, reps):
