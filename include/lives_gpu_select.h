@@ -54,8 +54,8 @@ typedef struct { int kind;                   /* 0 iris rectangle, 1 iris circle,
    chroma-average forms once.  Nothing else is uploaded: the K2 tables are lgpu_init's.
 
    Out of scope, each for its reason: "4 way split" and "slide over" show layer 1 at a SHIFTED position, and K2's walk depends on the position (the seeded first pair of a
-   row, the chroma rows a row pair reads), so a shifted pixel is not the cell's own conversion; "rand replace" keeps state from frame to frame; the luma overlays need
-   layer 2's luma, that is both layers at every pixel: lgpu_chain_flat_yuv_mix's ground.  Recording a transition class as a deferred stage of the layer seam
+   row, the chroma rows a row pair reads), so a shifted pixel is not the cell's own conversion; "rand replace" keeps state from frame to frame; the luma overlays decide
+   by ONE layer's luma, a predicate that comes from data and not from coordinates: they are lives_gpu_luma.h's lgpu_chain_flat_yuv_luma.  Recording a transition class as a deferred stage of the layer seam
    (lives_gpu_layer.h) is a follow-up; livesgpu_fx.so keeps its classes and its process functions. */
 #define LGPU_CHAIN_SELECT_TRACKS 32   /* tracks per launch of lgpu_chain_flat_yuv_select */
 int lgpu_chain_flat_yuv_select(const lgpu_chain_params *params, const lgpu_yuv_layer_source *src, const lgpu_yuv_layer_source *src2, const lgpu_select *sel,

@@ -8,12 +8,14 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-ma
 OBJ=build
 mkdir -p $OBJ
 pids=()
-for f in runtime swizzle yuv effects resize stencil palette pixbuf fused flat flat_select; do
+for f in runtime swizzle yuv effects resize stencil palette pixbuf fused flat flat_select flat_luma; do
   stale=
-  case $f in yuv|flat|flat_select|pixbuf) [ k2_walk.h -nt $OBJ/$f.o ] && stale=1 ;; esac      # K2's chroma walk, shared by the four
-  case $f in flat|flat_select) { [ flat_walk.h -nt $OBJ/$f.o ] || [ flat_plan.h -nt $OBJ/$f.o ]; } && stale=1 ;; esac      # the unscaled forms' device text and host plan
+  case $f in yuv|flat|flat_select|flat_luma|pixbuf) [ k2_walk.h -nt $OBJ/$f.o ] && stale=1 ;; esac      # K2's chroma walk, shared by the five
+  case $f in flat|flat_select|flat_luma) { [ flat_walk.h -nt $OBJ/$f.o ] || [ flat_plan.h -nt $OBJ/$f.o ]; } && stale=1 ;; esac      # the unscaled forms' device text and host plan
   case $f in effects|flat_select) [ select_pred.h -nt $OBJ/$f.o ] && stale=1 ;; esac         # the iris and dissolve predicates
   case $f in flat_select) [ ../../include/lives_gpu_select.h -nt $OBJ/$f.o ] && stale=1 ;; esac
+  case $f in effects|flat_luma) [ luma_pred.h -nt $OBJ/$f.o ] && stale=1 ;; esac             # the luma overlays' predicate
+  case $f in flat_luma) [ ../../include/lives_gpu_luma.h -nt $OBJ/$f.o ] && stale=1 ;; esac
   if [ ! -f $OBJ/$f.o ] || [ $f.hip -nt $OBJ/$f.o ] || [ lgpu_common.h -nt $OBJ/$f.o ] || [ ../../include/lives_gpu.h -nt $OBJ/$f.o ] || [ -n "$stale" ]; then
     $HIPCC $FLAGS -c $f.hip -o $OBJ/$f.o &
     pids+=($!)

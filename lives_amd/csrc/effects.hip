@@ -11,6 +11,7 @@
 // normalised to one dword per pixel by v_perm), applies a per-pixel functor and stores 4 pixels.
 #include "lgpu_common.h"
 #include "select_pred.h"      // the iris and dissolve predicates, shared with flat_select.hip
+#include "luma_pred.h"        // the luma overlays' predicate, shared with flat_luma.hip
 
 namespace lgpu {
 
@@ -146,11 +147,7 @@ struct LumaTab {
     for (int i = threadIdx.x; i < 768; i += kBlock) lds[i] = gl[i];
     __syncthreads();
   }
-  __device__ __forceinline__ uint32_t luma(uint32_t p, int order) const {
-    const uint32_t c0 = p & 0xFF, c1 = (p >> 8) & 0xFF, c2 = (p >> 16) & 0xFF;
-    const int32_t v = order ? (s[c2] + s[256 + c1] + s[512 + c0]) : (s[c0] + s[256 + c1] + s[512 + c2]);
-    return (uint32_t)(v >> 16) & 0xFF;
-  }
+  __device__ __forceinline__ uint32_t luma(uint32_t p, int order) const { return luma_px(s, p, order); }      // luma_pred.h
 };
 
 // luma overlay (1, 4) / underlay (2) / negative overlay (3): copies 3 bytes from layer 2 or layer 1
@@ -163,9 +160,10 @@ struct LumaBlend {
   __device__ __forceinline__ void setup(int32_t *lds) { t.stage(lds); }
   __device__ __forceinline__ uint32_t operator()(uint32_t p1, uint32_t p2, uint32_t pd) const {
     bool take2;
-    if (type == 2) take2 = t.luma(p2, order) > neg;
-    else if (type == 3) take2 = t.luma(p1, order) > neg;
-    else take2 = t.luma(p1, order) < bf;
+    // luma_pred.h's predicate (k_flat_luma takes the same one)
+    if (type == 2) take2 = LGPU_LUMA_ABOVE(t.luma(p2, order), neg);
+    else if (type == 3) take2 = LGPU_LUMA_ABOVE(t.luma(p1, order), neg);
+    else take2 = LGPU_LUMA_BELOW(t.luma(p1, order), bf);
     const uint32_t c = take2 ? p2 : p1;
     return (c & 0x00FFFFFFu) | (pd & 0xFF000000u);
   }

@@ -20,6 +20,7 @@ LGPU_CHAIN_MAX_TRACKS = 64
 LGPU_CHAIN_MIX_TRACKS = 32
 LGPU_CHAIN_SELECT_TRACKS = 32
 SELECT_IRIS_RECT, SELECT_IRIS_CIRCLE, SELECT_DISSOLVE = 0, 1, 3      # lgpu_select.kind: multi_transitions.c's `type`
+LGPU_CHAIN_LUMA_TRACKS = 32
 
 (SWAP3, SWAP4, SWAP3ADDPOST, SWAP3ADDPRE, SWAP3POSTALPHA, SWAP3PREALPHA, ADDPOST, ADDPRE, SWAP3DELPOST, DELPOST,
  DELPRE, SWAP3DELPRE, SWAPPREPOST) = range(13)
@@ -88,6 +89,11 @@ class YuvLayerSource(ctypes.Structure):
 class Select(ctypes.Structure):
     """lgpu_select (include/lives_gpu_select.h)"""
     _fields_ = [("kind", ci), ("amounts", ctypes.POINTER(cd)), ("mask_d", ctypes.POINTER(vp))]
+
+
+class LumaKey(ctypes.Structure):
+    """lgpu_luma_key (include/lives_gpu_luma.h)"""
+    _fields_ = [("type", ci), ("thresholds", ctypes.POINTER(ctypes.c_uint8))]
 
 
 class Canvas(ctypes.Structure):
@@ -285,6 +291,11 @@ SELECT_PROTOTYPES = {
     "lgpu_chain_flat_yuv_select": [vp, vp, vp, ctypes.POINTER(Select), vp, vp, vp, ci, vp],
 }
 
+# the entry points of include/lives_gpu_luma.h, in a table of their own for the same reason
+LUMA_PROTOTYPES = {
+    "lgpu_chain_flat_yuv_luma": [vp, vp, vp, ctypes.POINTER(LumaKey), vp, vp, vp, ci, vp],
+}
+
 _lib = None
 
 
@@ -296,7 +307,7 @@ def load():
             raise LgpuError("%s is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                             "(lives_amd/csrc/build.sh).  There is no CPU fallback." % SO_PATH)
         lib = ctypes.CDLL(SO_PATH)
-        for name, args in list(PROTOTYPES.items()) + list(SELECT_PROTOTYPES.items()):
+        for name, args in list(PROTOTYPES.items()) + list(SELECT_PROTOTYPES.items()) + list(LUMA_PROTOTYPES.items()):
             fn = getattr(lib, name)
             fn.argtypes = args
             fn.restype = ci

@@ -653,6 +653,27 @@ def chain_flat_yuv_select(params, src, src2, tracks, kind, amounts, masks=None, 
     return _call("lgpu_chain_flat_yuv_select", args, check)
 
 
+def luma_key(type, thresholds):
+    """lgpu_luma_key: type 1 luma overlay / 2 underlay / 3 negative overlay / 4 averaged overlay (== 1) and one threshold (0..255) per track.  The array it points to
+    is kept alive on the returned struct"""
+    k = lib.LumaKey()
+    k.type = type
+    k._thresholds = (ctypes.c_uint8 * max(1, len(thresholds)))(*[int(t) for t in thresholds]) if thresholds is not None else None
+    k.thresholds = ctypes.cast(k._thresholds, ctypes.POINTER(ctypes.c_uint8)) if k._thresholds is not None else None
+    return k
+
+
+def chain_flat_yuv_luma(params, src, src2, tracks, type, thresholds, sink=None, canvas=None, check=True):
+    """lgpu_chain_flat_yuv_luma (include/lives_gpu_luma.h): two decoded frames of the project's size, each YUV420P, YUV422P, UYVY or YUYV, through a luma overlay -- type 1
+    overlay, 2 underlay, 3 negative overlay, 4 averaged overlay -- in one launch that converts the keyed layer everywhere and the other layer only where it is shown;
+    to RGBA (sink=None, rowstride params.orow; canvas = (nwidth, nheight, offs_x, offs_y) letterboxes both layers) or to a YUV sink.  src / src2: yuv_layer_source;
+    tracks: chain_yuv_mix_tracks; thresholds: 0..255 per track.  check=False returns the library's code instead of raising (tests of the refusals)"""
+    key = luma_key(type, thresholds)
+    cv = lib.Canvas(*canvas) if canvas is not None else None
+    args = (ctypes.byref(params), ctypes.byref(src), ctypes.byref(src2), ctypes.byref(key), _ref(cv), _ref(sink), tracks, len(tracks), stream_ptr())
+    return _call("lgpu_chain_flat_yuv_luma", args, check)
+
+
 def stream_probe(params, tracks, reps):
     """lgpu_debug_stream_probe: the chain's algorithmic bytes as a bare stream on the same frames, ms for `reps` launches (destinations left dirty)"""
     ms = ctypes.c_float()
